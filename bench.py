@@ -6,6 +6,13 @@
          bench.py --gpus N --steps K --warmup W         (the launcher provides RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT)
 
   python bench.py --config c2|c3|c4|c5                  (one line per BASELINE config; default c4 = the headline)
+  python bench.py ... --full                            (also everything beside the headline, see below)
+  python bench.py ... --dump-outputs DIR                (after the timed steps: what the last step returned, DIR/<name>.npy)
+
+A plain run sets up, warms up (W steps), times ONE window of exactly K steps and prints the line: `value`, `ms_per_step` and
+the workload description.  `--full` adds what takes runs of its own: two more K-step windows (the line then carries the
+median window and the spread), per-kernel HIP-event times and the rooflines, the ECM loop, the calibration-fold batch, the
+opt-in throughput mode, the CPU baseline and, with N > 1, the final track gather, `per_rank` and `expected`.
 
 Default workload = BASELINE config 4 (BASELINE.json metric "genomic bins/sec (forward+backward pass), hg38 200bp x 32 samples"):
 22 synthetic chains with the hg38 autosome bin counts at 200 bp (14 375 018 bins), m = 32 samples, levelTrend model,
@@ -28,7 +35,7 @@ workload 808 of 2.9e7 filtered-state values differ from the oracle's, all of the
 6-iteration kappa-ECM on a chr1-sized hard chain every bin stays within 0.10 x the 1e-5 gate (tests/test_hard_data.py).  The
 opt-in 2-ulp throughput mode (a single pass within a few float32 ulps of the reference -- half of the filtered values differ in
 their last bits --, gated on all 22 chromosomes by test_bench_workload_matches_oracle and on hard data by test_hard_data.py) is
-reported beside it as `throughput_mode`.
+reported beside it as `throughput_mode` (--full).
 
 No PyTorch: a launcher only provides the rank environment; the barrier and the max-over-ranks of the timed region are RCCL
 all-reduces on the library's stream (consenrich_amd.sharding.RcclComm -> csr_comm_* in libconsenrich_amd.so, librccl
@@ -183,6 +190,48 @@ def cpu_baseline(m: int, max_seconds: float = 15.0, forward_only: bool = False, 
     }
 
 
+DUMP_BUDGET_BYTES = 60 * 2**20     # below the 64 MB a dump may hold in all
+DUMP_MAX_ROWS = 1 << 17            # sampled bins (and bin-to-bin transitions) per job
+DUMP_SEED = 20240607
+
+
+def dump_outputs(batch, lens, forward_only: bool, sums, out_dir: str, prefix: str = "", share: int = 1):
+    """Write what the last timed step returned (`sums` = its per-chain (sumD, sumNLL)) and the arrays it exported, as
+    out_dir/<prefix><name>.npy.  Per-bin arrays (D, xf, Pf, and unless forward-only xs, Ps, resid) hold the rows of a fixed,
+    seeded sample of the batch's bins, in bin order over the chains as configured; pNoise and lagCov (n - 1 rows per chain)
+    those of a sample of the transitions.  Same arguments -> same sample."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    d, m = batch.d, batch.m
+    per_bin = ["D", "xf", "Pf"] + ([] if forward_only else ["xs", "Ps", "resid"])
+    per_step = ["pnoise"] + ([] if forward_only else ["lag"])
+    row_shape = {"D": (), "xf": (d,), "Pf": (d, d), "xs": (d,), "Ps": (d, d), "resid": (m,), "pnoise": (d, d), "lag": (d, d)}
+    row_bytes = 4 * sum(int(np.prod(row_shape[k])) for k in per_bin + per_step)
+    rows = max(1, min(DUMP_MAX_ROWS, DUMP_BUDGET_BYTES // (row_bytes * max(share, 1))))
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(counts):
+        total = int(sum(counts))
+        idx = np.sort(rng.choice(total, size=min(rows, total), replace=False)) if total else np.zeros(0, np.int64)
+        starts = np.concatenate([[0], np.cumsum(counts)])
+        chain = np.searchsorted(starts, idx, side="right") - 1
+        return chain, idx - starts[chain]
+
+    out = {}
+    for names, counts in ((per_bin, list(lens)), (per_step, [max(n - 1, 0) for n in lens])):
+        chain, local = sample(counts)
+        for name in names:
+            parts = [np.zeros((0, *row_shape[name]), np.float32)]
+            for c in np.unique(chain):
+                parts.append(batch.download(int(c), name)[local[chain == c]])
+            out[name] = np.concatenate(parts)
+    out["sumD"], out["sumNLL"] = (np.asarray(s, np.float64) for s in sums)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), arr)
+    return sorted(out)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -194,13 +243,22 @@ def parse_args(argv=None):
     ap.add_argument("--samples", type=int, default=None, help="override the config's sample count")
     ap.add_argument("--bin-bp", type=int, default=None, help="override the config's bin size")
     ap.add_argument("--q0", default="1e-3,1e-4", help="diagonal of the base process noise Q0 (long-memory regime: 1e-5,1e-6)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the throughput-mode, ECM and calibration-fold measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: three timed windows, per-kernel times and rooflines, the extras, the CPU "
+                         "baseline, and with N > 1 the track gather, per_rank and expected")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned to DIR/<name>.npy (a fixed, seeded "
+                         "sample of the per-bin arrays; at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-gather", action="store_true", help="with --full: skip the final track gather")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the throughput-mode, ECM and calibration-fold measurements")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: every rank uses GPU 0 (no RCCL: file barrier)")
     ap.add_argument("--fake-ranks", action="store_true",
                     help="CPU rehearsal of the launcher and control plane: no GPU, no measurement; rank 0 prints a stub line")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs writes what the last timed step returned: needs --steps >= 1")
     cfg = CONFIGS[args.config]
     if args.samples is None:
         args.samples = cfg["samples"]
@@ -320,13 +378,15 @@ def main() -> int:
     def max_over_ranks(v: float) -> float:
         return comm.allreduce_max(v) if comm is not None else v
 
+    last = {}
+
     def timed(b, fn, warmup, steps):
         for _ in range(warmup):
             fn()
         fence(b)
         t0 = time.perf_counter()
         for _ in range(steps):
-            fn()
+            last["ret"] = fn()
         fence(b)
         return max_over_ranks(time.perf_counter() - t0)
 
@@ -384,14 +444,20 @@ def main() -> int:
         return out
 
     # ---- the headline: the library's default mode --------------------------------------------------------------------
-    # three timed windows of exactly K steps each (every one bracketed by barrier + synchronize, max over ranks); the line
-    # carries the MEDIAN window (a latency-bound step's time depends on which chain is the unlucky one: box-to-box and
-    # window-to-window spread is several per cent) and the spread beside it
-    windows = sorted(timed(batch, lambda: one_step(batch), args.warmup if w == 0 else 0, args.steps) for w in range(3))
-    elapsed = windows[1]
+    # a timed window of exactly K steps (bracketed by barrier + synchronize, max over ranks).  --full times three such windows
+    # and the line carries the MEDIAN one (a latency-bound step's time depends on which chain is the unlucky one: box-to-box
+    # and window-to-window spread is several per cent) and the spread beside it
+    n_windows = 3 if args.full else 1
+    windows = sorted(timed(batch, lambda: one_step(batch), args.warmup if w == 0 else 0, args.steps) for w in range(n_windows))
+    elapsed = windows[len(windows) // 2]
     ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
     value = total_bins * args.steps / elapsed
-    per_kernel = profile_kernels(batch, args.steps)
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step returned, before anything else runs on this batch
+        dumped = dump_outputs(batch, my_lens, args.forward_only, last["ret"], args.dump_outputs,
+                              prefix="" if world == 1 else f"rank{rank}_", share=world)
+    per_kernel = profile_kernels(batch, args.steps) if args.full else {}
     rs = batch.run_stats()
     roofline = roofline_of(per_kernel, rs["x_tol_ulps"])
     # the dominant bandwidth-bound kernel beside it (what an HBM roofline is meaningful for)
@@ -414,7 +480,7 @@ def main() -> int:
 
     # what fits: c2 is a forward-only line (no ECM, no folds); three more copies of c5 (59 GB each) beside the two resident
     # batches would not leave headroom in 288 GB
-    do_ecm = not args.no_extras and not args.forward_only
+    do_ecm = args.full and not args.no_extras and not args.forward_only
     do_folds = do_ecm and my_bins * (16.0 * m + 400.0) * 4.0 < 200e9
     if do_ecm:
         # (1) the ECM loop -- what real runs execute: 5 x [forward, smoother + kappa E-step] + 1 NLL forward
@@ -444,7 +510,7 @@ def main() -> int:
         extras["with_calibration_folds"]["ecm_ms_per_iter"] = 1000.0 * efe / ecm_iters
         extras["with_calibration_folds"]["ecm_bin_sweeps_per_s"] = total_bins * (folds + 1) * ecm_iters * inner / efe
         fb.close()
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # (3) the opt-in throughput mode (2-ulp carry acceptance): same step, same outputs within a few float32 ulps
         tb = DeviceBatch(local_rank, x_tol_ulps=2)
         tb.configure(model, m, my_lens)
@@ -480,13 +546,15 @@ def main() -> int:
             return [v]
         return [comm.allreduce_sum(v if r == rank else 0.0) for r in range(world)]
 
-    state_ms = (roofline or {}).get("avg_launch_ms", 0.0) if (roofline or {}).get("kernel") == "fwd_state" else \
-        per_kernel.get("fwd_state_chain", {}).get("ms_per_step", 0.0)
-    ranks_info = {"fwd_state_ms": per_rank(float(state_ms)), "longest_chain_bins": [int(v) for v in per_rank(float(max(my_lens)))],
-                  "bins": [int(v) for v in per_rank(float(my_bins))]}
+    ranks_info = None
+    if args.full:
+        state_ms = (roofline or {}).get("avg_launch_ms", 0.0) if (roofline or {}).get("kernel") == "fwd_state" else \
+            per_kernel.get("fwd_state_chain", {}).get("ms_per_step", 0.0)
+        ranks_info = {"fwd_state_ms": per_rank(float(state_ms)), "longest_chain_bins": [int(v) for v in per_rank(float(max(my_lens)))],
+                      "bins": [int(v) for v in per_rank(float(my_bins))]}
 
     gather_ms, gather_note = None, comm_note
-    if comm_kind == "rccl" and not args.no_gather:
+    if args.full and comm_kind == "rccl" and not args.no_gather:
         # final track gather (state + its variance): once per job, packed on the device from the exported arrays and
         # all-gathered over RCCL / xGMI; not part of `value`.  A failure here must not cost the measurement its JSON line.
         try:
@@ -509,7 +577,8 @@ def main() -> int:
             "metric": args.metric,
             "value": value, "unit": "genomic bins/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "ms_per_step_min": 1000.0 * windows[0] / max(args.steps, 1),
-            "ms_per_step_median": ms_per_step, "ms_per_step_max": 1000.0 * windows[2] / max(args.steps, 1), "timed_windows": 3,
+            "ms_per_step_median": ms_per_step, "ms_per_step_max": 1000.0 * windows[-1] / max(args.steps, 1),
+            "timed_windows": n_windows,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f64 arithmetic on f32 storage", "data": "synthetic",
             "config": {
@@ -521,7 +590,7 @@ def main() -> int:
                              "stats + forward(store,NLL) + RTS backward + lagCov + reference-layout tracks + residuals, "
                              "levelTrend, constant process noise (no per-bin lambda / kappa / qScale, one Q0 for every chain: "
                              "the case of a plain forward + backward call; the ECM loop's sweeps carry kappa per bin and are "
-                             "reported under `ecm`)"),
+                             "reported under `ecm` with --full)"),
                 "mfma": "not eligible: the observation update is a length-m weighted reduction per bin (pyx:443-456), no dense "
                         "contraction at any m; the bound is HBM",
                 "chains_per_rank": "LPT over contigs", "block_len": rs["block_len"], "q0_diag": [q00, q11],
@@ -531,23 +600,24 @@ def main() -> int:
                 "comm": comm_kind, "n_ranks_seen": n_ranks_seen,
             },
             "build": L.build_id(),
-            "roofline": roofline,
-            "roofline_streaming": roofline_streaming,
             "path_roofline": {"alg_bytes_per_bin": bytes_per_bin, "achieved": value * bytes_per_bin / 1e9,
                               "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
                               "frac": value * bytes_per_bin / 1e9 / (HBM_PEAK_GBS * world)},
-            "kernels_rank0": per_kernel,
             "speculation": {"blocks": rs["blocks"], "reruns_cov": rs["reruns_p"], "reruns_state": rs["reruns_x"],
                             "reruns_bwd": rs["reruns_b"], "fix_launches": rs["fix_launches"],
                             "pipeline_redos": rs["pipeline_redos"],
                             # bit-exact steps: groups of chains whose tail was launched on its own (step_pipelined), and single
                             # launches of the state chain that gave up on a bounded wait (the pass form ran instead)
                             "tail_groups": rs.get("tail_groups", 0), "state_chain_bailouts": rs.get("sb_bailouts", 0)},
-            "gather_ms": gather_ms,
-            "per_rank": ranks_info,
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full:
+            out.update({"roofline": roofline, "roofline_streaming": roofline_streaming, "kernels_rank0": per_kernel,
+                        "gather_ms": gather_ms, "per_rank": ranks_info})
         out.update(extras)
-        if world > 1 and args.config == "c4":
+        if args.full and world > 1 and args.config == "c4":
             out["expected"] = expected_speedup(ranks_info["bins"], total_bins)
             # measured against the model: > 1 = faster than the emulated shards said
             out["speedup_vs_expected"] = out["expected"]["default"]["ms_per_step"] / ms_per_step
@@ -555,7 +625,7 @@ def main() -> int:
                 out["throughput_mode"]["speedup_vs_expected"] = out["expected"]["ulp2"]["ms_per_step"] / out["throughput_mode"]["ms_per_step"]
         if gather_note:
             out["gather_note"] = gather_note
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(m, forward_only=args.forward_only, n_bins=args.single_chain)
         print(json.dumps(out))
         sys.stdout.flush()

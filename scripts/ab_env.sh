@@ -5,7 +5,7 @@ REPS=${REPS:-4}
 ARGS=${ARGS:-"--steps 30"}
 for i in $(seq $REPS); do
   for val in "$A" "$B"; do
-    env $VAR=$val python3 bench.py $ARGS --no-cpu-baseline --no-extras 2>/dev/null | VAL="$val" VARN="$VAR" python3 -c '
+    env $VAR=$val python3 bench.py $ARGS --full --no-cpu-baseline --no-extras 2>/dev/null | VAL="$val" VARN="$VAR" python3 -c '
 import sys, json, os
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print("%s=%s  ms/step %.4f (min %.4f max %.4f)" % (os.environ["VARN"], os.environ["VAL"], d["ms_per_step"], d["ms_per_step_min"], d["ms_per_step_max"]))'

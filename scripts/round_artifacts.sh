@@ -15,9 +15,9 @@ for part in $PART; do
 case $part in
 bench)
   for c in c4 c2 c3 c5; do
-    timeout -k 10 600 python3 bench.py --config $c > $O/${R}_bench_$c.json 2> $O/bench_$c.err || echo "bench $c FAILED"
+    timeout -k 10 600 python3 bench.py --config $c --full > $O/${R}_bench_$c.json 2> $O/bench_$c.err || echo "bench $c FAILED"
     rm -rf $O/kt
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 bench.py --config $c --no-cpu-baseline --no-extras > $O/${R}_bench_${c}_under_rocprofv3.json 2> $O/kt_$c.err || echo "rocprof bench $c FAILED"
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 bench.py --config $c --full --no-cpu-baseline --no-extras > $O/${R}_bench_${c}_under_rocprofv3.json 2> $O/kt_$c.err || echo "rocprof bench $c FAILED"
     cp "$(find $O/kt -name '*kernel_stats.csv' | head -1)" $O/${R}_kernel_stats_$c.csv
     rm -rf $O/kt
     echo "bench $c done"
@@ -25,7 +25,7 @@ bench)
   cp $O/${R}_bench_c4.json $O/${R}_bench.json
   # long-memory process noise (the floor the reference's Q0 seed clamps to is 1e-6): windows lengthen, repair runs multiply
   for q in 1e-5,1e-6 1e-6,1e-7; do
-    timeout -k 10 600 python3 bench.py --config c4 --q0 $q --no-cpu-baseline > $O/${R}_bench_q0_$q.json 2> $O/bench_q0_$q.err || echo "bench q0 $q FAILED"
+    timeout -k 10 600 python3 bench.py --config c4 --q0 $q --full --no-cpu-baseline > $O/${R}_bench_q0_$q.json 2> $O/bench_q0_$q.err || echo "bench q0 $q FAILED"
   done
   # the throughput-mode steps of c4 under the kernel trace (the bench line's `throughput_mode`)
   XTOL=2 STEPS=3 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktx -o kt -- python3 scripts/one_step.py > $O/ktx.log 2>&1

@@ -3,7 +3,7 @@
 set -e
 for v in ${VARIANTS:-"BASE=1" "BASE=2"}; do
   echo "== $v"
-  env $v python bench.py --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | python -c "
+  env $v python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernels_rank0']

@@ -6,6 +6,7 @@ case parameters (seeds / shapes / flags, or small literal matrices) and the refe
 re-synthesised from the seed by tests/golden/cases.py, which both this script and the tests import.
 
 Usage:  python tests/golden/make_golden.py          (rewrites every fixture, then cross-checks the C oracle bit-for-bit)
+        python tests/golden/make_golden.py --live   (rewrites live_reference.json alone)
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ import bg_cases  # noqa: E402
 import unc_cases  # noqa: E402
 import qseed_cases  # noqa: E402
 import cases  # noqa: E402
+import live_cases  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from oracle import qseed as orc_qseed  # noqa: E402
 from oracle import ref_loader  # noqa: E402
@@ -33,6 +35,12 @@ def main() -> int:
     if ref is None:
         print("reference build not available (make -C oracle ref)", file=sys.stderr)
         return 2
+    if "--live" in sys.argv[1:]:
+        from consenrich import cuncertainty as ref_unc  # noqa: E402  (compiled by `make -C oracle ref`)
+
+        write_live_record(ref, ref_unc)
+        print(f"{os.path.basename(live_cases.RECORD)} written; oracle == reference on it")
+        return 0
     n_written = 0
     for case in cases.all_cases():
         out_ref = cases.run_case(ref, case)
@@ -100,8 +108,35 @@ def main() -> int:
         qseed_cases.same(out_ref, out_orc)
         np.savez_compressed(os.path.join(HERE, case["name"] + ".npz"), **out_ref)
         n_written += 1
+    write_live_record(ref, ref_unc)
+    n_written += 1
     print(f"{n_written} fixtures written; oracle == reference on all of them")
     return 0
+
+
+def write_live_record(ref, ref_unc) -> None:
+    """live_reference.json: what the reference returns on the inputs of the oracle tests' live comparisons (live_cases.py)."""
+    import json
+
+    rec = {"golden": {}, "background": {}, "uncertainty": {}}
+    for name in live_cases.GOLDEN_CASES:
+        case = next(c for c in cases.all_cases() if c["name"] == name)
+        rec["golden"][name] = live_cases.record(cases.run_case(ref, case))
+    for key, (w, r, lam, zc, lam_first) in live_cases.background_inputs():
+        rec["background"][key] = live_cases.record({"x": ref.csolveZeroCenteredBackground(w, r, lam, zc, lamFirst=lam_first)})
+    rec["uncertainty"]["live"] = live_cases.record(unc_cases.run(ref_unc, live_cases.UNC_CASE))
+    spec = ref_unc.cmakeFoldSpec(*live_cases.FOLD_SPEC_ARGS)
+    rec["uncertainty"]["fold_spec"] = live_cases.record({str(i): np.asarray(a) for i, a in enumerate(spec)})
+    with open(live_cases.RECORD, "w") as fh:
+        json.dump(rec, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    # the oracle against the record just written
+    for name in live_cases.GOLDEN_CASES:
+        case = next(c for c in cases.all_cases() if c["name"] == name)
+        live_cases.check("golden", name, cases.run_case(orc, case))
+    for key, (w, r, lam, zc, lam_first) in live_cases.background_inputs():
+        live_cases.check("background", key, {"x": orc.csolveZeroCenteredBackground(w, r, lam, zc, lamFirst=lam_first)})
+    live_cases.check("uncertainty", "live", unc_cases.run(orc, live_cases.UNC_CASE))
 
 
 if __name__ == "__main__":

@@ -313,3 +313,51 @@ def test_bench_line_helpers_read_the_committed_records():
     exp = bench.expected_speedup(bins, sum(lengths))
     assert 1.5 < exp["default"]["speedup_vs_1gpu"] < 3.0 and 4.5 < exp["ulp2"]["speedup_vs_1gpu"] < 7.67, exp
     assert os.path.isfile(os.path.join(root, bench.TRAFFIC_FILES[0])) and os.path.isfile(os.path.join(root, bench.TRAFFIC_FILES[2]))
+
+
+def test_bench_dump_is_a_fixed_sample_of_the_returned_arrays(tmp_path):
+    """`bench.py --dump-outputs`: the rows written are the returned arrays' own rows at a seeded sample of bins (transitions for
+    pNoise / lagCov), the same sample for the same batch, float32 / float64 only, within the 64 MB budget."""
+    import importlib
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+
+    class Batch:                # what dump_outputs reads of a DeviceBatch: d, m, download(chain, name)
+        d, m = 2, 32
+        lens = [700000, 1, 2, 300000, 5]
+
+        def download(self, chain, name):
+            n = self.lens[chain]
+            rows = n - 1 if name in ("pnoise", "lag") else n
+            shape = {"D": (), "xf": (2,), "xs": (2,), "resid": (self.m,)}.get(name, (2, 2))
+            base = np.arange(rows, dtype=np.float64).reshape((rows,) + (1,) * len(shape))
+            return np.broadcast_to(base + 1e6 * chain, (rows, *shape)).astype(np.float32)
+
+    b = Batch()
+    sums = (np.arange(5) * 1.5, np.arange(5) * -2.0)
+    names = bench.dump_outputs(b, b.lens, False, sums, str(tmp_path / "a"))
+    assert set(names) == {"D", "xf", "Pf", "pnoise", "xs", "Ps", "lag", "resid", "sumD", "sumNLL"}
+    bench.dump_outputs(b, b.lens, False, sums, str(tmp_path / "b"))
+    total = 0
+    for n in names:
+        a, c = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, c), n
+        total += os.path.getsize(tmp_path / "a" / f"{n}.npy")
+    assert total <= 64 * 2**20
+    resid = np.load(tmp_path / "a" / "resid.npy")
+    assert resid.shape == (bench.DUMP_MAX_ROWS, 32) and np.all(resid == resid[:, :1])
+    # every sampled row IS a row of its chain's array (chain in the millions, bin index below), rows in bin order, no repeats
+    D = np.load(tmp_path / "a" / "D.npy").astype(np.float64)
+    chain, local = np.floor(D / 1e6), D % 1e6
+    assert np.all(np.diff(D) > 0) and set(np.unique(chain)) <= set(range(5))
+    assert all(local[chain == c].max() < b.lens[int(c)] for c in np.unique(chain))
+    lag = np.load(tmp_path / "a" / "lag.npy")
+    assert lag.shape == (bench.DUMP_MAX_ROWS, 2, 2) and 1 not in set(np.floor(lag[:, 0, 0] / 1e6).astype(int))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "sumNLL.npy"), sums[1])
+    # forward only: the forward exports alone
+    fwd = bench.dump_outputs(b, b.lens, True, sums, str(tmp_path / "f"))
+    assert set(fwd) == {"D", "xf", "Pf", "pnoise", "sumD", "sumNLL"}

@@ -2245,14 +2245,14 @@ def test_lds_dma_paths_agree_with_the_plain_kernels(product, block_len, flags_na
 
 
 def test_bench_line_contract(product):
-    """bench.py prints ONE JSON line with the driver's contract fields plus the roofline object (2 steps, no extras)."""
+    """bench.py --full prints ONE JSON line with the driver's contract fields plus the roofline object (2 steps, no extras)."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-extras"], capture_output=True, text=True, timeout=600, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -2273,6 +2273,46 @@ def test_bench_line_contract(product):
     assert rs["kernel"] in ("stats", "residuals") and 0.2 < rs["frac"] < 1.0
 
 
+def test_plain_bench_times_k_steps_and_dumps_what_the_last_one_returned(product, tmp_path):
+    """A plain bench.py run times one window of exactly K steps and measures nothing beside the headline; --dump-outputs
+    writes the last step's returns as float .npy files (a fixed sample of the per-bin arrays, within 64 MB), and a second
+    run with the same arguments writes the same values."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
+        assert len(out) == 1, out
+        lines[tag] = json.loads(out[0])
+    d = lines["a"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["timed_windows"] == 1 and d["full"] is False
+    assert d["value"] == pytest.approx(14375018 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    for key in ("roofline", "kernels_rank0", "cpu_baseline", "throughput_mode", "ecm", "with_calibration_folds"):
+        assert key not in d, key
+    names = {"D", "xf", "Pf", "pnoise", "xs", "Ps", "lag", "resid", "sumD", "sumNLL"}
+    assert set(d["dumped_outputs"]) == names
+    assert {f for f in os.listdir(tmp_path / "a")} == {n + ".npy" for n in names}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 2**20
+    for n in sorted(names):
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and a.size > 0, n
+        assert np.all(np.isfinite(a)), n
+        if n in ("sumD", "sumNLL"):
+            assert a.shape == (22,), n
+            np.testing.assert_allclose(a, b, rtol=1e-12, atol=0.0, err_msg=n)
+        else:
+            assert np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "resid.npy").shape[1:] == (32,)
+
+
 def test_bench_started_plainly_with_two_ranks_on_one_gpu(product):
     """`python bench.py --gpus 2` started plainly (no launcher): the parent spawns its two rank processes, which shard the
     genome and meet through the job's directory; --same-device puts both on GPU 0 (RCCL refuses two ranks on one device, so the
@@ -2284,7 +2324,8 @@ def test_bench_started_plainly_with_two_ranks_on_one_gpu(product):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--same-device", "--steps", "2", "--warmup",
-                        "1", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
+                        "1", "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=900, cwd=root,
+                       env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
     assert len(lines) == 1, lines

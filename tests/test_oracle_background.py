@@ -1,6 +1,6 @@
 """CPU tests pinning the oracle's background-update natives (oracle/consenrich_oracle.c
 `cor_solve_background`, `cor_background_stats`) to the REAL reference: committed golden vectors (bit for bit,
-including the pivot-modification error text), the live reference build when present, the reference's own literal test
+including the pivot-modification error text), the reference's recorded outputs and its live build when present, the reference's own literal test
 values (tests/test_core.py:95-110) and an independent dense specification."""
 import os
 import sys
@@ -11,6 +11,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import bg_cases  # noqa: E402
+import live_cases  # noqa: E402
 
 from oracle import oracle as orc  # noqa: E402
 from oracle import ref_loader  # noqa: E402
@@ -58,17 +59,15 @@ def test_oracle_stats_match_golden():
     np.testing.assert_allclose(r, np.sum(inv.astype(np.float64) * res.astype(np.float64), axis=0), rtol=1e-7)
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference build only exists in the build container")
 def test_oracle_matches_live_reference():
+    """Bit for bit: against what the reference returned (recorded, tests/golden/live_reference.json) and, where its build
+    exists, against the reference itself."""
     ref = ref_loader.load()
-    rng = np.random.default_rng(3)
-    for n in (6, 131, 4099):
-        w = np.abs(rng.normal(50, 20, n))
-        r = rng.normal(0, 10, n)
-        for lam_first, lam in ((0.0, 0.0), (3.0, 0.0), (0.0, 40.0), (1e3, 1e7)):
-            for zc in (False, True):
-                assert np.array_equal(ref.csolveZeroCenteredBackground(w, r, lam, zc, lamFirst=lam_first),
-                                      orc.csolveZeroCenteredBackground(w, r, lam, zc, lamFirst=lam_first))
+    for key, (w, r, lam, zc, lam_first) in live_cases.background_inputs():
+        got = orc.csolveZeroCenteredBackground(w, r, lam, zc, lamFirst=lam_first)
+        live_cases.check("background", key, {"x": got})
+        if ref is not None:
+            assert np.array_equal(ref.csolveZeroCenteredBackground(w, r, lam, zc, lamFirst=lam_first), got), key
 
 
 def test_reference_literals_and_dense_specification():

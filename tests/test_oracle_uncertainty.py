@@ -1,6 +1,7 @@
 """CPU: the oracle's delete-block calibration natives (oracle/consenrich_oracle.c
 `cor_total_information`, `cor_fold_mask_information`) against golden vectors captured from the compiled reference
-(cuncertainty.pyx:97-157, 160-305) -- bit for bit -- and live against it where it exists; argument validation."""
+(cuncertainty.pyx:97-157, 160-305) -- bit for bit -- and live against it where it exists (else against its
+recorded outputs); argument validation."""
 import os
 import sys
 
@@ -9,6 +10,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
+import live_cases  # noqa: E402
 import unc_cases  # noqa: E402
 
 from oracle import oracle as orc  # noqa: E402
@@ -27,17 +29,22 @@ def test_oracle_matches_golden(name):
         assert np.array_equal(got[k], gold[k], equal_nan=True), k
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference build only exists in the build container")
 def test_oracle_matches_live_reference_and_fold_spec():
-    ref_loader.load()
+    """Bit for bit: against what the reference returned (recorded, tests/golden/live_reference.json) and, where its build
+    exists, against the reference itself."""
+    case = live_cases.UNC_CASE
+    b = unc_cases.run(orc, case)
+    live_cases.check("uncertainty", "live", b)
+    spec = unc_cases.fold_spec(*live_cases.FOLD_SPEC_ARGS)
+    live_cases.check("uncertainty", "fold_spec", {str(i): np.asarray(x) for i, x in enumerate(spec)})
+    if ref_loader.load() is None:
+        return
     from consenrich import cuncertainty as ref
 
-    case = dict(name="live", m=5, n=777, block_len=20, folds=3, rho=0.15, use_lam=True, f64=False, seed=99)
-    a, b = unc_cases.run(ref, case), unc_cases.run(orc, case)
+    a = unc_cases.run(ref, case)
     for k in a:
         assert np.array_equal(a[k], b[k], equal_nan=True), k
-    spec = unc_cases.fold_spec(5, 777, 20, 3, 0.5, 100)
-    assert all(np.array_equal(x, y) for x, y in zip(spec, ref.cmakeFoldSpec(5, 777, 20, 3, 0.5, 100)))
+    assert all(np.array_equal(x, y) for x, y in zip(spec, ref.cmakeFoldSpec(*live_cases.FOLD_SPEC_ARGS)))
 
 
 def test_validation_messages():
