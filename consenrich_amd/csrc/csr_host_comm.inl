@@ -167,7 +167,7 @@ extern "C" int csr_batch_gather_tracks(csr_ctx *c, csr_comm *k, int64_t cap_bins
     if (!c->nat[CSR_ARR_XS] || !c->nat[CSR_ARR_PS]) return fail("smoothed tracks were not exported (CSR_EXPORT_SMOOTH)");
     // the natural arrays must hold the RESIDENT fit: a later ecm / forward_backward / background_apply without an export
     // would otherwise be gathered as stale tracks
-    if (!c->haveBwd || c->natSmoothGen != c->fitGen)
+    if (!c->haveBwd || !c->where[CSR_ARR_XS].nat || !c->where[CSR_ARR_PS].nat)
         return fail("the exported smoothed tracks are not those of the resident fit: export (CSR_EXPORT_SMOOTH) after the last pass");
     const int nc = (int)c->chains.size();
     int64_t mine = 0;

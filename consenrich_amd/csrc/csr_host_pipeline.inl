@@ -403,13 +403,38 @@ static int ensure_sb_view(csr_ctx *c) {
     return 0;
 }
 
+// A reader needs the blocked copies of arrays whose resident result may stand in the reference layout only (xf / Pf in front of a
+// smoother that reads blocks, xs / Ps / lag in front of a MASKED pass that rewrites the blocks of its own chains only): those that
+// are not .blocked come back through LDS tiles.  (A masked import leaves the other chains stale.)
+static int need_blocked(csr_ctx *c, std::initializer_list<int> ids, const unsigned char *active) {
+    bool any = false;
+    for (int id : ids) any = any || !c->where[id].blocked;
+    if (!any) return 0;
+    Prm p = c->p;
+    p.chainActive = active;
+    const dim3 grid((int)(c->NG * (c->B / 32)));
+    Scope sc(c, "state_reblock_out");
+    for (int id : ids) {
+        if (c->where[id].blocked) continue;
+        const float *src = c->nat[id];
+        if (id == CSR_ARR_XF || id == CSR_ARR_XS)
+            hipLaunchKernelGGL(k_import_tiled<float2>, grid, dim3(256), 0, c->stream, p, reinterpret_cast<const float2 *>(src),
+                               id == CSR_ARR_XF ? p.tXf : p.tXs, (int64_t)0);
+        else
+            hipLaunchKernelGGL(k_import_tiled<float4>, grid, dim3(256), 0, c->stream, p, reinterpret_cast<const float4 *>(src),
+                               id == CSR_ARR_PF ? p.tPf : (id == CSR_ARR_PS ? p.tPs : p.tLag), (int64_t)0);
+        if (active == nullptr) c->where[id].blocked = true;
+    }
+    LAUNCH_CHECK("k_import_tiled");
+    return 0;
+}
+
 // Bit-exact state chain, systolic form (k_sb_sys): the gain / statistics records go to the natural layout (one tiled
 // conversion launch), one wavefront per superblock walks 64 bins per batch as a shift register and writes the filtered state
 // straight into the reference-layout xf array; superblocks start from the cold prior and the validation / repair passes run
 // to the fixed point (= the sequential recursion, whatever the superblock length); one tiled launch brings the filtered state
 // back into the batch's blocked layout for the epilogue and the smoother.
 static int early_cov_exports(csr_ctx *c, const Prm &p, uint32_t flags, bool withPf);
-static int ensure_blocked_fwd(csr_ctx *c, const unsigned char *active);
 // phase 0: the whole chain.  phase 1 (a step that pipelines its tail per chain, step_pipelined): stop right after the launch of
 // the barrier-free kernel, with per-chain "done" words the host can watch -- c->sbp.active says that this happened (otherwise
 // the whole chain ran, as in phase 0).  phase 2: wait for that launch (or run the pass form if it bailed out); the filtered
@@ -555,7 +580,7 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
                            reinterpret_cast<const float2 *>(natXf), p.tXf, (int64_t)0);
     }
     LAUNCH_CHECK("k_import_tiled_f2");
-    c->xfNat = true;
+    produced(c, {CSR_ARR_XF}, W_BLOCKED | W_NAT);
     return 0;
 }
 
@@ -647,10 +672,10 @@ static int early_cov_exports(csr_ctx *c, const Prm &p, uint32_t flags, bool with
     // stored it; per-chain base matrices: a table -- so that a step with multipliers pipelines its tail as well)
     const bool convQ = withPf && !constQ;
     if (!withPf && !constQ) return 0;
-    const bool doPf = withPf && !c->pfNat;          // (the covariance chain may have written Pf in the reference layout itself)
+    const bool doPf = withPf && !c->where[CSR_ARR_PF].nat;      // (the covariance chain may have written Pf in the reference layout itself)
     const bool fill = constQ && !pn_fill_current(c, p);
-    if (constQ && !fill) c->pnNat = true;           // the array already holds this constant fill
-    if (!doPf && !fill && !convQ) { if (withPf) c->pfNat = true; return 0; }
+    if (constQ) produced(c, {CSR_ARR_PNOISE}, W_NAT);           // (filled below unless the array already holds this constant fill)
+    if (!doPf && !fill && !convQ) return 0;
     // (a reference-layout array is allocated -- and zeroed ON THE MAIN STREAM -- at its first use: before the fork, so that the
     // side stream's writes are ordered behind the zeroing)
     float *dstPf = nullptr, *dstPn = nullptr;
@@ -680,12 +705,9 @@ static int early_cov_exports(csr_ctx *c, const Prm &p, uint32_t flags, bool with
         hipLaunchKernelGGL(k_export_tiled, dim3((int)(c->NG * (c->B / 32))), dim3(256), 0, c->side, p, L);
     }
     LAUNCH_CHECK("k_export_tiled (early Pf)");
-    if (withPf) c->pfNat = true;
-    if (convQ) { c->pnNat = true; c->pnFillValid = false; }
-    if (fill) {
-        CHECK(launch_pn_fill(c, p, dstPn, c->side));
-        c->pnNat = true;
-    }
+    if (doPf) c->where[CSR_ARR_PF].nat = true;
+    if (convQ) { produced(c, {CSR_ARR_PNOISE}, W_BLOCKED | W_NAT); c->pnFillValid = false; }
+    if (fill) CHECK(launch_pn_fill(c, p, dstPn, c->side));
     HIPOK(hipEventRecord(c->evPf, c->side));
     c->pfPending = true;
     return 0;
@@ -702,10 +724,10 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
     // a MASKED pass rewrites the blocked xf / Pf of its own chains only: when the resident pass left them in the reference layout
     // alone, the chains outside the mask get their blocked copies back first (they keep their resident results)
     // (whether or not new statistics have invalidated those results since: the masked chains get new ones, the others keep the old)
-    if (active != nullptr && (c->fwdBlockedStale || c->pfBlockedStale)) CHECK(ensure_blocked_fwd(c, nullptr));
+    if (active != nullptr) CHECK(need_blocked(c, {CSR_ARR_XF, CSR_ARR_PF}, nullptr));
     c->sbp.active = false;
     join_pf(c);         // (an early export nobody asked for afterwards still reads the arrays this pass overwrites)
-    c->pfNat = c->pnNat = false;
+    new_forward_pass(c);        // GAP: claims a current blocked D for the chains outside a mask even when the resident pass wrote D in the reference layout only
     c->gainNat = false;
     Prm p = c->p;
     p.flags = flags;
@@ -718,11 +740,6 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
     p.storePP = (wantD || !c->sweepSkipQ) ? 1 : 0;
     c->fwdQCompact = p.qFromKappa != 0;
     defer = defer && c->deferEnabled;
-    c->fwdNat = false;
-    c->xfNat = false;
-    c->dNat = false;
-    c->fwdBlockedStale = false;
-    c->pfBlockedStale = false;
     c->pendFwdNat = natOut;
     const bool seq = (flags & F_APN) && !(flags & F_QSCALE);
     if (seq) {
@@ -732,7 +749,7 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
         LAUNCH_CHECK("k_fwd_apn");
     } else {
         bool dP = defer && c->optimistic[ST_P], dX = defer && c->optimistic[ST_X];
-        bool nisInChain = false, natOnly = false;
+        bool nisInChain = false;
         if (wantD && natOut && c->natOutEnabled && c->natOutD) {        // D straight into the reference layout
             const size_t tileBytes = sizeof(float) * 64 * (size_t)(c->B + 1);
             bool ok = true;
@@ -744,7 +761,7 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
             }
             if (ok) {
                 CHECK(nat_array(c, CSR_ARR_D, &p.natD));
-                c->dNat = true;
+                produced(c, {CSR_ARR_D}, W_NAT);
             }
         }
         // Fused chain (tolerant mode).  Its state recursion warms up on SPECULATIVE gains (the split state chain reads the
@@ -770,7 +787,7 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
                 CHECK(nat_array(c, CSR_ARR_XF, &p.natXs));
                 CHECK(nat_array(c, CSR_ARR_PF, &p.natPs));
                 p.natOut = 1;
-                c->fwdNat = true;
+                produced(c, {CSR_ARR_XF, CSR_ARR_PF}, W_BLOCKED | W_NAT);
                 // the constant process noise depends on nothing: its reference-layout rows are filled on the side stream beside
                 // the (latency-bound) forward chain instead of after the smoother
                 if (c->earlyPf && active == nullptr) CHECK(early_cov_exports(c, p, flags, false));
@@ -785,7 +802,7 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
                 // reference-layout arrays through its tiles): the tile walker stores nothing in the blocked layout
                 if (c->natOnlyEnabled && p.qFromMult && p.chainQ == nullptr && (nisInChain || !wantD) && (c->B % 8) == 0 && unit_f(c, p)) {
                     p.natOnly = 1;
-                    natOnly = true;
+                    produced(c, {CSR_ARR_XF, CSR_ARR_PF}, W_NAT);
                 }
             }
             if (c->mdl.state_dim == 2 && unit_f(c, p)) CHECK(run_chain<FwdTrendFusedT<true>>(c, p, "fwd_chain", "fwd_fix", ST_P, dP));
@@ -795,7 +812,6 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
             p.ckptIn = nullptr; p.ckptOut = nullptr; p.ckptSaveWarm = 0;
             c->lastFwdWindow = c->fwdWindow;
             c->fwdWindow = nullptr;
-            c->fwdBlockedStale = natOnly;
         } else if (c->mdl.state_dim == 2) {
             c->lastFwdWindow = nullptr;
             const bool sbX = c->xTolUlps == 0 && c->sbState && !c->seqState;
@@ -818,12 +834,12 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
                 pc.natPs = nullptr;
                 if (natOut && c->earlyPf && active == nullptr && c->natOutEnabled) {
                     CHECK(nat_array(c, CSR_ARR_PF, &pc.natPs));
-                    c->pfNat = true;
+                    produced(c, {CSR_ARR_PF}, W_BLOCKED | W_NAT);
                     // a pipelined step with one constant process noise: the smoother of every group reads xf / Pf in the reference
                     // layout (k_smooth_natin) -- no blocked copy of Pf
                     if (c->natOnlyEnabled && split && p.qFromMult && p.chainQ == nullptr && (c->B % 8) == 0 && unit_f(c, p)) {
                         pc.natOnly = 1;
-                        c->pfBlockedStale = true;
+                        produced(c, {CSR_ARR_PF}, W_NAT);
                     }
                 }
                 c->gainNat = true;
@@ -892,46 +908,6 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
     return 0;
 }
 
-// The resident forward pass left xf / Pf in the reference layout only and a reader needs the blocked copies after all (a
-// smoother pass without reference-layout outputs, per-chain base matrices): bring them back through LDS tiles.
-static int ensure_blocked_fwd(csr_ctx *c, const unsigned char *active) {
-    if (!c->fwdBlockedStale && !c->pfBlockedStale) return 0;
-    float *natXf, *natPf;
-    CHECK(nat_array(c, CSR_ARR_XF, &natXf));
-    CHECK(nat_array(c, CSR_ARR_PF, &natPf));
-    Prm p = c->p;
-    p.chainActive = active;
-    Scope sc(c, "state_reblock_out");
-    if (c->fwdBlockedStale)
-        hipLaunchKernelGGL(k_import_tiled<float2>, dim3((int)(c->NG * (c->B / 32))), dim3(256), 0, c->stream, p,
-                           reinterpret_cast<const float2 *>(natXf), p.tXf, (int64_t)0);
-    hipLaunchKernelGGL(k_import_tiled<float4>, dim3((int)(c->NG * (c->B / 32))), dim3(256), 0, c->stream, p,
-                       reinterpret_cast<const float4 *>(natPf), p.tPf, (int64_t)0);
-    LAUNCH_CHECK("k_import_tiled");
-    if (active == nullptr) c->fwdBlockedStale = c->pfBlockedStale = false;      // (a masked import leaves the other chains stale)
-    return 0;
-}
-
-// The resident smoother wrote xs / Ps / lag in the reference layout only (a step, forward_backward) and a MASKED ECM call is about
-// to rewrite the blocked copies of its own chains: the chains outside the mask get theirs back first, so that the conversions
-// that follow the call (exports, per-phase tracks, the background update: all from the blocked copies) return what is resident.
-static int ensure_blocked_smooth(csr_ctx *c) {
-    if (!c->smoothNat || c->mdl.state_dim != 2 || !c->nat[CSR_ARR_XS] || !c->nat[CSR_ARR_PS] || !c->nat[CSR_ARR_LAG]) return 0;
-    float *xs, *Ps, *lag;
-    CHECK(nat_array(c, CSR_ARR_XS, &xs));
-    CHECK(nat_array(c, CSR_ARR_PS, &Ps));
-    CHECK(nat_array(c, CSR_ARR_LAG, &lag));
-    Prm p = c->p;
-    p.chainActive = nullptr;
-    const dim3 grid((int)(c->NG * (c->B / 32)));
-    Scope sc(c, "state_reblock_out");
-    hipLaunchKernelGGL(k_import_tiled<float2>, grid, dim3(256), 0, c->stream, p, reinterpret_cast<const float2 *>(xs), p.tXs, (int64_t)0);
-    hipLaunchKernelGGL(k_import_tiled<float4>, grid, dim3(256), 0, c->stream, p, reinterpret_cast<const float4 *>(Ps), p.tPs, (int64_t)0);
-    hipLaunchKernelGGL(k_import_tiled<float4>, grid, dim3(256), 0, c->stream, p, reinterpret_cast<const float4 *>(lag), p.tLag, (int64_t)0);
-    LAUNCH_CHECK("k_import_tiled (smoothed)");
-    return 0;
-}
-
 // estep: 0 = plain smoother; 1 = ECM sweep whose kappa E-step is evaluated inside the smoother chain, moments stored;
 //        2 = same, but the smoothed moments are not stored (an inner sweep nobody reads them from)
 static int backward_impl(csr_ctx *c, bool wantLag, const unsigned char *active, bool defer = false, bool natOut = false,
@@ -955,11 +931,12 @@ static int backward_impl(csr_ctx *c, bool wantLag, const unsigned char *active, 
     }
     // preferNatIn (a group's tail of a pipelined step): the reference-layout xf / Pf of these chains stand -- read them there
     // even though a blocked xf is on its way for the epilogue
-    if (c->fwdBlockedStale || c->pfBlockedStale || preferNatIn) {
+    const csr_ctx::Where xfW = c->where[CSR_ARR_XF], pfW = c->where[CSR_ARR_PF];
+    const bool need = !xfW.blocked || !pfW.blocked;
+    if (need || preferNatIn) {
         const bool pcq = p.chainQ != nullptr;
         const bool constQ = c->fwdInternal && !(c->fwdFlags & (F_APN | F_QSCALE | F_KAPPA));
-        const bool natValid = c->fwdNat || (c->pfNat && (c->xfNat || preferNatIn));
-        const bool need = c->fwdBlockedStale || c->pfBlockedStale;
+        const bool natValid = pfW.nat && (xfW.nat || preferNatIn);
         if (c->natInEnabled && natOut && !pcq && !p.qFromKappa && natValid && (need || constQ) && (stage_warm(c, ST_B) % 8) == 0 &&
             unit_f(c, p)) {
             float *natXf, *natPf;
@@ -969,13 +946,12 @@ static int backward_impl(csr_ctx *c, bool wantLag, const unsigned char *active, 
             p.natXfIn = reinterpret_cast<const float2 *>(natXf);
             p.natPfIn = reinterpret_cast<const float4 *>(natPf);
         } else {
-            CHECK(ensure_blocked_fwd(c, active));
+            CHECK(need_blocked(c, {CSR_ARR_XF, CSR_ARR_PF}, active));
         }
     }
-    c->smoothNat = natOut;
+    new_smoothed_fit(c);
+    if (natOut) produced(c, {CSR_ARR_XS, CSR_ARR_PS, CSR_ARR_LAG}, W_NAT);   // this smoother writes the reference layout only
     c->pendNatOut = natOut;
-    c->fitGen += 1;
-    if (natOut) c->natSmoothGen = c->fitGen;        // this smoother writes xs / Ps in the reference layout itself
     // constant process noise (no kappa / qScale / adaptive noise): the smoother need not read pNoise at all
     p.qFromMult = (c->fwdInternal && !(c->fwdFlags & (F_APN | F_QSCALE | F_KAPPA))) ? 1 : 0;
     (void)wantLag;      // the lag-one covariance is produced by the smoother's own main phase
@@ -1158,7 +1134,7 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
     CHECK(settle(c));
     if (!cfg || !out) return fail("null argument");
     if (!c->statsValid) CHECK(csr_batch_stats(c));
-    c->multGen += 1;        // the E-steps rewrite the resident multipliers
+    multipliers_changed(c);     // the E-steps rewrite the resident multipliers
     const int nc = (int)c->chains.size();
     uint32_t fl = flags & (F_QSCALE);
     if (cfg->use_lambda) fl |= F_LAMBDA;
@@ -1186,7 +1162,7 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
         if (c->chains[i].n <= 5) { act[i] = 1; anyTiny = true; out[i].skipped = 1; }
         else anyBig = true;
     }
-    if (anyMasked && (anyTiny || anyBig)) CHECK(ensure_blocked_smooth(c));
+    if (anyMasked && (anyTiny || anyBig)) CHECK(need_blocked(c, {CSR_ARR_XS, CSR_ARR_PS, CSR_ARR_LAG}, nullptr));
     if (anyTiny) {
         CHECK(push_active());
         CHECK(forward_impl(c, fl | F_NLL, true, c->dActive, true));
@@ -1375,31 +1351,24 @@ static int flush_export(csr_ctx *c, ExpList &L) {
     L.count = 0;
     return 0;
 }
-static int add_export(csr_ctx *c, ExpList &L, int id, const float *src, int E, int n, int skipLast) {
+// The reference-layout copy of array `id` is needed: queue its conversion unless that copy is current already.  keep = false
+// does not remember the conversion (every export of a forward pass converts D / xf / Pf / pNoise again unless the pass wrote them)
+static int need_natural(csr_ctx *c, ExpList &L, int id, const float *src, int E, int n, int skipLast, bool keep = true) {
+    if (c->where[id].nat) return 0;
     if (L.count == 8) CHECK(flush_export(c, L));       // one launch converts up to eight arrays
     float *dst;
     CHECK(nat_array(c, id, &dst));
     ExpDesc &d = L.d[L.count++];
     memset(&d, 0, sizeof(d));
     d.src = src; d.dst = dst; d.E = E; d.n = n; d.skipLast = skipLast;
+    c->where[id].nat = keep;
     return 0;
 }
-
-// the smoothed state / one multiplier array into the reference layout unless the array there already is this fit's / these
-// multipliers' (csr_ctx::natXsStamp, natMultStamp)
-static int add_export_xs(csr_ctx *c, ExpList &L) {
-    if (c->smoothNat || c->natXsStamp == c->fitGen) return 0;
-    CHECK(add_export(c, L, CSR_ARR_XS, (const float *)c->p.tXs, 2, c->mdl.state_dim, 0));
-    c->natXsStamp = c->fitGen;
-    return 0;
+static int need_natural_xs(csr_ctx *c, ExpList &L) {
+    return need_natural(c, L, CSR_ARR_XS, (const float *)c->p.tXs, 2, c->mdl.state_dim, 0);
 }
-static int add_export_mult(csr_ctx *c, ExpList &L, int id) {
-    const int k = id == CSR_ARR_LAMBDA ? 0 : (id == CSR_ARR_KAPPA ? 1 : 2);
-    if (c->nat[id] && c->natMultStamp[k] == c->multGen) return 0;
-    const float *src = k == 0 ? c->p.tLam : (k == 1 ? c->p.tKap : c->p.tQs);
-    CHECK(add_export(c, L, id, src, 1, 1, 0));
-    c->natMultStamp[k] = c->multGen;
-    return 0;
+static int need_natural_mult(csr_ctx *c, ExpList &L, int id) {
+    return need_natural(c, L, id, id == CSR_ARR_LAMBDA ? c->p.tLam : (id == CSR_ARR_KAPPA ? c->p.tKap : c->p.tQs), 1, 1, 0);
 }
 
 // residuals of the bins [off, off + nb) of the batch's natural layout (whole chains: off and nb are multiples of 64)
@@ -1443,21 +1412,20 @@ static int export_impl(csr_ctx *c, uint32_t what) {
     // The NIS/NLL track is the only export that depends on the side stream's epilogue: when that is still running it is
     // converted last, after the (long, bandwidth-bound) residual kernel, so the epilogue leaves the critical path.
     // (Small batches are launch-bound: there the extra conversion launch costs more than the overlap saves.)
-    const bool lateD = (what & CSR_EXPORT_FORWARD) && c->sidePending && (what & CSR_EXPORT_RESID) && !c->dNat &&
+    const bool natD = c->where[CSR_ARR_D].nat;
+    const bool lateD = (what & CSR_EXPORT_FORWARD) && c->sidePending && (what & CSR_EXPORT_RESID) && !natD &&
                        c->Npad >= ((int64_t)4 << 20);
-    // dNat: the epilogue writes D in the reference layout itself -- nothing in this export depends on the side stream; it
-    // is joined at the next settle point (sums, download, device_array, synchronize)
-    if (!lateD && !c->dNat) join_side(c);
+    // D is current in the reference layout (the epilogue wrote it there itself): nothing in this export depends on the side
+    // stream; it is joined at the next settle point (sums, download, device_array, synchronize)
+    if (!lateD && !natD) join_side(c);
     if (what & CSR_EXPORT_FORWARD) {
         if (!c->haveFwd) return fail("no forward results to export");
         join_pf(c);
-        if (!lateD && !c->dNat) CHECK(add_export(c, L, CSR_ARR_D, p.tD, 1, 1, 0));   // dNat: the epilogue wrote it already
-        if (!c->fwdNat) {       // fwdNat: the forward chain already wrote both in the reference layout
-            if (!c->xfNat) CHECK(add_export(c, L, CSR_ARR_XF, (const float *)p.tXf, 2, nv, 0));    // xfNat: the systolic state chain wrote it
-            if (!c->pfNat) CHECK(add_export(c, L, CSR_ARR_PF, (const float *)p.tPf, 4, nm, 0));    // pfNat: written underneath the state chain
-        }
+        if (!lateD) CHECK(need_natural(c, L, CSR_ARR_D, p.tD, 1, 1, 0, false));
+        CHECK(need_natural(c, L, CSR_ARR_XF, (const float *)p.tXf, 2, nv, 0, false));
+        CHECK(need_natural(c, L, CSR_ARR_PF, (const float *)p.tPf, 4, nm, 0, false));
         const bool constQ = c->fwdInternal && !(c->fwdFlags & (F_APN | F_QSCALE | F_KAPPA));
-        if (c->pnNat) {
+        if (c->where[CSR_ARR_PNOISE].nat) {
             // (the constant process noise was filled underneath the state chain as well)
         } else if (constQ && p.chainQ == nullptr) {
             // one Q0 for every bin of every chain: a streaming fill (rows past a chain's n-1 are padding nobody reads)
@@ -1467,7 +1435,7 @@ static int export_impl(csr_ctx *c, uint32_t what) {
                 CHECK(launch_pn_fill(c, p, dst, c->stream));
             }
         } else {
-            CHECK(add_export(c, L, CSR_ARR_PNOISE, constQ ? nullptr : (const float *)p.tQ, 4, nm, 1));
+            CHECK(need_natural(c, L, CSR_ARR_PNOISE, constQ ? nullptr : (const float *)p.tQ, 4, nm, 1, false));
             c->pnFillValid = false;
         }
         if (constQ && p.chainQ != nullptr) {
@@ -1480,23 +1448,19 @@ static int export_impl(csr_ctx *c, uint32_t what) {
     }
     if (what & (CSR_EXPORT_SMOOTH | CSR_EXPORT_RESID)) {
         if (!c->haveBwd) return fail("no smoothed results to export");
-        CHECK(add_export_xs(c, L));
+        CHECK(need_natural_xs(c, L));
     }
-    if ((what & CSR_EXPORT_SMOOTH) && !c->smoothNat && c->natSmoothGen != c->fitGen) {      // smoothNat: the smoother already wrote the natural arrays; natSmoothGen: converted before
-        CHECK(add_export(c, L, CSR_ARR_PS, (const float *)p.tPs, 4, nm, 0));
-        CHECK(add_export(c, L, CSR_ARR_LAG, (const float *)p.tLag, 4, nm, 1));
+    if (what & CSR_EXPORT_SMOOTH) {
+        CHECK(need_natural(c, L, CSR_ARR_PS, (const float *)p.tPs, 4, nm, 0));
+        CHECK(need_natural(c, L, CSR_ARR_LAG, (const float *)p.tLag, 4, nm, 1));
     }
-    if (what & CSR_EXPORT_SMOOTH) c->natSmoothGen = c->fitGen;
-    if (what & CSR_EXPORT_MULT) {
-        CHECK(add_export_mult(c, L, CSR_ARR_LAMBDA));
-        CHECK(add_export_mult(c, L, CSR_ARR_KAPPA));
-        CHECK(add_export_mult(c, L, CSR_ARR_QSCALE));
-    }
+    if (what & CSR_EXPORT_MULT)
+        for (int id : {CSR_ARR_LAMBDA, CSR_ARR_KAPPA, CSR_ARR_QSCALE}) CHECK(need_natural_mult(c, L, id));
     CHECK(flush_export(c, L));
     if (what & CSR_EXPORT_RESID) CHECK(launch_resid(c, 0, c->Npad, true));
     if (lateD) {
         join_side(c);
-        CHECK(add_export(c, L, CSR_ARR_D, p.tD, 1, 1, 0));
+        CHECK(need_natural(c, L, CSR_ARR_D, p.tD, 1, 1, 0, false));
         CHECK(flush_export(c, L));
     }
     return 0;
@@ -1519,7 +1483,7 @@ static int step_tail(csr_ctx *c, const Prm &pf, const unsigned char *dmask, cons
     // one constant process noise: the smoother reads xf / Pf of these chains in the reference layout (k_smooth_natin) and starts
     // at once; the blocked copy of xf only the NIS / NLL epilogue needs is made on the side stream in front of it
     const bool constQ = c->fwdInternal && !(c->fwdFlags & (F_APN | F_QSCALE | F_KAPPA));
-    const bool natTail = c->natOnlyEnabled && c->natInEnabled && c->pfNat && constQ && pf.chainQ == nullptr && (c->B % 8) == 0 &&
+    const bool natTail = c->natOnlyEnabled && c->natInEnabled && c->where[CSR_ARR_PF].nat && constQ && pf.chainQ == nullptr && (c->B % 8) == 0 &&
                          (stage_warm(c, ST_B) % 8) == 0 && unit_f(c, pf);
     HIPOK(hipEventRecord(c->evFork, c->stream));
     HIPOK(hipStreamWaitEvent(c->side, c->evFork, 0));
@@ -1580,7 +1544,7 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
         return 0;
     }
     const Prm pf = c->sbp.p;
-    if (!(c->dNat && c->pfNat && c->pnNat)) {
+    if (!(c->where[CSR_ARR_D].nat && c->where[CSR_ARR_PF].nat && c->where[CSR_ARR_PNOISE].nat)) {
         // an output of this pass still needs a conversion launch of its own (export_impl): no pipelining, finish in order
         CHECK(state_chain_systolic(c, pf, false, flags, 2));
         Prm pt = pf;
@@ -1682,7 +1646,6 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     LAUNCH_CHECK("k_chain_sums");
     c->pendActiveB = nullptr;           // a replay after a failed optimistic validation covers every chain
     if (c->pendBwd) c->pendExport |= what;
-    if (what & CSR_EXPORT_SMOOTH) c->natSmoothGen = c->fitGen;
     c->rs.tail_groups += phase;
     *handled = true;
     return 0;

@@ -66,7 +66,7 @@ extern "C" int csr_output_diagnostics(const csr_model *mdl, int64_t m, int64_t n
         flags |= e.flag;
         float *dst;
         CHECK(nat_array(c, e.id, &dst));
-        if (e.flag) c->natMultStamp[e.id == CSR_ARR_LAMBDA ? 0 : (e.id == CSR_ARR_KAPPA ? 1 : 2)] = ~0ull;     // (not the resident multipliers)
+        c->where[e.id].nat = false;     // (not the resident results / multipliers)
         if (e.id == CSR_ARR_PNOISE) c->pnFillValid = false;
         if (e.rows > 0)
             HIPOK(hipMemcpyAsync(dst + ci.off * e.comps, e.src, sizeof(float) * e.comps * e.rows, hipMemcpyHostToDevice,
@@ -367,8 +367,8 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
     {
         ExpList L;
         memset(&L, 0, sizeof(L));
-        if (!zeroState) CHECK(add_export_xs(c, L));
-        if (cfg->use_lambda) CHECK(add_export_mult(c, L, CSR_ARR_LAMBDA));
+        if (!zeroState) CHECK(need_natural_xs(c, L));
+        if (cfg->use_lambda) CHECK(need_natural_mult(c, L, CSR_ARR_LAMBDA));
         CHECK(flush_export(c, L));
     }
     a.xsNat = zeroState ? nullptr : c->nat[CSR_ARR_XS]; a.xsStride = c->mdl.state_dim;
@@ -758,8 +758,8 @@ extern "C" int csr_batch_objective_terms(csr_ctx *c, const csr_objective_cfg *cf
     {
         ExpList L;
         memset(&L, 0, sizeof(L));
-        if (needLam) CHECK(add_export_mult(c, L, CSR_ARR_LAMBDA));
-        if (cfg->use_kappa_penalty) CHECK(add_export_mult(c, L, CSR_ARR_KAPPA));
+        if (needLam) CHECK(need_natural_mult(c, L, CSR_ARR_LAMBDA));
+        if (cfg->use_kappa_penalty) CHECK(need_natural_mult(c, L, CSR_ARR_KAPPA));
         CHECK(flush_export(c, L));
     }
     ObjArgs o;
@@ -865,8 +865,8 @@ extern "C" int csr_batch_phase_tracks(csr_ctx *c, int32_t chain, int32_t use_lam
     {
         ExpList L;
         memset(&L, 0, sizeof(L));
-        CHECK(add_export_xs(c, L));
-        if (useLam) CHECK(add_export_mult(c, L, CSR_ARR_LAMBDA));
+        CHECK(need_natural_xs(c, L));
+        if (useLam) CHECK(need_natural_mult(c, L, CSR_ARR_LAMBDA));
         CHECK(flush_export(c, L));
     }
     const int64_t n = c->chains[chain].n;
@@ -912,7 +912,7 @@ extern "C" int csr_batch_gain_summary(csr_ctx *c, int32_t chain, int32_t use_lam
     {
         ExpList L;
         memset(&L, 0, sizeof(L));
-        if (use_lambda) CHECK(add_export_mult(c, L, CSR_ARR_LAMBDA));
+        if (use_lambda) CHECK(need_natural_mult(c, L, CSR_ARR_LAMBDA));
         CHECK(flush_export(c, L));
     }
     const int m = (int)c->m;

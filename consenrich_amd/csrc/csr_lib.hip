@@ -12,6 +12,7 @@
 #include "csr_gain.h"
 
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstdarg>
@@ -155,16 +156,15 @@ struct csr_ctx {
     int64_t Npad = 0, NB = 0, NG = 0, TN = 0;
     bool statsValid = false;
     bool haveFwd = false, haveBwd = false;
-    uint64_t fitGen = 0, natSmoothGen = ~0ull;     // generation of the resident smoothed fit / of the natural xs + Ps arrays (csr_batch_gather_tracks)
-    // Conversions of the smoothed state / the multipliers into the reference layout are remembered: a caller that asks chain by
-    // chain (the per-phase run diagnostics: 22 chains x every ECM phase) converts the batch once per phase, not once per chain.
-    // multGen counts changes of the resident multipliers (uploads, ECM calls); the stamps say what the arrays were converted from.
-    uint64_t multGen = 0, natMultStamp[3] = {~0ull, ~0ull, ~0ull}, natXsStamp = ~0ull;
-    bool smoothNat = false;     // the last smoother pass wrote xs / Ps / lag straight into the natural arrays (the
-                                // block-transposed copies are stale; nothing but the ECM E-steps reads those)
-    bool pendNatOut = false;
-    bool fwdNat = false, pendFwdNat = false;   // the last forward pass wrote xf / Pf in the reference layout too
-    bool dNat = false;          // ... and its NIS/NLL epilogue wrote D there (nothing left to convert)
+    // Resident copies.  Every result array has up to two copies: the blocked (tile-transposed) one the chains walk (Prm::t*) and
+    // the reference-layout one callers download (nat[]).  where[id].blocked / .nat say which of them holds the resident result of
+    // EVERY chain, at the boundaries of a C-ABI call (inside a pipelined step groups of chains are at different stages).  A pass
+    // marks what it wrote (produced), an export converts only what is not .nat and a reader of the blocked layout imports only
+    // what is not .blocked (need_natural, need_blocked); new inputs to a pass invalidate (new_forward_pass, new_smoothed_fit,
+    // multipliers_changed).  A caller that asks chain by chain therefore converts the batch once, not once per chain.
+    struct Where { bool blocked = true, nat = false; };
+    std::array<Where, CSR_ARR_COUNT> where{};
+    bool pendNatOut = false, pendFwdNat = false;
     static constexpr bool natOutD = true;       // the NIS / NLL epilogue writes D in the reference layout itself
     bool dstatLdsRaised = false;
     // 2-ulp throughput mode, the byte cuts of round 5 (their A/B switch CONSENRICH_AMD_LEAN was retired in round 6; each of them
@@ -173,9 +173,7 @@ struct csr_ctx {
     static constexpr bool nisInChainEnabled = true;     // NIS / NLL terms inside the fused forward chain's tile walker (no epilogue kernel)
     static constexpr bool natOnlyEnabled = true;        // constant process noise: xf / Pf only in the reference layout, the smoother reads them there
     bool natInEnabled = true;           // CONSENRICH_AMD_NATIN=0 (tests): the smoother never reads the reference layout -- blocked copies
-                                        // a forward pass did not write are brought back first (ensure_blocked_fwd)
-    bool fwdBlockedStale = false;       // the resident forward pass wrote xf / Pf in the reference layout ONLY (blocked tXf / tPf are stale)
-    bool pfBlockedStale = false;        // ... Pf alone (default mode: the covariance chain of a pipelined step writes it in the reference layout only)
+                                        // a forward pass did not write are brought back first (need_blocked)
     bool sideSumsDone = false;          // the pending side-stream work already includes the per-chain sums (join_side only waits)
     double lastSbLoopUs = 0.0;          // how long the host watched the previous single launch of the state chain (step_pipelined)
     double lastWaitUs[2] = {0.0, 0.0};  // how long the previous host wait for the stream lasted, per wait site (wait_stream polls around that moment)
@@ -232,7 +230,6 @@ struct csr_ctx {
     bool natSZValid = false;    // sbNatSZ holds the current statistics of every chain
     bool gainNat = false;       // this forward pass's covariance chain wrote sbNatGain itself (walk_nat_gain)
     float4 *sbNatGain = nullptr, *sbNatSZ = nullptr;    // natural-layout records of the systolic walker (freed with the batch)
-    bool xfNat = false;         // the resident forward pass left xf in the reference layout already (systolic walker)
     struct SbView {
         bool ready = false;
         int B = 0;
@@ -308,7 +305,7 @@ struct csr_ctx {
     // 50 / 15) -- tail kernels take issue slots from the walking wavefronts, so fewer, later groups win (profiles/r04_tail_sweep.txt)
     int tailFirstPct = 60, tailNextPct = 40;
     bool tailSplit = true;      // CONSENRICH_AMD_TAIL_SPLIT=0: a step's tail follows the state chain for all chains at once
-    bool pfPending = false, pfNat = false, pnNat = false;
+    bool pfPending = false;
     // the reference-layout process-noise array holds the constant fill of THESE values in every row (k_fill_rows): a step with the
     // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)
     bool pnFillValid = false;
@@ -324,6 +321,16 @@ struct csr_ctx {
 
 static int settle(csr_ctx *c);
 static int export_impl(csr_ctx *c, uint32_t what);
+
+// The pass that just ran wrote these arrays in the given copies (and not in the other)
+enum : unsigned { W_BLOCKED = 1u, W_NAT = 2u };
+static void produced(csr_ctx *c, std::initializer_list<int> ids, unsigned copies) {
+    for (int id : ids) c->where[id] = csr_ctx::Where{(copies & W_BLOCKED) != 0, (copies & W_NAT) != 0};
+}
+// New inputs: whatever the reference layout holds is no longer the resident result (the blocked copies are what the next pass writes)
+static void new_forward_pass(csr_ctx *c) { produced(c, {CSR_ARR_D, CSR_ARR_XF, CSR_ARR_PF, CSR_ARR_PNOISE}, W_BLOCKED); }
+static void new_smoothed_fit(csr_ctx *c) { produced(c, {CSR_ARR_XS, CSR_ARR_PS, CSR_ARR_LAG}, W_BLOCKED); }
+static void multipliers_changed(csr_ctx *c) { produced(c, {CSR_ARR_LAMBDA, CSR_ARR_KAPPA, CSR_ARR_QSCALE}, W_BLOCKED); }
 
 static int ctx_select(csr_ctx *c) {
     HIPOK(hipSetDevice(c->device));
@@ -365,15 +372,12 @@ static void free_batch(csr_ctx *c) {
     for (auto &m : c->dMask) m = nullptr;
     c->sbp.active = false;
     c->pfPending = false;
-    c->xfNat = false;
-    c->fwdNat = c->pfNat = c->pnNat = c->dNat = c->smoothNat = false;
-    c->fwdBlockedStale = c->pfBlockedStale = false;     // (the reference-layout arrays they point at are gone)
+    c->where = {};      // (the reference-layout arrays are gone)
     c->pnFillValid = false;
     c->ckF[0] = c->ckF[1] = c->ckB[0] = c->ckB[1] = nullptr;
     c->wsSavedF = c->wsSavedB = 0;
     c->wsActive = c->wsCold = false;
     for (auto &n : c->nat) n = nullptr;
-    c->natXsStamp = c->natMultStamp[0] = c->natMultStamp[1] = c->natMultStamp[2] = ~0ull;
 }
 
 // Warm-up windows that gave zero re-runs on the bench workload with margin (hg38 x 32 synthetic: the state chain needs

@@ -7,6 +7,9 @@ re-synthesised from the seed by tests/golden/cases.py, which both this script an
 
 Usage:  python tests/golden/make_golden.py          (rewrites every fixture, then cross-checks the C oracle bit-for-bit)
         python tests/golden/make_golden.py --live   (rewrites live_reference.json alone)
+        python tests/golden/make_golden.py --launches   (rewrites conversion_launches.json alone: needs a GPU, not the reference.
+                                                         Run it in a checkout of the commit BEFORE a change of the host layer with
+                                                         this file and launch_cases.py copied in -- never on the code under test)
 """
 from __future__ import annotations
 
@@ -30,7 +33,30 @@ from oracle import qseed as orc_qseed  # noqa: E402
 from oracle import ref_loader  # noqa: E402
 
 
+def write_launch_record() -> int:
+    """conversion_launches.json: what every call sequence of launch_cases.py launches in the conversion scopes, per mode."""
+    import json
+
+    import launch_cases
+
+    os.environ["CONSENRICH_AMD_TAIL_SPLIT"] = "0"
+    rec = {}
+    for xtol, natin in launch_cases.MODES:
+        os.environ["CONSENRICH_AMD_NATIN"] = natin
+        rec[launch_cases.mode_key(xtol, natin)] = launch_cases.run_mode(xtol)
+    bad = [(k, s) for k, seqs in rec.items() for s, r in seqs.items() if r.get("pipeline_redos", 0) != 0]
+    if bad:
+        raise SystemExit(f"pipeline replays in {bad}: a replay repeats launches -- pick another seed (launch_cases.SEED)")
+    with open(launch_cases.RECORD, "w") as fh:
+        json.dump(rec, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(f"{os.path.basename(launch_cases.RECORD)} written")
+    return 0
+
+
 def main() -> int:
+    if "--launches" in sys.argv[1:]:
+        return write_launch_record()
     ref = ref_loader.load()
     if ref is None:
         print("reference build not available (make -C oracle ref)", file=sys.stderr)

@@ -277,3 +277,26 @@ def test_constant_process_noise_rows_are_written_once_and_follow_the_model(produ
 
     if _default_switches():         # (under the suite's mode switches a step converts other arrays under the same profile name)
         assert fills == 0, fills    # the second step with the same constant Q launched no conversion / fill at all
+
+
+@pytest.mark.parametrize("xtol,natin", [(0, "1"), (0, "0"), (2, "1"), (2, "0")], ids=["exact-natin", "exact-blocked", "ulp2-natin", "ulp2-blocked"])
+def test_every_call_sequence_launches_the_recorded_conversions(product, monkeypatch, xtol, natin):
+    """Census of the conversion launches (exports, imports into the blocked layout, record conversions, residuals, NIS / NLL
+    epilogue, per-chain sums, multiplier imports, summaries) of the call sequences in tests/golden/launch_cases.py against
+    tests/golden/conversion_launches.json, recorded with the library of the commit before the flags that say which copy of an
+    array is current became one table (csr_ctx::where): every count of every sequence equal, and no pipeline replay."""
+    import launch_cases
+
+    # (the record holds the launches of the library's default forms: under another mode switch of scripts/suite_variants.sh the
+    # sequences still have to run through, but other kernels convert other arrays under the same profile names)
+    own = ("CONSENRICH_AMD_TAIL_SPLIT", "CONSENRICH_AMD_NATIN")
+    switched = sorted(k for k in os.environ if k.startswith("CONSENRICH_AMD_") and k not in own)
+    monkeypatch.setenv("CONSENRICH_AMD_TAIL_SPLIT", "0")        # (the number of tail groups of a pipelined step depends on timing)
+    monkeypatch.setenv("CONSENRICH_AMD_NATIN", natin)
+    want = launch_cases.load()[launch_cases.mode_key(xtol, natin)]
+    got = launch_cases.run_mode(xtol)
+    for name in sorted(set(want) | set(got)):
+        print(name, got.get(name), want.get(name))
+    if not switched:
+        assert got == want
+        assert all(r.get("pipeline_redos", 0) == 0 for r in got.values())
