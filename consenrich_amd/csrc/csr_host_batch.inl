@@ -171,7 +171,6 @@ extern "C" int csr_batch_configure(csr_ctx *c, const csr_model *mdl, int64_t m, 
     p.tKapOut = p.tKap;
     p.storePP = 1;
     c->kapScratch[0] = c->kapScratch[1] = nullptr;
-    c->kapIn = c->kapOut = nullptr;
     CHECK(dalloc(c, &p.tXin, T)); CHECK(dalloc(c, &p.tPf, T)); CHECK(dalloc(c, &p.tQ, T)); CHECK(dalloc(c, &p.tQ2, T));
     CHECK(dalloc(c, &p.tXf, T)); CHECK(dalloc(c, &p.tD, T)); CHECK(dalloc(c, &p.tPP, T));
     CHECK(dalloc(c, &p.tXs, T)); CHECK(dalloc(c, &p.tPs, T)); CHECK(dalloc(c, &p.tLag, T));

@@ -9,10 +9,10 @@ extern "C" int csr_batch_stats(csr_ctx *c) {
     CHECK(settle(c));
     // 2-ulp throughput mode: {S2c, log R} as one float32 pair (csr_device.h Prm::tS2L); the form is a property of the RESIDENT
     // statistics (a later csr_set_validation does not invalidate them: every reader goes through load_s2c / load_logr / load_s2l)
-    c->p.statsF32 = (c->statsF32Enabled && c->xTolUlps > 0) ? 1 : 0;
+    c->p.statsF32 = c->xTolUlps > 0 ? 1 : 0;
     Prm p = c->p;
     // default mode with the superblock state chain: that chain reads {S0u, zbar} in the reference layout -- written here directly
-    const bool natSZ = CSR_GAIN_NAT && CSR_STATS_NATSZ && c->xTolUlps == 0 && c->mdl.state_dim == 2 && c->sbState && !c->seqState;
+    const bool natSZ = c->xTolUlps == 0 && c->mdl.state_dim == 2 && !c->seqState;
     p.natSZ = nullptr;
     if (natSZ) {
         if (!c->sbNatGain) { CHECK(dalloc(c, &c->sbNatGain, c->Npad)); CHECK(dalloc(c, &c->sbNatSZ, c->Npad)); }
@@ -54,36 +54,33 @@ struct TimerSlack {
 // site: which wait of the pipeline this is (0 = the settle point's mailbox read, 1 = the state chain's verdict): each keeps its own
 // estimate -- a step has both, of very different lengths
 static hipError_t wait_stream(csr_ctx *c, int site = 0) {
-    if (c->spinWait) {
-        // a short burst of polls (the waits on a shard's critical path are tens of microseconds), then polls 20 us apart, then
-        // a blocking wait: a rank never burns a core for the length of a latency-bound launch (8 ranks per node).  Two details
-        // keep the wake-up from costing the step tens of microseconds: the calling thread's timer slack is lowered FOR THE LENGTH OF
-        // THE WAIT (the kernel's default of 50 us turns a 20-us sleep into ~75; the caller's setting is put back on the way out),
-        // and around the moment the PREVIOUS wait of this context ended (steps repeat) the loop polls without sleeping -- at most
-        // ~0.4 ms of spinning per wait.
-        TimerSlack slack;
-        const auto t0 = std::chrono::steady_clock::now();
-        auto elapsed_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-        for (int i = 0; i < 128; ++i) {
-            const hipError_t q = hipStreamQuery(c->stream);
-            if (q == hipSuccess) { c->lastWaitUs[site] = elapsed_us(); return hipSuccess; }
-            if (q != hipErrorNotReady) return q;
-        }
-        const double expect = c->lastWaitUs[site];
-        for (;;) {
-            const double el = elapsed_us();
-            if (el > 8000.0) break;
-            const bool nearEnd = expect > 0.0 && el > expect - 150.0 && el < expect + 250.0;
-            if (!nearEnd) std::this_thread::sleep_for(std::chrono::microseconds(20));
-            const hipError_t q = hipStreamQuery(c->stream);
-            if (q == hipSuccess) { c->lastWaitUs[site] = elapsed_us(); return hipSuccess; }
-            if (q != hipErrorNotReady) return q;
-        }
-        const hipError_t r = hipStreamSynchronize(c->stream);
-        c->lastWaitUs[site] = elapsed_us();
-        return r;
+    // a short burst of polls (the waits on a shard's critical path are tens of microseconds), then polls 20 us apart, then
+    // a blocking wait: a rank never burns a core for the length of a latency-bound launch (8 ranks per node).  Two details
+    // keep the wake-up from costing the step tens of microseconds: the calling thread's timer slack is lowered FOR THE LENGTH OF
+    // THE WAIT (the kernel's default of 50 us turns a 20-us sleep into ~75; the caller's setting is put back on the way out),
+    // and around the moment the PREVIOUS wait of this context ended (steps repeat) the loop polls without sleeping -- at most
+    // ~0.4 ms of spinning per wait.
+    TimerSlack slack;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto elapsed_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
+    for (int i = 0; i < 128; ++i) {
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess) { c->lastWaitUs[site] = elapsed_us(); return hipSuccess; }
+        if (q != hipErrorNotReady) return q;
     }
-    return hipStreamSynchronize(c->stream);
+    const double expect = c->lastWaitUs[site];
+    for (;;) {
+        const double el = elapsed_us();
+        if (el > 8000.0) break;
+        const bool nearEnd = expect > 0.0 && el > expect - 150.0 && el < expect + 250.0;
+        if (!nearEnd) std::this_thread::sleep_for(std::chrono::microseconds(20));
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess) { c->lastWaitUs[site] = elapsed_us(); return hipSuccess; }
+        if (q != hipErrorNotReady) return q;
+    }
+    const hipError_t r = hipStreamSynchronize(c->stream);
+    c->lastWaitUs[site] = elapsed_us();
+    return r;
 }
 // hand a pending folded check to the kernel about to be launched with `p` (or clear the fields)
 static void take_pending_check(csr_ctx *c, Prm &p) {
@@ -138,8 +135,46 @@ static int64_t &stage_reruns(csr_ctx *c, int stage) {
 }
 
 // F = [[1, f], [0, 1]] (constructMatrixF, core.py:2164-2176): the UF instances of the levelTrend policies (csr_device.h)
-static bool unit_f(const csr_ctx *c, const Prm &p) {
-    return c->unitFEnabled && p.F00 == 1.0 && p.F10 == 0.0 && p.F11 == 1.0;
+static bool unit_f(const Prm &p) { return p.F00 == 1.0 && p.F10 == 0.0 && p.F11 == 1.0; }
+
+// ---- launch idioms shared by the passes ---------------------------------------------------------------------------
+// one workgroup per 32-bin tile of every wavefront-group (the tiled conversions between the two layouts)
+static dim3 tile_grid(const csr_ctx *c) { return dim3((int)(c->NG * (c->B / 32))); }
+// the side stream continues from this point of the main stream
+static int fork_side(csr_ctx *c, hipEvent_t ev) {
+    HIPOK(hipEventRecord(ev, c->stream));
+    HIPOK(hipStreamWaitEvent(c->side, ev, 0));
+    return 0;
+}
+// NIS / NLL epilogue (D in the reference layout goes through one LDS tile per block)
+static int launch_dstat(csr_ctx *c, const Prm &p, hipStream_t st) {
+    {
+        Scope sc(c, "fwd_dstat", st);
+        if (p.natD) hipLaunchKernelGGL(k_fwd_dstat<true>, dim3((int)c->NG), dim3(256), sizeof(float) * 64 * (c->B + 1), st, p);
+        else hipLaunchKernelGGL(k_fwd_dstat<false>, dim3((int)c->NG), dim3(256), 0, st, p);
+    }
+    LAUNCH_CHECK("k_fwd_dstat");
+    return 0;
+}
+// per-chain sums of the per-block sums the epilogue (or the chain itself) left
+static void launch_chain_sums(csr_ctx *c, const Prm &p, hipStream_t st) {
+    Scope sc(c, "chain_sums", st);
+    hipLaunchKernelGGL(k_chain_sums, dim3((int)c->chains.size()), dim3(1024), 0, st, p, c->dChainFirst, c->dChainNb);
+}
+// blocked copy of the filtered state from the reference-layout one (which the bit-exact state chain wrote), for `groups`
+// wavefront-groups from g0 on; profiled = false: the launch is not counted under a profile scope
+static int import_xf_blocked(csr_ctx *c, const Prm &p, hipStream_t st, int64_t g0, int64_t groups, bool profiled = true) {
+    float *natXf;
+    CHECK(nat_array(c, CSR_ARR_XF, &natXf));
+    const dim3 grid((int)(groups * (c->B / 32)));
+    if (profiled) {
+        Scope sc(c, "state_reblock_out", st);
+        hipLaunchKernelGGL(k_import_tiled<float2>, grid, dim3(256), 0, st, p, reinterpret_cast<const float2 *>(natXf), p.tXf, g0);
+    } else {
+        hipLaunchKernelGGL(k_import_tiled<float2>, grid, dim3(256), 0, st, p, reinterpret_cast<const float2 *>(natXf), p.tXf, g0);
+    }
+    LAUNCH_CHECK("k_import_tiled_f2");
+    return 0;
 }
 
 // Speculative pass + validation/fix-up.  defer = true: launch the speculative pass and ONE validation pass and return
@@ -412,7 +447,7 @@ static int need_blocked(csr_ctx *c, std::initializer_list<int> ids, const unsign
     if (!any) return 0;
     Prm p = c->p;
     p.chainActive = active;
-    const dim3 grid((int)(c->NG * (c->B / 32)));
+    const dim3 grid = tile_grid(c);
     Scope sc(c, "state_reblock_out");
     for (int id : ids) {
         if (c->where[id].blocked) continue;
@@ -467,7 +502,7 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
             pe.chainActive = nullptr;       // the statistics of EVERY chain (csr_batch_stats computed them all), whatever this pass masks
             c->natSZValid = true;
         }
-        hipLaunchKernelGGL(k_export_tiled, dim3((int)(c->NG * (c->B / 32))), dim3(256), 0, c->stream, pe, L);
+        hipLaunchKernelGGL(k_export_tiled, tile_grid(c), dim3(256), 0, c->stream, pe, L);
     }
     LAUNCH_CHECK("k_export_tiled (state records)");
     if (earlyExports && !resume) CHECK(early_cov_exports(c, p, flags, true));
@@ -478,9 +513,9 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
     q.rerunCount = cnt + ST_X;
     q.rerunCountPass = cnt + MAIL_DUMMY;
     q.prevKind = CK_NONE;
-    const int mode = unit_f(c, p) ? ((p.F01 == 1.0 && c->unitF1Enabled) ? 2 : 1) : 0;
+    const int mode = unit_f(p) ? (p.F01 == 1.0 ? 2 : 1) : 0;     // F01 == 1: the walker's predicted level is one float32 add
     const int grid = (int)((v.NB + 3) / 4);
-    q.sbDbg = nullptr;          // (the instrumented instances of round 4's studies, CONSENRICH_AMD_SB_DEBUG, were retired in round 6)
+    q.sbDbg = nullptr;
     auto launch = [&](int which, int fix) {
         float2 *xf = reinterpret_cast<float2 *>(natXf);
         if (fix) {        // repair passes in delta form (k_sb_delta)
@@ -574,12 +609,7 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
         burst = c->dbgLog ? 1 : std::min(32, burst * 2);
     }
     if (!done) return fail("fwd_state_chain (systolic superblocks): fix-up did not reach a fixed point");
-    if (!resume) {
-        Scope sc(c, "state_reblock_out");
-        hipLaunchKernelGGL(k_import_tiled<float2>, dim3((int)(c->NG * (c->B / 32))), dim3(256), 0, c->stream, p,
-                           reinterpret_cast<const float2 *>(natXf), p.tXf, (int64_t)0);
-    }
-    LAUNCH_CHECK("k_import_tiled_f2");
+    if (!resume) CHECK(import_xf_blocked(c, p, c->stream, 0, c->NG));
     produced(c, {CSR_ARR_XF}, W_BLOCKED | W_NAT);
     return 0;
 }
@@ -592,9 +622,7 @@ static void join_side(csr_ctx *c) {
         (void)hipStreamWaitEvent(c->stream, c->evJoin, 0);
         c->sidePending = false;
         if (c->sideSumsDone) { c->sideSumsDone = false; return; }    // the side stream ran the per-chain sums itself
-        Scope sc(c, "chain_sums");
-        hipLaunchKernelGGL(k_chain_sums, dim3((int)c->chains.size()), dim3(1024), 0, c->stream, c->sidePrm, c->dChainFirst,
-                           c->dChainNb);
+        launch_chain_sums(c, c->sidePrm, c->stream);
     }
 }
 
@@ -604,26 +632,17 @@ static int forward_epilogue(csr_ctx *c, const Prm &p, bool side) {
     hipStream_t st = c->stream;
     if (side) {
         join_side(c);
-        HIPOK(hipEventRecord(c->evFork, c->stream));
-        HIPOK(hipStreamWaitEvent(c->side, c->evFork, 0));
+        CHECK(fork_side(c, c->evFork));
         st = c->side;
     }
-    {
-        Scope sc(c, "fwd_dstat", st);
-        if (p.natD) hipLaunchKernelGGL(k_fwd_dstat<true>, dim3((int)c->NG), dim3(256), sizeof(float) * 64 * (c->B + 1), st, p);
-        else hipLaunchKernelGGL(k_fwd_dstat<false>, dim3((int)c->NG), dim3(256), 0, st, p);
-    }
-    LAUNCH_CHECK("k_fwd_dstat");
+    CHECK(launch_dstat(c, p, st));
     if (side) {
         HIPOK(hipEventRecord(c->evJoin, c->side));
         c->sidePending = true;
         c->sidePrm = p;                 // k_chain_sums follows on the main stream at the join
         return 0;
     }
-    {
-        Scope sc(c, "chain_sums", st);
-        hipLaunchKernelGGL(k_chain_sums, dim3((int)c->chains.size()), dim3(1024), 0, st, p, c->dChainFirst, c->dChainNb);
-    }
+    launch_chain_sums(c, p, st);
     LAUNCH_CHECK("k_chain_sums");
     return 0;
 }
@@ -681,8 +700,7 @@ static int early_cov_exports(csr_ctx *c, const Prm &p, uint32_t flags, bool with
     float *dstPf = nullptr, *dstPn = nullptr;
     if (doPf) CHECK(nat_array(c, CSR_ARR_PF, &dstPf));
     if (fill || convQ) CHECK(nat_array(c, CSR_ARR_PNOISE, &dstPn));
-    HIPOK(hipEventRecord(c->evFork2, c->stream));
-    HIPOK(hipStreamWaitEvent(c->side, c->evFork2, 0));
+    CHECK(fork_side(c, c->evFork2));
     if (doPf || convQ) {
         ExpList L;
         memset(&L, 0, sizeof(L));
@@ -702,7 +720,7 @@ static int early_cov_exports(csr_ctx *c, const Prm &p, uint32_t flags, bool with
             }
         }
         Scope sc(c, "export_natural", c->side);
-        hipLaunchKernelGGL(k_export_tiled, dim3((int)(c->NG * (c->B / 32))), dim3(256), 0, c->side, p, L);
+        hipLaunchKernelGGL(k_export_tiled, tile_grid(c), dim3(256), 0, c->side, p, L);
     }
     LAUNCH_CHECK("k_export_tiled (early Pf)");
     if (doPf) c->where[CSR_ARR_PF].nat = true;
@@ -715,8 +733,10 @@ static int early_cov_exports(csr_ctx *c, const Prm &p, uint32_t flags, bool with
 
 // split: the caller pipelines everything behind the bit-exact state chain per group of chains (step_pipelined); if that chain
 // went out as one barrier-free launch the pass returns right behind it (c->sbp.active) without the NIS / NLL epilogue.
-static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned char *active, bool defer = false,
-                        bool side = false, bool natOut = false, bool split = false) {
+static int forward_impl(csr_ctx *c, const FwdPass &pass) {
+    const uint32_t flags = pass.flags;
+    const bool wantD = pass.wantD, natOut = pass.natOut, side = pass.side, split = pass.split;
+    const unsigned char *const active = pass.active;
     if (!c->statsValid) return fail("csr_batch_stats must run before the forward pass");
     // the resident statistics carry {S2c, log R} as a float32 pair (computed in the 2-ulp mode) and the context is back in the
     // bit-exact mode: that mode's D / NLL / lambda E-step promise float64 statistics -- recompute them
@@ -732,15 +752,15 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
     Prm p = c->p;
     p.flags = flags;
     p.chainActive = active;
-    if (c->kapIn) p.tKap = c->kapIn;                                  // ECM sweep: the kappa of the previous sweep's E-step
+    if (pass.kappaIn) p.tKap = pass.kappaIn;                          // ECM sweep: the kappa of the previous sweep's E-step
     p.qFromMult = (flags & (F_APN | F_QSCALE | F_KAPPA)) ? 0 : 1;     // constant process noise: pNoise is not stored
     // inner ECM sweeps: only the smoother reads this pass's pNoise (diagonal base process noise: its two diagonal entries,
     // 8 B instead of 16) and nobody its predicted variance (no NIS/NLL epilogue)
-    p.qFromKappa = (c->sweepSkipQ && !p.qFromMult && !(flags & F_APN) && c->qDiagonal) ? 1 : 0;
-    p.storePP = (wantD || !c->sweepSkipQ) ? 1 : 0;
+    p.qFromKappa = (pass.sweep && !p.qFromMult && !(flags & F_APN) && c->qDiagonal) ? 1 : 0;
+    p.storePP = (wantD || !pass.sweep) ? 1 : 0;
     c->fwdQCompact = p.qFromKappa != 0;
-    defer = defer && c->deferEnabled;
-    c->pendFwdNat = natOut;
+    const bool defer = pass.defer && c->deferEnabled;
+    c->last.fwd = pass;
     const bool seq = (flags & F_APN) && !(flags & F_QSCALE);
     if (seq) {
         Scope sc(c, "fwd_apn_sequential");
@@ -750,7 +770,7 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
     } else {
         bool dP = defer && c->optimistic[ST_P], dX = defer && c->optimistic[ST_X];
         bool nisInChain = false;
-        if (wantD && natOut && c->natOutEnabled && c->natOutD) {        // D straight into the reference layout
+        if (wantD && natOut) {          // D straight into the reference layout
             const size_t tileBytes = sizeof(float) * 64 * (size_t)(c->B + 1);
             bool ok = true;
             if (tileBytes > 48 * 1024 && !c->dstatLdsRaised) {      // 256-bin blocks: 65.8 KB of dynamic LDS
@@ -770,7 +790,7 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
         // pipeline).  With up to four confirmation passes per stage (check_stages) the few blocks that need more are simply
         // repaired: the window starts 16 bins above the plain one (96: ECM iteration 3.01 -> 2.85 ms at genome scale, 1.02 ->
         // 0.88 ms on a 1/8-genome shard) and widens itself like the others when many blocks fail.
-        if (c->fuseFwd && c->xTolUlps > 0) {
+        if (c->xTolUlps > 0) {
             // one stage (counter of the covariance stage; the window covers the state chain's needs too)
             const bool mult = (flags & (F_KAPPA | F_LAMBDA | F_QSCALE)) != 0;
             if (c->warmP < c->warmX) c->warmP = c->warmX;
@@ -783,29 +803,29 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
                 CHECK(ws_prepare(c, p, true, &w));
                 if (w) c->fwdWindow = w;
             }
-            if (natOut && c->natOutEnabled && c->natOutFwd && c->mdl.state_dim == 2) {     // xf / Pf also in the reference layout
+            if (natOut && c->mdl.state_dim == 2) {      // xf / Pf also in the reference layout
                 CHECK(nat_array(c, CSR_ARR_XF, &p.natXs));
                 CHECK(nat_array(c, CSR_ARR_PF, &p.natPs));
                 p.natOut = 1;
                 produced(c, {CSR_ARR_XF, CSR_ARR_PF}, W_BLOCKED | W_NAT);
                 // the constant process noise depends on nothing: its reference-layout rows are filled on the side stream beside
                 // the (latency-bound) forward chain instead of after the smoother
-                if (c->earlyPf && active == nullptr) CHECK(early_cov_exports(c, p, flags, false));
+                if (active == nullptr) CHECK(early_cov_exports(c, p, flags, false));
                 // NIS / NLL inside the chain's tile walker (csr_device.h FwdTrendFusedT::step_nis): no epilogue kernel, no
                 // predicted-variance track.  (Per-bin NLL in D keeps the epilogue: its log terms belong off the serial path.)
-                if (c->nisInChainEnabled && wantD && p.natD != nullptr && !(flags & F_NLL_IN_D)) {
+                if (wantD && p.natD != nullptr && !(flags & F_NLL_IN_D)) {
                     p.nisInChain = 1;
                     p.storePP = 0;
                     nisInChain = true;
                 }
                 // constant process noise and nobody left to read the blocked xf / Pf but the smoother (which then reads the
                 // reference-layout arrays through its tiles): the tile walker stores nothing in the blocked layout
-                if (c->natOnlyEnabled && p.qFromMult && p.chainQ == nullptr && (nisInChain || !wantD) && (c->B % 8) == 0 && unit_f(c, p)) {
+                if (p.qFromMult && p.chainQ == nullptr && (nisInChain || !wantD) && (c->B % 8) == 0 && unit_f(p)) {
                     p.natOnly = 1;
                     produced(c, {CSR_ARR_XF, CSR_ARR_PF}, W_NAT);
                 }
             }
-            if (c->mdl.state_dim == 2 && unit_f(c, p)) CHECK(run_chain<FwdTrendFusedT<true>>(c, p, "fwd_chain", "fwd_fix", ST_P, dP));
+            if (c->mdl.state_dim == 2 && unit_f(p)) CHECK(run_chain<FwdTrendFusedT<true>>(c, p, "fwd_chain", "fwd_fix", ST_P, dP));
             else if (c->mdl.state_dim == 2) CHECK(run_chain<FwdTrendFused>(c, p, "fwd_chain", "fwd_fix", ST_P, dP));
             else CHECK(run_chain<FwdLevelFused>(c, p, "fwd_chain", "fwd_fix", ST_P, dP));
             ws_launched(c, p, true);
@@ -814,15 +834,13 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
             c->fwdWindow = nullptr;
         } else if (c->mdl.state_dim == 2) {
             c->lastFwdWindow = nullptr;
-            const bool sbX = c->xTolUlps == 0 && c->sbState && !c->seqState;
-            const bool seqX = c->xTolUlps == 0 && c->seqState;
-            // (round 4: the covariance chain is validated optimistically here too.  Rounds 1-3 read its counters back before the
-            // millisecond state chains -- one host round trip, ~0.1 ms per forward pass -- although a failed validation is as
-            // rare here as in the 2-ulp mode and costs the same replay of the pass.  The sequential yardstick keeps the round trip.)
+            // bit-exact mode: the superblock state chain, or the sequential yardstick (CONSENRICH_AMD_SEQ_STATE=1)
+            const bool seqX = c->seqState;
+            // (the covariance chain is validated optimistically here too: a failed validation is as rare as in the 2-ulp mode and
+            // costs the same replay of the pass.  The sequential yardstick keeps the host round trip.)
             if (seqX) dP = false;
-            c->gainNat = false;
             Prm pc = p;
-            if (sbX && CSR_GAIN_NAT) {
+            if (!seqX) {
                 // the superblock state chain reads its records in the reference layout: the covariance chain writes the gain
                 // records there itself (and Pf, when this pass's Pf is an output), through LDS tiles -- no conversion launch
                 // between the two chains; the NIS epilogue reads P00pred from the compact track instead of the blocked record
@@ -832,19 +850,19 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
                 pc.natOut = 1;
                 pc.natLag = reinterpret_cast<float *>(c->sbNatGain);
                 pc.natPs = nullptr;
-                if (natOut && c->earlyPf && active == nullptr && c->natOutEnabled) {
+                if (natOut && active == nullptr) {
                     CHECK(nat_array(c, CSR_ARR_PF, &pc.natPs));
                     produced(c, {CSR_ARR_PF}, W_BLOCKED | W_NAT);
                     // a pipelined step with one constant process noise: the smoother of every group reads xf / Pf in the reference
                     // layout (k_smooth_natin) -- no blocked copy of Pf
-                    if (c->natOnlyEnabled && split && p.qFromMult && p.chainQ == nullptr && (c->B % 8) == 0 && unit_f(c, p)) {
+                    if (split && p.qFromMult && p.chainQ == nullptr && (c->B % 8) == 0 && unit_f(p)) {
                         pc.natOnly = 1;
                         produced(c, {CSR_ARR_PF}, W_NAT);
                     }
                 }
                 c->gainNat = true;
             }
-            if (unit_f(c, p)) CHECK(run_chain<FwdPTrendT<true>>(c, pc, "fwd_cov_chain", "fwd_cov_fix", ST_P, dP));
+            if (unit_f(p)) CHECK(run_chain<FwdPTrendT<true>>(c, pc, "fwd_cov_chain", "fwd_cov_fix", ST_P, dP));
             else CHECK(run_chain<FwdPTrend>(c, pc, "fwd_cov_chain", "fwd_cov_fix", ST_P, dP));
             if (seqX) {
                 // bit-exact mode: the state recursion cannot be validated speculatively in reasonable time (see
@@ -858,15 +876,11 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
                                        c->dChainFirst, c->dChainNb);
                 LAUNCH_CHECK("k_state_seq_trend");
                 dX = false;
-            } else if (sbX) {
+            } else {
                 // (the early covariance exports fork off behind the state chain's own record conversion)
-                const bool early = natOut && c->earlyPf && active == nullptr && c->natOutEnabled;
+                const bool early = natOut && active == nullptr;
                 CHECK(state_chain_systolic(c, p, early, flags, split ? 1 : 0));
                 dX = false;
-            } else {
-                // (round 6: the form that validated the levelTrend state chain on the batch's own blocks -- it only ever ran under the
-                // retired switches CONSENRICH_AMD_FUSE=0 / CONSENRICH_AMD_SB_STATE=0 -- is gone)
-                return fail("internal: no state chain for this mode");
             }
         } else {
             CHECK(run_chain<FwdPLevel>(c, p, "fwd_cov_chain", "fwd_cov_fix", ST_P, dP));
@@ -878,14 +892,10 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
             join_side(c);
             hipStream_t st = c->stream;
             if (side && c->deferEnabled) {
-                HIPOK(hipEventRecord(c->evFork, c->stream));
-                HIPOK(hipStreamWaitEvent(c->side, c->evFork, 0));
+                CHECK(fork_side(c, c->evFork));
                 st = c->side;
             }
-            {
-                Scope sc(c, "chain_sums", st);
-                hipLaunchKernelGGL(k_chain_sums, dim3((int)c->chains.size()), dim3(1024), 0, st, p, c->dChainFirst, c->dChainNb);
-            }
+            launch_chain_sums(c, p, st);
             LAUNCH_CHECK("k_chain_sums");
             if (st == c->side) {
                 HIPOK(hipEventRecord(c->evJoin, c->side));
@@ -894,35 +904,30 @@ static int forward_impl(csr_ctx *c, uint32_t flags, bool wantD, const unsigned c
             }
         } else
         if (wantD && !c->sbp.active) CHECK(forward_epilogue(c, p, side && c->deferEnabled));
-        if (dP || dX) {
-            c->pendFwd = true;
-            c->pendFlags = flags;
-            c->pendWantD = wantD;
-            c->pendActiveF = active;
-        }
+        if (dP || dX) c->last.fwdPending = true;
     }
     c->haveFwd = true;
     c->haveBwd = false;
     c->fwdInternal = true;
-    c->fwdFlags = flags;
     return 0;
 }
 
-// estep: 0 = plain smoother; 1 = ECM sweep whose kappa E-step is evaluated inside the smoother chain, moments stored;
-//        2 = same, but the smoothed moments are not stored (an inner sweep nobody reads them from)
-static int backward_impl(csr_ctx *c, bool wantLag, const unsigned char *active, bool defer = false, bool natOut = false,
-                         int estep = 0, bool preferNatIn = false) {
+// (the lag-one covariance is produced by the smoother's own main phase: there is no pass without it)
+static int backward_impl(csr_ctx *c, const BwdPass &pass) {
     if (!c->haveFwd) return fail("forward results are not resident: run csr_batch_forward first");
+    const unsigned char *const active = pass.active;
+    const int estep = pass.estep;
+    const bool preferNatIn = pass.preferNatIn;
     Prm p = c->p;
-    p.flags = c->fwdFlags;
+    p.flags = c->last.fwd.flags;
     p.chainActive = active;
     p.estepKappa = estep != 0 ? 1 : 0;
     p.storeMoments = estep == 2 ? 0 : 1;
-    if (c->kapIn) p.tKap = c->kapIn;
-    p.tKapOut = c->kapOut ? c->kapOut : p.tKap;
+    if (pass.kappaIn) p.tKap = pass.kappaIn;
+    p.tKapOut = pass.kappaOut ? pass.kappaOut : p.tKap;
     p.qFromKappa = c->fwdQCompact ? 1 : 0;       // the resident forward pass stored qf instead of pNoise
-    c->pendEstep = estep;
-    natOut = natOut && c->natOutEnabled && c->mdl.state_dim == 2;
+    c->last.bwd = pass;
+    const bool natOut = pass.natOut && c->mdl.state_dim == 2;      // the smoother writes the reference layout directly
     if (natOut) {
         CHECK(nat_array(c, CSR_ARR_XS, &p.natXs));
         CHECK(nat_array(c, CSR_ARR_PS, &p.natPs));
@@ -935,10 +940,9 @@ static int backward_impl(csr_ctx *c, bool wantLag, const unsigned char *active, 
     const bool need = !xfW.blocked || !pfW.blocked;
     if (need || preferNatIn) {
         const bool pcq = p.chainQ != nullptr;
-        const bool constQ = c->fwdInternal && !(c->fwdFlags & (F_APN | F_QSCALE | F_KAPPA));
         const bool natValid = pfW.nat && (xfW.nat || preferNatIn);
-        if (c->natInEnabled && natOut && !pcq && !p.qFromKappa && natValid && (need || constQ) && (stage_warm(c, ST_B) % 8) == 0 &&
-            unit_f(c, p)) {
+        if (c->natInEnabled && natOut && !pcq && !p.qFromKappa && natValid && (need || const_q(c)) && (stage_warm(c, ST_B) % 8) == 0 &&
+            unit_f(p)) {
             float *natXf, *natPf;
             CHECK(nat_array(c, CSR_ARR_XF, &natXf));
             CHECK(nat_array(c, CSR_ARR_PF, &natPf));
@@ -951,11 +955,8 @@ static int backward_impl(csr_ctx *c, bool wantLag, const unsigned char *active, 
     }
     new_smoothed_fit(c);
     if (natOut) produced(c, {CSR_ARR_XS, CSR_ARR_PS, CSR_ARR_LAG}, W_NAT);   // this smoother writes the reference layout only
-    c->pendNatOut = natOut;
-    // constant process noise (no kappa / qScale / adaptive noise): the smoother need not read pNoise at all
-    p.qFromMult = (c->fwdInternal && !(c->fwdFlags & (F_APN | F_QSCALE | F_KAPPA))) ? 1 : 0;
-    (void)wantLag;      // the lag-one covariance is produced by the smoother's own main phase
-    const bool dB = defer && c->deferEnabled && c->optimistic[ST_B];
+    p.qFromMult = const_q(c) ? 1 : 0;       // constant process noise: the smoother need not read pNoise at all
+    const bool dB = pass.defer && c->deferEnabled && c->optimistic[ST_B];
     if (!natOut && c->mdl.state_dim == 2 && estep != 0) {       // ECM sweep: window from the previous sweep's carries
         int *w = nullptr;
         CHECK(ws_prepare(c, p, false, &w));
@@ -963,20 +964,17 @@ static int backward_impl(csr_ctx *c, bool wantLag, const unsigned char *active, 
     }
     struct BwdWindowReset { csr_ctx *c; ~BwdWindowReset() { c->bwdWindow = nullptr; } } bwdWindowReset{c};
     if (p.qFromKappa && !natOut) {
-        if (c->mdl.state_dim == 2 && unit_f(c, p)) CHECK(run_chain<BwdTrendQ2T<true>>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
+        if (c->mdl.state_dim == 2 && unit_f(p)) CHECK(run_chain<BwdTrendQ2T<true>>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
         else if (c->mdl.state_dim == 2) CHECK(run_chain<BwdTrendQ2>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
         else CHECK(run_chain<BwdLevelQ2>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
     } else if (p.qFromKappa) {
         return fail("internal: compact process noise is only produced by ECM sweeps (no reference-layout outputs)");
-    } else if (c->mdl.state_dim == 2 && unit_f(c, p)) CHECK(run_chain<BwdTrendT<true>>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
+    } else if (c->mdl.state_dim == 2 && unit_f(p)) CHECK(run_chain<BwdTrendT<true>>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
     else if (c->mdl.state_dim == 2) CHECK(run_chain<BwdTrend>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
     else CHECK(run_chain<BwdLevel>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
     ws_launched(c, p, false);
     c->lastBwdWindow = c->bwdWindow;
-    if (dB) {
-        c->pendBwd = true;
-        c->pendActiveB = active;
-    }
+    if (dB) c->last.bwdPending = true;
     c->haveBwd = true;
     return 0;
 }
@@ -1038,23 +1036,26 @@ static int check_stages(csr_ctx *c) {
 static int settle(csr_ctx *c) {
     join_side(c);
     join_pf(c);
-    if (!c->pendFwd && !c->pendBwd) return 0;
+    if (!anything_pending(c)) return 0;
     CHECK(read_mail(c, c->mailBytes));
-    const bool pf = c->pendFwd, pb = c->pendBwd;
-    const uint32_t pe = c->pendExport;
-    c->pendFwd = c->pendBwd = false;
-    c->pendExport = 0;
+    const bool pf = c->last.fwdPending, pb = c->last.bwdPending;
+    const uint32_t pe = c->last.exports;
+    drop_pending(c);
     const int firstFail = check_stages(c);
     if (firstFail < 0) return 0;
     c->rs.pipeline_redos += 1;     // pipelines re-run after a failed optimistic validation
+    // the recorded passes again, in order, validated synchronously on this stream alone (copies: the passes record themselves)
+    FwdPass fwd = c->last.fwd;
+    fwd.defer = fwd.side = fwd.split = false;
+    BwdPass bwd = c->last.bwd;
+    bwd.defer = bwd.preferNatIn = false;
     if (firstFail <= ST_X && pf) {
-        const bool bwdToo = pb || c->haveBwd;
-        CHECK(forward_impl(c, c->pendFlags, c->pendWantD, c->pendActiveF, false, false, c->pendFwdNat));
-        const bool nat = c->pendNatOut;
-        const int es = c->pendEstep;
-        if (bwdToo) CHECK(backward_impl(c, true, pb ? c->pendActiveB : c->pendActiveF, false, nat, es));
+        const bool bwdToo = pb || c->haveBwd;      // (a smoother that validated synchronously behind the failed stage ran on its results)
+        if (!pb) bwd.active = fwd.active;
+        CHECK(forward_impl(c, fwd));
+        if (bwdToo) CHECK(backward_impl(c, bwd));
     } else if (pb) {
-        CHECK(backward_impl(c, true, c->pendActiveB, false, c->pendNatOut, c->pendEstep));
+        CHECK(backward_impl(c, bwd));
     }
     if (pe) CHECK(export_impl(c, pe));      // arrays exported from the unvalidated results
     CHECK(read_mail(c, c->mailBytes));
@@ -1064,7 +1065,7 @@ static int settle(csr_ctx *c) {
 
 static int read_sums(csr_ctx *c, double *sum_d, double *sum_nll) {
     const size_t nc = c->chains.size();
-    const bool pending = c->pendFwd || c->pendBwd;
+    const bool pending = anything_pending(c);
     CHECK(settle(c));
     if (!pending) CHECK(read_mail(c, c->mailBytes));
     const double *hs = reinterpret_cast<const double *>(c->hMail + MAIL_HDR);
@@ -1076,7 +1077,7 @@ static int read_sums(csr_ctx *c, double *sum_d, double *sum_nll) {
 extern "C" int csr_batch_forward(csr_ctx *c, uint32_t flags, double *sum_d, double *sum_nll) {
     CHECK(need(c));
     CHECK(settle(c));
-    CHECK(forward_impl(c, flags, true, nullptr, true, false, true));
+    CHECK(forward_impl(c, {.flags = flags, .wantD = true, .defer = true, .natOut = true}));
     if (sum_d || sum_nll) CHECK(read_sums(c, sum_d, sum_nll));
     return 0;
 }
@@ -1091,14 +1092,14 @@ extern "C" int csr_batch_forward_masked(csr_ctx *c, uint32_t flags, const unsign
     std::vector<unsigned char> act(chain_mask, chain_mask + nc);
     HIPOK(hipMemcpyAsync(c->dActive, act.data(), nc, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
-    CHECK(forward_impl(c, flags, true, c->dActive, true, false, false));
+    CHECK(forward_impl(c, {.flags = flags, .wantD = true, .active = c->dActive, .defer = true}));
     if (sum_d || sum_nll) CHECK(read_sums(c, sum_d, sum_nll));
     return 0;
 }
 
 extern "C" int csr_batch_backward(csr_ctx *c) {
     CHECK(need(c));
-    CHECK(backward_impl(c, true, nullptr, true, true));
+    CHECK(backward_impl(c, {.defer = true, .natOut = true}));
     return 0;       // validated at the next settle point
 }
 
@@ -1107,8 +1108,8 @@ extern "C" int csr_batch_backward(csr_ctx *c) {
 extern "C" int csr_batch_forward_backward(csr_ctx *c, uint32_t flags, double *sum_d, double *sum_nll) {
     CHECK(need(c));
     CHECK(settle(c));
-    CHECK(forward_impl(c, flags, true, nullptr, true, true, true));
-    CHECK(backward_impl(c, true, nullptr, true, true));
+    CHECK(forward_impl(c, {.flags = flags, .wantD = true, .defer = true, .side = true, .natOut = true}));
+    CHECK(backward_impl(c, {.defer = true, .natOut = true}));
     if (sum_d || sum_nll) return read_sums(c, sum_d, sum_nll);
     return 0;       // validation stays pending until the next settle point (sums, download, synchronize, new inputs)
 }
@@ -1165,8 +1166,8 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
     if (anyMasked && (anyTiny || anyBig)) CHECK(need_blocked(c, {CSR_ARR_XS, CSR_ARR_PS, CSR_ARR_LAG}, nullptr));
     if (anyTiny) {
         CHECK(push_active());
-        CHECK(forward_impl(c, fl | F_NLL, true, c->dActive, true));
-        CHECK(backward_impl(c, true, c->dActive, true));
+        CHECK(forward_impl(c, {.flags = fl | F_NLL, .wantD = true, .active = c->dActive, .defer = true}));
+        CHECK(backward_impl(c, {.active = c->dActive, .defer = true}));
         CHECK(read_sums(c, nullptr, nll.data()));
         for (int i = 0; i < nc; ++i)
             if (act[i]) { out[i].final_nll = out[i].initial_nll = nll[i]; st[i].done = true; }
@@ -1177,13 +1178,13 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
         bool fwdFresh = false;   // forward results already match the current multipliers
         struct SweepStateReset {     // also on the error paths
             csr_ctx *c;
-            ~SweepStateReset() { c->sweepSkipQ = false; c->kapIn = c->kapOut = nullptr; c->wsActive = c->wsCold = false; }
+            ~SweepStateReset() { c->wsActive = c->wsCold = false; }
         } sweepStateReset{c};
         c->wsSavedF = c->wsSavedB = 0;      // the first sweep of a call starts cold (the data / background may have changed)
         // kappa only (the reference CLI's default, constants.py:270-271): the smoother chain holds the moments of bins k
         // and k+1 and the lag covariance when it finishes bin k, so it evaluates the E-step itself; only the last inner
         // sweep's moments can become the result of this iteration, the others are not even stored.
-        const bool fusedE = c->fuseEstep && cfg->use_kappa && !cfg->use_lambda && !cfg->use_apn && c->mdl.state_dim == 2;
+        const bool fusedE = cfg->use_kappa && !cfg->use_lambda && !cfg->use_apn && c->mdl.state_dim == 2;
         if (fusedE) {
             // The fused E-step must not overwrite the kappa its own sweep's forward pass ran with: were that pass's
             // deferred validation to fail, its re-run would read the NEXT sweep's kappa (one E-step ahead of pyx:8222-8300).
@@ -1198,18 +1199,15 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
             c->wsActive = true;
             float *cur = nullptr;                   // nullptr = the resident kappa (the one this iteration starts from)
             for (int64_t inner = 0; inner < cfg->inner_iters; ++inner) {
-                c->kapIn = cur;
-                c->sweepSkipQ = true;
-                if (!(inner == 0 && skipFirstForward)) CHECK(forward_impl(c, fl, false, c->dActive, defer));
-                c->sweepSkipQ = false;
-                c->kapOut = c->kapScratch[inner & 1];
-                CHECK(backward_impl(c, true, c->dActive, defer, false, inner + 1 == cfg->inner_iters ? 1 : 2));
-                cur = c->kapOut;
-                c->kapOut = nullptr;
+                if (!(inner == 0 && skipFirstForward))
+                    CHECK(forward_impl(c, {.flags = fl, .active = c->dActive, .defer = defer, .sweep = true, .kappaIn = cur}));
+                float *const next = c->kapScratch[inner & 1];
+                CHECK(backward_impl(c, {.active = c->dActive, .defer = defer, .estep = inner + 1 == cfg->inner_iters ? 1 : 2,
+                                        .kappaIn = cur, .kappaOut = next}));
+                cur = next;
             }
-            c->kapIn = cur;
-            CHECK(forward_impl(c, fl | F_NLL, true, c->dActive, defer));      // pyx:8300 (stores everything: it is the
-            c->kapIn = nullptr;                                               // forward pass that stays resident)
+            // pyx:8300 (stores everything: it is the forward pass that stays resident)
+            CHECK(forward_impl(c, {.flags = fl | F_NLL, .wantD = true, .active = c->dActive, .defer = defer, .kappaIn = cur}));
             c->wsActive = false;
             iterKappa = cur;
             return 0;
@@ -1220,12 +1218,10 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
                 // ONE settle point per iteration: every stage of every sweep is validated optimistically; if any of them
                 // re-ran blocks, the whole iteration is replayed with synchronous validation from the kappa it started with
                 // (still resident: it is replaced only below, once the iteration stands).
-                const bool defer = c->deferIteration && c->deferEnabled;
-                CHECK(launch_iteration(defer, fwdFresh));
+                CHECK(launch_iteration(c->deferEnabled, fwdFresh));
                 CHECK(read_mail(c, c->mailBytes));
-                const bool hadPending = c->pendFwd || c->pendBwd;
-                c->pendFwd = c->pendBwd = false;
-                c->pendExport = 0;
+                const bool hadPending = anything_pending(c);
+                drop_pending(c);        // (the iteration is replayed here, as a whole, not pass by pass at a settle point)
                 if (hadPending && check_stages(c) >= 0) {
                     c->rs.pipeline_redos += 1;
                     c->wsCold = true;               // the replay starts every window cold (and records fresh checkpoints)
@@ -1233,7 +1229,7 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
                     c->wsCold = false;
                     CHECK(rcReplay);
                     CHECK(read_mail(c, c->mailBytes));
-                    c->pendFwd = c->pendBwd = false;
+                    drop_pending(c);
                     for (int stg = ST_P; stg <= ST_B; ++stg) (void)take_fresh(c, stg);
                 }
                 if (iterKappa) {      // the iteration's kappa becomes the resident one (for the chains of this iteration)
@@ -1259,12 +1255,10 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
                 for (int i = 0; i < nc; ++i) nll[i] = mailSums[nc + i];
             } else {
                 for (int64_t inner = 0; inner < cfg->inner_iters; ++inner) {
-                    c->sweepSkipQ = true;
-                    if (!fwdFresh) CHECK(forward_impl(c, fl, false, c->dActive, true));
+                    if (!fwdFresh) CHECK(forward_impl(c, {.flags = fl, .active = c->dActive, .defer = true, .sweep = true}));
                     fwdFresh = false;
-                    CHECK(backward_impl(c, true, c->dActive, true, false, 0));
+                    CHECK(backward_impl(c, {.active = c->dActive, .defer = true}));
                     CHECK(settle(c));          // the E-step kernels consume validated results and update in place
-                    c->sweepSkipQ = false;
                     Prm p = c->p;
                     p.flags = fl;
                     p.chainActive = c->dActive;
@@ -1279,7 +1273,7 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
                         LAUNCH_CHECK("k_estep_kappa");
                     }
                 }
-                CHECK(forward_impl(c, fl | F_NLL, true, c->dActive, true));      // pyx:8300
+                CHECK(forward_impl(c, {.flags = fl | F_NLL, .wantD = true, .active = c->dActive, .defer = true}));    // pyx:8300
                 CHECK(read_sums(c, nullptr, nll.data()));
             }
             // the multipliers do not change until the next E-step: the next sweep may reuse this forward pass,
@@ -1318,8 +1312,7 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
             out[i].final_nll = st[i].prev;
         }
     }
-    c->sweepSkipQ = false;
-    c->fwdFlags = fl;
+    c->last.fwd.flags = fl;     // the multipliers the resident fit stands for (nothing is pending here)
     c->haveFwd = c->haveBwd = true;
     return 0;
 }
@@ -1331,7 +1324,7 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
 // Exports may be queued behind an optimistically validated pipeline: they are re-issued by settle() if it fails.
 extern "C" int csr_batch_export(csr_ctx *c, uint32_t what) {
     CHECK(need(c));
-    if (c->pendFwd || c->pendBwd) c->pendExport |= what;
+    if (anything_pending(c)) reexport_on_replay(c, what);
     return export_impl(c, what);
 }
 
@@ -1345,7 +1338,7 @@ static int flush_export(csr_ctx *c, ExpList &L) {
     if (L.count == 0) return 0;
     {
         Scope sc(c, "export_natural");
-        hipLaunchKernelGGL(k_export_tiled, dim3((int)(c->NG * (c->B / 32))), dim3(256), 0, c->stream, c->p, L);
+        hipLaunchKernelGGL(k_export_tiled, tile_grid(c), dim3(256), 0, c->stream, c->p, L);
     }
     LAUNCH_CHECK("k_export_tiled");
     L.count = 0;
@@ -1424,7 +1417,7 @@ static int export_impl(csr_ctx *c, uint32_t what) {
         if (!lateD) CHECK(need_natural(c, L, CSR_ARR_D, p.tD, 1, 1, 0, false));
         CHECK(need_natural(c, L, CSR_ARR_XF, (const float *)p.tXf, 2, nv, 0, false));
         CHECK(need_natural(c, L, CSR_ARR_PF, (const float *)p.tPf, 4, nm, 0, false));
-        const bool constQ = c->fwdInternal && !(c->fwdFlags & (F_APN | F_QSCALE | F_KAPPA));
+        const bool constQ = const_q(c);
         if (c->where[CSR_ARR_PNOISE].nat) {
             // (the constant process noise was filled underneath the state chain as well)
         } else if (constQ && p.chainQ == nullptr) {
@@ -1478,42 +1471,27 @@ static int step_tail(csr_ctx *c, const Prm &pf, const unsigned char *dmask, cons
     Prm pt = pf;
     pt.chainActive = dmask;
     pt.prevKind = CK_NONE;
-    float *natXf;
-    CHECK(nat_array(c, CSR_ARR_XF, &natXf));
     // one constant process noise: the smoother reads xf / Pf of these chains in the reference layout (k_smooth_natin) and starts
     // at once; the blocked copy of xf only the NIS / NLL epilogue needs is made on the side stream in front of it
-    const bool constQ = c->fwdInternal && !(c->fwdFlags & (F_APN | F_QSCALE | F_KAPPA));
-    const bool natTail = c->natOnlyEnabled && c->natInEnabled && c->where[CSR_ARR_PF].nat && constQ && pf.chainQ == nullptr && (c->B % 8) == 0 &&
-                         (stage_warm(c, ST_B) % 8) == 0 && unit_f(c, pf);
-    HIPOK(hipEventRecord(c->evFork, c->stream));
-    HIPOK(hipStreamWaitEvent(c->side, c->evFork, 0));
+    const bool natTail = c->natInEnabled && c->where[CSR_ARR_PF].nat && const_q(c) && pf.chainQ == nullptr && (c->B % 8) == 0 &&
+                         (stage_warm(c, ST_B) % 8) == 0 && unit_f(pf);
+    CHECK(fork_side(c, c->evFork));
     hipStream_t imp = natTail ? c->side : c->stream;
     // (the smoother is what the group's residuals wait for: when it reads the reference layout it is launched FIRST, the
     // epilogue's kernels of the side stream after it -- they were forked above and do not wait for it)
-    if (natTail) CHECK(backward_impl(c, true, dmask, true, true, 0, true));
+    if (natTail) CHECK(backward_impl(c, {.active = dmask, .defer = true, .natOut = true, .preferNatIn = true}));
     if (!runs.empty()) {
         // ONE launch over the wavefront-groups from the first to the last block of these chains: the mask trims what lies between
         // (round 4: a launch per run of chains serialised four 60-us launches behind the state chain for a scattered last group)
         int64_t g0 = runs.front().b0 / 64, g1 = (runs.front().b1 + 63) / 64;
         for (const ChainRun &r : runs) { g0 = std::min(g0, r.b0 / 64); g1 = std::max(g1, (r.b1 + 63) / 64); }
-        Scope sc(c, "state_reblock_out", imp);
-        hipLaunchKernelGGL(k_import_tiled<float2>, dim3((int)((g1 - g0) * (c->B / 32))), dim3(256), 0, imp, pt,
-                           reinterpret_cast<const float2 *>(natXf), pt.tXf, g0);
+        CHECK(import_xf_blocked(c, pt, imp, g0, g1 - g0));
     }
-    LAUNCH_CHECK("k_import_tiled_f2");
     // the NIS / NLL epilogue beside the (latency-bound) smoother chain, on the side stream
-    if (!natTail) {
-        HIPOK(hipEventRecord(c->evFork, c->stream));
-        HIPOK(hipStreamWaitEvent(c->side, c->evFork, 0));
-    }
-    {
-        Scope sc(c, "fwd_dstat", c->side);
-        if (pt.natD) hipLaunchKernelGGL(k_fwd_dstat<true>, dim3((int)c->NG), dim3(256), sizeof(float) * 64 * (c->B + 1), c->side, pt);
-        else hipLaunchKernelGGL(k_fwd_dstat<false>, dim3((int)c->NG), dim3(256), 0, c->side, pt);
-    }
-    LAUNCH_CHECK("k_fwd_dstat");
+    if (!natTail) CHECK(fork_side(c, c->evFork));
+    CHECK(launch_dstat(c, pt, c->side));
     HIPOK(hipEventRecord(c->evJoin, c->side));
-    if (!natTail) CHECK(backward_impl(c, true, dmask, true, true, 0, false));
+    if (!natTail) CHECK(backward_impl(c, {.active = dmask, .defer = true, .natOut = true}));
     CHECK(flush_pending_check(c));              // (the residual launches below cover a part of the batch each: no folded check)
     if (what & CSR_EXPORT_RESID)
         for (const ChainRun &r : runs) CHECK(launch_resid(c, r.off, r.len, false));
@@ -1531,14 +1509,14 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     *handled = false;
     // (round 4: per-bin multipliers and per-chain base matrices pipeline as well -- their process noise goes to the reference
     // layout underneath the state chain with Pf, early_cov_exports; the sequential APN pass has no state chain to hide behind)
-    if (!(c->tailSplit && c->xTolUlps == 0 && c->mdl.state_dim == 2 && c->sbState && !c->seqState && c->sbAsync &&
+    if (!(c->tailSplit && c->xTolUlps == 0 && c->mdl.state_dim == 2 && !c->seqState && c->sbAsync &&
           c->deferEnabled && !((flags & F_APN) && !(flags & F_QSCALE)) &&
           !(what & CSR_EXPORT_MULT) && c->chains.size() >= 2 && c->chains.size() <= 4096))
         return 0;
     CHECK(settle(c));
-    CHECK(forward_impl(c, flags, true, nullptr, true, false, true, true));
+    CHECK(forward_impl(c, {.flags = flags, .wantD = true, .defer = true, .natOut = true, .split = true}));
     if (!c->sbp.active) {               // the state chain did not go out as one launch: the pass is complete, carry on as usual
-        CHECK(backward_impl(c, true, nullptr, true, true));
+        CHECK(backward_impl(c, {.defer = true, .natOut = true}));
         if (what) CHECK(csr_batch_export(c, what));
         *handled = true;
         return 0;
@@ -1547,14 +1525,9 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     if (!(c->where[CSR_ARR_D].nat && c->where[CSR_ARR_PF].nat && c->where[CSR_ARR_PNOISE].nat)) {
         // an output of this pass still needs a conversion launch of its own (export_impl): no pipelining, finish in order
         CHECK(state_chain_systolic(c, pf, false, flags, 2));
-        Prm pt = pf;
-        float *natXf;
-        CHECK(nat_array(c, CSR_ARR_XF, &natXf));
-        hipLaunchKernelGGL(k_import_tiled<float2>, dim3((int)(c->NG * (c->B / 32))), dim3(256), 0, c->stream, pt,
-                           reinterpret_cast<const float2 *>(natXf), pt.tXf, (int64_t)0);
-        LAUNCH_CHECK("k_import_tiled_f2");
+        CHECK(import_xf_blocked(c, pf, c->stream, 0, c->NG, false));
         CHECK(forward_epilogue(c, pf, true));
-        CHECK(backward_impl(c, true, nullptr, true, true));
+        CHECK(backward_impl(c, {.defer = true, .natOut = true}));
         if (what) CHECK(csr_batch_export(c, what));
         *handled = true;
         return 0;
@@ -1637,15 +1610,12 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     if (anyRest) CHECK(launch_group(rest));
     HIPOK(hipEventRecord(c->evTailJoin, c->tail));
     HIPOK(hipStreamWaitEvent(mainStream, c->evTailJoin, 0));
-    {
-        Scope sc(c, "chain_sums");
-        Prm ps = pf;
-        ps.chainActive = nullptr;
-        hipLaunchKernelGGL(k_chain_sums, dim3((int)c->chains.size()), dim3(1024), 0, c->stream, ps, c->dChainFirst, c->dChainNb);
-    }
+    Prm ps = pf;
+    ps.chainActive = nullptr;
+    launch_chain_sums(c, ps, c->stream);
     LAUNCH_CHECK("k_chain_sums");
-    c->pendActiveB = nullptr;           // a replay after a failed optimistic validation covers every chain
-    if (c->pendBwd) c->pendExport |= what;
+    replay_covers_every_chain(c);
+    if (c->last.bwdPending) reexport_on_replay(c, what);
     c->rs.tail_groups += phase;
     *handled = true;
     return 0;
@@ -1666,7 +1636,7 @@ extern "C" int csr_batch_step(csr_ctx *c, uint32_t flags, uint32_t what, double 
 extern "C" int csr_batch_step_forward(csr_ctx *c, uint32_t flags, uint32_t what, double *sum_d, double *sum_nll) {
     CHECK(csr_batch_stats(c));
     CHECK(settle(c));
-    CHECK(forward_impl(c, flags, true, nullptr, true, false, true));
+    CHECK(forward_impl(c, {.flags = flags, .wantD = true, .defer = true, .natOut = true}));
     if (what & CSR_EXPORT_FORWARD) CHECK(csr_batch_export(c, CSR_EXPORT_FORWARD));
     if (sum_d || sum_nll) return csr_batch_sums(c, sum_d, sum_nll);
     return 0;

@@ -150,12 +150,10 @@ extern "C" int csr_backward_pass(const csr_model *mdl, int64_t m, int64_t n, con
     CHECK(import_nat(c, Pf, d * d, n, 0, (float *)c->p.tPf, 4));
     if (n > 1) CHECK(import_nat(c, pnoise, d * d, n - 1, 0, (float *)c->p.tQ, 4));
     c->haveFwd = true;
-    c->fwdInternal = false;
-    c->fwdQCompact = false;
+    forward_imported(c);
     // the caller's xf / Pf ARE the blocked copies now: whatever a previous resident pass left in the reference layout is not theirs
     produced(c, {CSR_ARR_XF, CSR_ARR_PF, CSR_ARR_PNOISE}, W_BLOCKED);
-    c->fwdFlags = 0;
-    CHECK(backward_impl(c, true, nullptr));
+    CHECK(backward_impl(c, {}));
     CHECK(csr_batch_export(c, CSR_EXPORT_SMOOTH | CSR_EXPORT_RESID));
     pf.join();
     CHECK(csr_batch_download(c, 0, CSR_ARR_XS, xs));

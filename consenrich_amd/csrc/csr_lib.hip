@@ -25,12 +25,6 @@
 #include <string>
 #include <chrono>
 #include <sys/prctl.h>
-#ifndef CSR_GAIN_NAT
-#define CSR_GAIN_NAT 1       // 0: gain records through the blocked layout and a conversion launch (yardstick; scripts/ sweeps)
-#endif
-#ifndef CSR_STATS_NATSZ
-#define CSR_STATS_NATSZ 1    // 0: the statistics records reach the reference layout through the conversion launch
-#endif
 #include <thread>
 #include <type_traits>
 #include <vector>
@@ -114,6 +108,29 @@ struct DevBuf {
     }
 };
 
+// One forward pass / one smoother pass as its caller describes it (forward_impl, backward_impl).  Everything a pass depends on
+// beyond the resident arrays is in here, so that settle() can replay the pass from the copy kept in csr_ctx::last.
+struct FwdPass {
+    uint32_t flags = 0;
+    bool wantD = false;                     // NIS / NLL track and per-chain sums
+    const unsigned char *active = nullptr;  // device chain mask (nullptr: every chain)
+    bool defer = false;                     // optimistic validation, checked at the next settle point
+    bool side = false;                      // a smoother follows: the epilogue runs beside it on the side stream
+    bool natOut = false;                    // the outputs also go to the reference layout
+    bool split = false;                     // step_pipelined: return right behind a barrier-free state chain
+    bool sweep = false;                     // inner ECM sweep (Prm::qFromKappa, storePP)
+    float *kappaIn = nullptr;               // ECM sweep: the kappa of the previous sweep's E-step (nullptr: the resident one)
+};
+// estep: 0 = plain smoother; 1 = ECM sweep whose kappa E-step is evaluated inside the smoother chain, moments stored;
+//        2 = same, but the smoothed moments are not stored (an inner sweep nobody reads them from)
+struct BwdPass {
+    const unsigned char *active = nullptr;
+    bool defer = false, natOut = false;
+    int estep = 0;
+    bool preferNatIn = false;               // a group's tail of a pipelined step: read xf / Pf in the reference layout
+    float *kappaIn = nullptr, *kappaOut = nullptr;      // ECM sweep with the E-step inside the smoother (nullptr: the resident kappa)
+};
+
 struct csr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -164,24 +181,23 @@ struct csr_ctx {
     // multipliers_changed).  A caller that asks chain by chain therefore converts the batch once, not once per chain.
     struct Where { bool blocked = true, nat = false; };
     std::array<Where, CSR_ARR_COUNT> where{};
-    bool pendNatOut = false, pendFwdNat = false;
-    static constexpr bool natOutD = true;       // the NIS / NLL epilogue writes D in the reference layout itself
+    // The last forward pass and the last smoother pass, as launched: EVERY pass records itself here, deferred or not.  fwdPending /
+    // bwdPending: its optimistic validation has not been read yet; exports: what was exported from the unvalidated results.
+    // settle() replays from these descriptors (drop_pending, replay_covers_every_chain, reexport_on_replay are the only other writers).
+    struct LastPass {
+        FwdPass fwd;
+        BwdPass bwd;
+        bool fwdPending = false, bwdPending = false;
+        uint32_t exports = 0;
+    } last;
     bool dstatLdsRaised = false;
-    // 2-ulp throughput mode, the byte cuts of round 5 (their A/B switch CONSENRICH_AMD_LEAN was retired in round 6; each of them
-    // still has its own conditions at the call site -- per-bin NLL in D, per-bin process noise, per-chain Q):
-    static constexpr bool statsF32Enabled = true;       // {S2c, log R} as one float32 pair
-    static constexpr bool nisInChainEnabled = true;     // NIS / NLL terms inside the fused forward chain's tile walker (no epilogue kernel)
-    static constexpr bool natOnlyEnabled = true;        // constant process noise: xf / Pf only in the reference layout, the smoother reads them there
     bool natInEnabled = true;           // CONSENRICH_AMD_NATIN=0 (tests): the smoother never reads the reference layout -- blocked copies
                                         // a forward pass did not write are brought back first (need_blocked)
     bool sideSumsDone = false;          // the pending side-stream work already includes the per-chain sums (join_side only waits)
     double lastSbLoopUs = 0.0;          // how long the host watched the previous single launch of the state chain (step_pipelined)
     double lastWaitUs[2] = {0.0, 0.0};  // how long the previous host wait for the stream lasted, per wait site (wait_stream polls around that moment)
     bool sbAsyncLdsRaised[3] = {false, false, false};   // per context = per device (HIP keeps the attribute per device)
-    int pendEstep = 0;
-    static constexpr bool fuseEstep = true;     // ECM: kappa E-step inside the smoother chain (levelTrend, no lambda re-weighting)
     bool fwdInternal = false;   // forward results were produced by this library (vs imported through csr_backward_pass)
-    uint32_t fwdFlags = 0;
     Prm p{};
     std::vector<void *> allocs;
     // device arrays not in Prm
@@ -206,16 +222,12 @@ struct csr_ctx {
     // pass + one validation pass, no host round trip); the counters are checked at the next settle point and the
     // pipeline is re-run synchronously from the first stage that did re-run blocks.
     bool deferEnabled = true;
-    static constexpr bool spinWait = true;
-    static constexpr bool fuseFwd = true;       // tolerant validation: covariance and state chains advance in one kernel
-    static constexpr bool unitF1Enabled = true; // F01 == 1: the superblock walker's predicted level is one float32 add
-    static constexpr bool unitFEnabled = true;  // F = [[1, f], [0, 1]] (constructMatrixF) runs the UF instances of the levelTrend chains; any other F the general ones
     bool seqState = false;      // bit-exact validation, levelTrend: one wavefront per chain walks the state chain sequentially (CONSENRICH_AMD_SEQ_STATE=1)
     // bit-exact validation, levelTrend (default): the state chain speculates on SUPERBLOCKS of sbBins bins with an sbWarm-bin
     // window -- two float32-rounded state trajectories need ~10^4 bins to coincide bit for bit (scripts/ubench/merge_time.c),
     // so the batch's own 32..256-bin blocks never validate; the gain / statistics records are re-blocked into a second view
     // of the batch (own block table and carries) for this one chain and the filtered state is re-blocked back
-    static constexpr bool sbState = true;       // (round 6: the form that speculated on the batch's own blocks is gone; CONSENRICH_AMD_SEQ_STATE=1 is the sequential yardstick)
+    // (CONSENRICH_AMD_SEQ_STATE=1 is the sequential yardstick)
     int sbBins = 8192;          // CONSENRICH_AMD_SB_BINS (default: chosen from the batch, ensure_sb_view)
     // k_sb_delta's fallback rule (CONSENRICH_AMD_SB_ADV = "min,from"): walk the rest of a batch when, from round `from` on, the
     // rounds have settled fewer than `min` bins each.  Measured flat between "give up after 20 rounds" (4,20) and "walk as soon
@@ -240,27 +252,19 @@ struct csr_ctx {
         void *carryIn = nullptr, *carryOutA = nullptr, *carryOutB = nullptr;
         unsigned long long *pub = nullptr;      // k_sb_async: carry[NB], {version, final}[NB], control words
     } sb;
-    static constexpr bool natOutEnabled = true; // the smoother writes the reference layout directly
-    static constexpr bool natOutFwd = true;     // ... and so does the fused forward chain
     // debugging switches, read once from the environment at creation (never on the launch path)
     bool dbgLog = false;
     bool optimistic[3] = {true, true, true};
-    bool pendFwd = false, pendBwd = false, sidePending = false;
+    bool sidePending = false;
     double *dChainQ = nullptr;  // per-chain base process noise (csr_batch_set_chain_q), freed with the batch
-    // ECM with the kappa E-step inside the smoother: a sweep's smoother writes kappa into a scratch buffer (kapOut), the next
-    // sweep's forward pass reads it (kapIn); the resident tKap only changes when a whole iteration has been validated
-    // (nullptr = the resident array).  Allocated on first use, freed with the batch.
+    // ECM with the kappa E-step inside the smoother: a sweep's smoother writes kappa into a scratch buffer (BwdPass::kappaOut),
+    // the next sweep's forward pass reads it (FwdPass::kappaIn); the resident tKap only changes when a whole iteration has been
+    // validated.  Allocated on first use, freed with the batch.
     float *kapScratch[2] = {nullptr, nullptr};
-    float *kapIn = nullptr, *kapOut = nullptr;
-    static constexpr bool deferIteration = true;    // ECM (fused E-step): one settle point per iteration, replay on a failed validation
-    bool sweepSkipQ = false;    // the forward pass being launched is an inner ECM sweep (Prm::qFromKappa, storePP)
     bool fwdQCompact = false;   // the resident forward pass stored the diagonal of pNoise (tQ2) instead of pNoise (tQ)
     bool qDiagonal = true;      // the base process noise in use (model's, or every chain's) is diagonal
     bool modelQDiagonal = true, chainQDiagonal = true;
     Prm sidePrm{};              // parameters of the epilogue running on the side stream (its sums follow at the join)
-    uint32_t pendFlags = 0, pendExport = 0;
-    bool pendWantD = false;
-    const unsigned char *pendActiveF = nullptr, *pendActiveB = nullptr;
     // device-resident background update (allocated on first use, freed with the batch)
     struct BgState {
         bool ready = false, haveCur = false;
@@ -310,7 +314,6 @@ struct csr_ctx {
     // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)
     bool pnFillValid = false;
     float pnFillQ[4] = {0.f, 0.f, 0.f, 0.f};
-    static constexpr bool earlyPf = true;       // Pf / constant pNoise are exported underneath the state chain
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -331,6 +334,26 @@ static void produced(csr_ctx *c, std::initializer_list<int> ids, unsigned copies
 static void new_forward_pass(csr_ctx *c) { produced(c, {CSR_ARR_D, CSR_ARR_XF, CSR_ARR_PF, CSR_ARR_PNOISE}, W_BLOCKED); }
 static void new_smoothed_fit(csr_ctx *c) { produced(c, {CSR_ARR_XS, CSR_ARR_PS, CSR_ARR_LAG}, W_BLOCKED); }
 static void multipliers_changed(csr_ctx *c) { produced(c, {CSR_ARR_LAMBDA, CSR_ARR_KAPPA, CSR_ARR_QSCALE}, W_BLOCKED); }
+
+// Pending optimistic validations (csr_ctx::last)
+static bool anything_pending(const csr_ctx *c) { return c->last.fwdPending || c->last.bwdPending; }
+// the pending validations have been read (or their results are gone): nothing is left for settle() to replay
+static void drop_pending(csr_ctx *c) {
+    c->last.fwdPending = c->last.bwdPending = false;
+    c->last.exports = 0;
+}
+// the smoother ran group by group under chain masks (step_pipelined): a replay after a failed validation covers every chain
+static void replay_covers_every_chain(csr_ctx *c) { c->last.bwd.active = nullptr; }
+// arrays exported from unvalidated results: settle() exports them again if it has to replay
+static void reexport_on_replay(csr_ctx *c, uint32_t what) { c->last.exports |= what; }
+// forward results that came in through csr_backward_pass: no pass of this library produced them (flags 0: no multipliers)
+static void forward_imported(csr_ctx *c) {
+    c->fwdInternal = false;
+    c->fwdQCompact = false;
+    c->last.fwd = FwdPass{};
+}
+// the resident forward pass ran with one constant process noise per chain (no kappa / qScale / adaptive noise)
+static bool const_q(const csr_ctx *c) { return c->fwdInternal && !(c->last.fwd.flags & (F_APN | F_QSCALE | F_KAPPA)); }
 
 static int ctx_select(csr_ctx *c) {
     HIPOK(hipSetDevice(c->device));
@@ -353,14 +376,13 @@ static void free_batch(csr_ctx *c) {
     c->allocs.clear();
     c->configured = false;
     c->statsValid = c->haveFwd = c->haveBwd = false;
-    c->pendFwd = c->pendBwd = c->sidePending = false;
-    c->pendExport = 0;
+    drop_pending(c);
+    c->sidePending = false;
     c->dMail = nullptr;
     c->dChainQ = nullptr;
     c->pendChk = csr_ctx::PendingCheck{};
     c->carrySet[0][0] = c->carrySet[0][1] = c->carrySet[1][0] = c->carrySet[1][1] = nullptr;
     c->kapScratch[0] = c->kapScratch[1] = nullptr;
-    c->kapIn = c->kapOut = nullptr;
     c->bg = csr_ctx::BgState{};
     c->dActive = nullptr;
     c->sb = csr_ctx::SbView{};

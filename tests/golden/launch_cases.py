@@ -1,9 +1,10 @@
-"""Call sequences against one batch context and the conversion launches each of them costs.
+"""Call sequences against one batch context and the launches each of them costs.
 
 Shared by `make_golden.py --launches` (writes conversion_launches.json from a library built from the commit BEFORE a change of
 the host layer's bookkeeping) and tests/test_gpu_residency.py (asserts that the library under test launches the same).  The
-record is data only: per mode and sequence, the launch count of every conversion scope of the profile and the number of
-pipeline replays (0: a replay repeats launches)."""
+record is data only: per mode and sequence, the launch count of every profile scope of the pipeline -- the conversions between
+the two layouts and, since the passes became descriptors, the chains, their fix-up and check launches, the state chain, the
+E-steps and the statistics -- and the number of pipeline replays (0: a replay repeats launches)."""
 from __future__ import annotations
 
 import json
@@ -15,7 +16,10 @@ import cases
 
 RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conversion_launches.json")
 SCOPES = ("export_natural", "state_reblock_out", "state_records_natural", "residuals", "fwd_dstat", "chain_sums", "import_f32",
-          "gain_summary", "phase_tracks")
+          "gain_summary", "phase_tracks",
+          "stats", "fwd_chain", "fwd_fix", "fwd_cov_chain", "fwd_cov_fix", "fwd_state_chain", "fwd_state_fix", "fwd_state_seq",
+          "fwd_apn_sequential", "bwd_chain", "bwd_fix", "chain_check", "estep_lambda", "estep_kappa", "ecm_commit_kappa",
+          "transition_sums")
 MODES = [(xtol, natin) for xtol in (0, 2) for natin in ("1", "0")]
 N_LIST, M, SEED = [20000, 7000, 3001], 8, 9100
 MASK = [True, False, True]
@@ -79,6 +83,12 @@ def _step_ecm_masked(b, L):
     b.export(L.EXPORT_MULT)
 
 
+def _step_ecm_lambda_kappa(b, L):
+    # (lambda re-weighting keeps the E-steps out of the smoother chain: kernels of their own after a settle point per sweep)
+    b.step(L.RETURN_NLL, L.EXPORT_FORWARD | L.EXPORT_SMOOTH | L.EXPORT_RESID)
+    b.ecm(max_iters=2, inner_iters=2, rtol=0.0, use_kappa=True, use_lambda=True)
+
+
 def _forward_backward_kappa(b, L):
     _kappa(b)
     b.stats()
@@ -115,6 +125,7 @@ SEQUENCES = {
     "forward_export_twice": (2, _forward_export_twice),
     "step_forward_masked": (2, _step_forward_masked),
     "step_ecm_masked_multipliers": (2, _step_ecm_masked),
+    "step_ecm_lambda_kappa": (2, _step_ecm_lambda_kappa),
     "forward_backward_kappa": (2, _forward_backward_kappa),
     "chain_q_step": (2, _chain_q_step),
     "summaries_chain_by_chain": (2, _summaries_chain_by_chain),

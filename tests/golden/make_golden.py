@@ -34,7 +34,7 @@ from oracle import ref_loader  # noqa: E402
 
 
 def write_launch_record() -> int:
-    """conversion_launches.json: what every call sequence of launch_cases.py launches in the conversion scopes, per mode."""
+    """conversion_launches.json: what every call sequence of launch_cases.py launches in the scopes it counts, per mode."""
     import json
 
     import launch_cases

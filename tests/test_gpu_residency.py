@@ -281,10 +281,11 @@ def test_constant_process_noise_rows_are_written_once_and_follow_the_model(produ
 
 @pytest.mark.parametrize("xtol,natin", [(0, "1"), (0, "0"), (2, "1"), (2, "0")], ids=["exact-natin", "exact-blocked", "ulp2-natin", "ulp2-blocked"])
 def test_every_call_sequence_launches_the_recorded_conversions(product, monkeypatch, xtol, natin):
-    """Census of the conversion launches (exports, imports into the blocked layout, record conversions, residuals, NIS / NLL
-    epilogue, per-chain sums, multiplier imports, summaries) of the call sequences in tests/golden/launch_cases.py against
-    tests/golden/conversion_launches.json, recorded with the library of the commit before the flags that say which copy of an
-    array is current became one table (csr_ctx::where): every count of every sequence equal, and no pipeline replay."""
+    """Census of the pipeline's launches (exports, imports into the blocked layout, record conversions, residuals, NIS / NLL
+    epilogue, per-chain sums, multiplier imports, summaries; statistics, chains with their fix-up and check launches, state
+    chains, E-steps) of the call sequences in tests/golden/launch_cases.py against tests/golden/conversion_launches.json,
+    recorded with the library of the commit before the passes became descriptors (FwdPass / BwdPass, csr_ctx::last): every count
+    of every sequence equal, and no pipeline replay."""
     import launch_cases
 
     # (the record holds the launches of the library's default forms: under another mode switch of scripts/suite_variants.sh the
