@@ -136,6 +136,26 @@ class BwSummary(C.Structure):
                 ("sum_data", C.c_double), ("sum_squares", C.c_double)]
 
 
+class RoccoCfg(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("max_iter", C.c_int32), ("penalty", C.c_double), ("target_count", C.c_int64),
+                ("gamma", C.c_double)]
+
+
+class RoccoOut(C.Structure):
+    _fields_ = [("selection_penalty", C.c_double), ("penalized_objective", C.c_double), ("objective", C.c_double),
+                ("selected_count", C.c_int64)]
+
+
+class RoccoStats(C.Structure):
+    _fields_ = [("rounds", C.c_int64), ("launches", C.c_int64), ("lane_steps", C.c_int64), ("h2d_bytes", C.c_int64),
+                ("d2h_bytes", C.c_int64), ("depth", C.c_int32), ("reserved", C.c_int32)]
+
+
+ROCCO_FIXED_PENALTY, ROCCO_TARGET_COUNT = 0, 1
+ROCCO_SCORE_STATE, ROCCO_SCORE_LOWER_CONFIDENCE = 0, 1
+ROCCO_ERR_VALUE = 2
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
@@ -231,6 +251,15 @@ SYMBOLS = {
     "csr_comm_barrier": (C.c_int, [C.c_void_p]),
     "csr_batch_gather_tracks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, FP]),
     "csr_expected_transition_residual_sums": (C.c_int, [C.c_int32, C.c_int64, DP, DP, DP, DP, DP, DP, I64P]),
+    "csr_rocco_solve": (C.c_int, [C.c_int32, I64P, DP, DP, C.POINTER(RoccoCfg), C.POINTER(RoccoOut), C.POINTER(C.c_uint8)]),
+    "csr_batch_upload_scores": (C.c_int, [C.c_void_p, C.c_int32, DP]),
+    "csr_batch_rocco_scores": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    "csr_batch_download_scores": (C.c_int, [C.c_void_p, C.c_int32, DP]),
+    "csr_batch_rocco": (C.c_int, [C.c_void_p, C.POINTER(RoccoCfg), C.c_char_p, C.POINTER(RoccoOut)]),
+    "csr_batch_rocco_download": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8)]),
+    "csr_batch_rocco_runs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, I64P, I64P, I64P]),
+    "csr_set_rocco_depth": (C.c_int, [C.c_void_p, C.c_int32]),
+    "csr_get_rocco_stats": (C.c_int, [C.c_void_p, C.POINTER(RoccoStats)]),
 }
 
 _lib = None

@@ -67,6 +67,7 @@ class DeviceBatch:
         self.m = 0
         self.d = 2
         self._comms = []
+        self._rocco_count = {}      # selected bins per chain of the last rocco() (an upper bound of its runs)
 
     def _attach_comm(self, comm):
         self._comms.append(comm)
@@ -431,6 +432,101 @@ class DeviceBatch:
         out = (L.QseedOut * len(self.chain_lens))()
         Q._call(self._lib.csr_batch_qseed(self._ctx, C.byref(cfg), out))
         return [Q.seed_result(o, float(minQ)) for o in out]
+
+    # -- budgeted chain peak selection (ROCCO, consenrich_amd/rocco.py) ----------------------------------------------------
+    def rocco_scores(self, mode: str = "state", z: float = 1.0):
+        """Score track of every chain from the resident smoothed fit (`consenrichStateScoreTrack`, peaks.py:342-393), kept on
+        the device: "state" = float64 of xs[:,0]; "lower_confidence" = xs0 - z * sqrt(Ps00) (float32 square root), floored at
+        -2 max(xs0) when that is finite and positive.  Reads the fit, changes none of its arrays."""
+        modes = {"state": L.ROCCO_SCORE_STATE, "lower_confidence": L.ROCCO_SCORE_LOWER_CONFIDENCE}
+        if mode not in modes:
+            raise ValueError("`uncertaintyScoreMode` must be 'state' or 'lower_confidence'")
+        rc = self._lib.csr_batch_rocco_scores(self._ctx, modes[mode], float(z))
+        if rc == L.ROCCO_ERR_VALUE:        # what the reference answers with ValueError (negative variance, bad z)
+            raise ValueError(L.last_error())
+        L.check(rc)
+
+    def upload_scores(self, chain: int, scores):
+        s = np.ascontiguousarray(np.asarray(scores, dtype=np.float64).ravel())
+        if s.shape != (self.chain_lens[chain],):
+            raise ValueError("scores must have shape (chain_len,)")
+        if not np.all(np.isfinite(s)):
+            raise ValueError("`scores` contains non-finite values")
+        L.check(self._lib.csr_batch_upload_scores(self._ctx, int(chain), L.dp(s)))
+
+    def download_scores(self, chain: int) -> np.ndarray:
+        out = np.empty(self.chain_lens[chain], np.float64)
+        L.check(self._lib.csr_batch_download_scores(self._ctx, int(chain), L.dp(out)))
+        return out
+
+    def rocco(self, budget=None, gamma=0.5, selection_penalty=None, max_iter=60, chains=None):
+        """`csolveChromROCCOExact` (pyx:8877-8958) of the chains' resident scores in ONE call: all chains, and the penalties a
+        calibration can visit next, run side by side.  budget / gamma / selection_penalty / max_iter: a scalar for every chain
+        or one value per chain (None entries allowed: the reference's three modes).  chains: optional per-chain booleans;
+        chains with False are not solved and keep their previous mask.  Returns one dict per chain (None where not solved)
+        with the reference's tuple values: objective, penalized_objective, selected_count, selection_penalty; the mask stays
+        on the device (rocco_solution / rocco_runs)."""
+        from . import rocco as R
+
+        nc = len(self.chain_lens)
+
+        def per_chain(v):
+            if isinstance(v, (list, tuple, np.ndarray)):
+                if len(v) != nc:
+                    raise ValueError("one value per chain")
+                return list(v)
+            return [v] * nc
+
+        b, g, p, it = per_chain(budget), per_chain(gamma), per_chain(selection_penalty), per_chain(max_iter)
+        take = [True] * nc if chains is None else [bool(t) for t in chains]
+        if len(take) != nc:
+            raise ValueError("one mask entry per chain")
+        cfg = (L.RoccoCfg * nc)()
+        for i in range(nc):
+            if take[i]:
+                cfg[i] = R.chrom_config(self.chain_lens[i], b[i], g[i], p[i], int(it[i]))
+        out = (L.RoccoOut * nc)()
+        mask = None if chains is None else bytes(bytearray(int(t) for t in take))
+        L.check(self._lib.csr_batch_rocco(self._ctx, cfg, mask, out))
+        for i in range(nc):
+            if take[i]:
+                self._rocco_count[i] = int(out[i].selected_count)
+        return [None if not take[i] else
+                {"objective": float(out[i].objective), "penalized_objective": float(out[i].penalized_objective),
+                 "selected_count": int(out[i].selected_count), "selection_penalty": float(out[i].selection_penalty)}
+                for i in range(nc)]
+
+    def rocco_solution(self, chain: int) -> np.ndarray:
+        """The uint8 selection mask of one chain."""
+        out = np.empty(self.chain_lens[chain], np.uint8)
+        L.check(self._lib.csr_batch_rocco_download(self._ctx, int(chain), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def rocco_runs(self, chain: int, max_gap_bins: int = 0):
+        """`cBooleanRunBounds(solution, maxGapBins)` (pyx:9427-9457) of one chain's mask, computed on the device: (starts, ends)
+        int64, inclusive bin indices -- a caller fetches the peaks, not n bytes."""
+        # one call: a mask of k selected bins has at most k runs (a second call only beyond 65 536 runs)
+        cap = max(1, min(self._rocco_count.get(int(chain), 4096), 1 << 16))
+        cnt = C.c_int64(0)
+        f = self._lib.csr_batch_rocco_runs
+        for _ in range(2):
+            starts, ends = np.empty(cap, np.int64), np.empty(cap, np.int64)
+            L.check(f(self._ctx, int(chain), int(max_gap_bins), cap, C.byref(cnt), starts.ctypes.data_as(L.I64P),
+                      ends.ctypes.data_as(L.I64P)))
+            if int(cnt.value) <= cap:
+                break
+            cap = int(cnt.value)
+        k = int(cnt.value)
+        return starts[:k].copy(), ends[:k].copy()
+
+    def set_rocco_depth(self, depth: int = 0):
+        """Speculation depth D of the penalty calibration (1..8, 0 = default 6).  Changes speed only."""
+        L.check(self._lib.csr_set_rocco_depth(self._ctx, int(depth)))
+
+    def rocco_stats(self):
+        rs = L.RoccoStats()
+        L.check(self._lib.csr_get_rocco_stats(self._ctx, C.byref(rs)))
+        return {k: getattr(rs, k) for k, _ in L.RoccoStats._fields_ if k != "reserved"}
 
     def export(self, what: int):
         L.check(self._lib.csr_batch_export(self._ctx, int(what)))

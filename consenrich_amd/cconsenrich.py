@@ -29,6 +29,7 @@ def set_validation(x_tol_ulps: int) -> None:
 __all__ = [
     "cforwardPass", "cbackwardPass", "cforwardPassLevel", "cbackwardPassLevel", "cfixedBackgroundECM",
     "cfixedBackgroundECMLevel", "cExpectedTransitionResidualSums", "cExpectedTransitionResidualSumsLevel",
+    "csolvePenalizedChainROCCO", "ccalibrateSelectionPenaltyROCCO", "csolveChromROCCOExact",
 ]
 
 
@@ -613,4 +614,11 @@ from .qseed import (  # noqa: E402,F401
     cEstimatePooledProcessNoiseTransitions,
     cEstimateSameTrackProcessNoiseTransitions,
     cQSeedPosteriorFromTransitions,
+)
+
+# budgeted chain peak selection (pyx:8719-8958), implemented in consenrich_amd/rocco.py
+from .rocco import (  # noqa: E402,F401
+    ccalibrateSelectionPenaltyROCCO,
+    csolveChromROCCOExact,
+    csolvePenalizedChainROCCO,
 )

@@ -10,6 +10,7 @@
 #include "csr_qseed_post.h"
 #include "csr_objective.h"
 #include "csr_gain.h"
+#include "csr_rocco.h"
 
 #include <algorithm>
 #include <array>
@@ -314,6 +315,18 @@ struct csr_ctx {
     // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)
     bool pnFillValid = false;
     float pnFillQ[4] = {0.f, 0.f, 0.f, 0.f};
+    // ROCCO peak selection (csr_host_rocco.inl): score tracks, masks and backtrace words of the batch's chains (allocated at
+    // first use, freed with the batch) and growable work space (freed with the context)
+    struct Rocco {
+        int depth = 0;          // speculation depth of the calibration (0 = default)
+        double *scores = nullptr, *mx = nullptr;
+        unsigned char *sol = nullptr;
+        unsigned long long *bt = nullptr;
+        int *bad = nullptr;
+        std::vector<char> haveScores, haveSol;
+        DevBuf work, arena, runBuf;
+        csr_rocco_stats stats{};
+    } rocco;
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -400,6 +413,12 @@ static void free_batch(csr_ctx *c) {
     c->wsSavedF = c->wsSavedB = 0;
     c->wsActive = c->wsCold = false;
     for (auto &n : c->nat) n = nullptr;
+    c->rocco.scores = c->rocco.mx = nullptr;
+    c->rocco.sol = nullptr;
+    c->rocco.bt = nullptr;
+    c->rocco.bad = nullptr;
+    c->rocco.haveScores.clear();
+    c->rocco.haveSol.clear();
 }
 
 // Warm-up windows that gave zero re-runs on the bench workload with margin (hg38 x 32 synthetic: the state chain needs
@@ -491,7 +510,8 @@ extern "C" void csr_destroy(csr_ctx *c) {
             (void)hipEventDestroy(pr.second);
         }
     for (hipEvent_t ev : c->eventPool) (void)hipEventDestroy(ev);
-    for (DevBuf *b : {&c->bgBuf, &c->wrBuf, &c->textBuf, &c->qsBuf, &c->qpBuf, &c->stageBuf})
+    for (DevBuf *b : {&c->bgBuf, &c->wrBuf, &c->textBuf, &c->qsBuf, &c->qpBuf, &c->stageBuf, &c->rocco.work, &c->rocco.arena,
+                      &c->rocco.runBuf})
         if (b->ptr) { (void)hipFree(b->ptr); b->ptr = nullptr; b->cap = 0; }
     if (c->hMail) (void)hipHostFree(c->hMail);
     if (c->evFork) (void)hipEventDestroy(c->evFork);
@@ -645,3 +665,4 @@ extern "C" int csr_get_run_stats(csr_ctx *c, csr_run_stats *out) {
 #include "csr_host_rows.inl"
 #include "csr_host_qseed.inl"
 #include "csr_host_comm.inl"
+#include "csr_host_rocco.inl"

@@ -564,3 +564,19 @@ def run_folds_batch(batch: DeviceBatch, cfg: FitConfig, specs, *, block_len_inte
     fits, results = run_consenrich_batch(batch, cfg, block_len_intervals=block_len_intervals, model_q0=model_q0,
                                          return_background=True, return_precision_diagnostics=return_precision_diagnostics)
     return fits, results, info
+
+
+def call_peaks_batch(batch: DeviceBatch, *, budget=None, gamma=0.5, selection_penalty=None, max_iter: int = 60,
+                     score_mode: str = "state", z: float = 1.0, max_gap_bins: int = 0, chains=None) -> List[dict]:
+    """The last native stage of the reference's per-chromosome loop (`solveChromROCCO`, peaks.py:1783) for every chain of a
+    fitted batch, on the device: score track from the resident smoothed fit -> budgeted chain selection
+    (`csolveChromROCCOExact`) -> run bounds of the mask (`cBooleanRunBounds`).  Thin composition of DeviceBatch.rocco_scores /
+    rocco / rocco_runs; the rest of peaks.py (null model, gamma from the dependence span, budget estimation, fallbacks,
+    merging) stays with the caller, who passes their results as budget / gamma.  Returns one dict per chain (None for a
+    chain masked out): the values of the reference's tuple plus `starts` / `ends` (inclusive bin indices)."""
+    batch.rocco_scores(score_mode, z)
+    res = batch.rocco(budget=budget, gamma=gamma, selection_penalty=selection_penalty, max_iter=max_iter, chains=chains)
+    for ch, r in enumerate(res):
+        if r is not None:
+            r["starts"], r["ends"] = batch.rocco_runs(ch, max_gap_bins)
+    return res

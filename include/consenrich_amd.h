@@ -496,6 +496,59 @@ int csr_comm_barrier(csr_comm *comm);
  * arrays are not those of the resident fit (a pass ran since the last CSR_EXPORT_SMOOTH). */
 int csr_batch_gather_tracks(csr_ctx *ctx, csr_comm *comm, int64_t cap_bins, float *host_out);
 
+/* ---- budgeted chain peak selection (ROCCO): pyx:8603-8958 `csolvePenalizedChainROCCO`, `ccalibrateSelectionPenaltyROCCO`,
+ * `csolveChromROCCOExact`; pyx:9427-9457 `cBooleanRunBounds`; peaks.py:342-393 `consenrichStateScoreTrack` --------------------
+ * Every value returned is the reference's bit for bit: the uint8 mask, the count, both objectives and the penalty the
+ * count-driven bisection ends on.  One lane runs the reference's sequential recursion per (chain, penalty) pair; the chains of
+ * a call and the 2^D - 1 midpoints the next D bisection steps can visit run side by side (D = the speculation depth, which
+ * changes speed only).  Additive to ABI 6: new functions and structs, no change to existing ones. */
+enum { CSR_ROCCO_FIXED_PENALTY = 0, CSR_ROCCO_TARGET_COUNT = 1 };
+enum { CSR_ROCCO_SCORE_STATE = 0, CSR_ROCCO_SCORE_LOWER_CONFIDENCE = 1 };
+enum { CSR_ROCCO_ERR_VALUE = 2 };   /* return code: an argument or input the reference answers with ValueError (message: csr_last_error) */
+typedef struct csr_rocco_cfg {
+    int32_t mode;               /* CSR_ROCCO_FIXED_PENALTY: one solve at `penalty`; CSR_ROCCO_TARGET_COUNT: calibrate (pyx:8773-8844) */
+    int32_t max_iter;           /* bisection steps; max(max_iter, 1) are made */
+    double penalty;
+    int64_t target_count;       /* clamped to [0, n]; n = one solve at penalty 0 */
+    double gamma;               /* constant switch cost of the chain (ignored where a cost array is given) */
+} csr_rocco_cfg;
+typedef struct csr_rocco_out {
+    double selection_penalty, penalized_objective, objective;
+    int64_t selected_count;
+} csr_rocco_out;
+typedef struct csr_rocco_stats {    /* cumulative per context */
+    int64_t rounds;             /* host round trips of the calibration loop */
+    int64_t launches;           /* kernel launches */
+    int64_t lane_steps;         /* sum over lanes of the bins they walked */
+    int64_t h2d_bytes, d2h_bytes;
+    int32_t depth, reserved;
+} csr_rocco_stats;
+/* Chains on host arrays (default context).  scores: the chains' float64 scores one after the other (sum of chain_len values);
+ * switch_costs: their n - 1 costs one after the other, or NULL = every chain's cfg.gamma; cfg / out: one record per chain;
+ * solution: the chains' masks one after the other (may be NULL). */
+int csr_rocco_solve(int32_t n_chains, const int64_t *chain_len, const double *scores, const double *switch_costs,
+                    const csr_rocco_cfg *cfg, csr_rocco_out *out, uint8_t *solution);
+/* The same on a batch context.  Scores are a float64 track per chain in buffers of their own (freed with the batch): uploaded
+ * chain by chain, or built for every chain from the resident smoothed fit -- CSR_ROCCO_SCORE_STATE: (double) xs[:,0];
+ * CSR_ROCCO_SCORE_LOWER_CONFIDENCE: (double) xs0 - z * (double)(float) sqrt(Ps00), floored at -2 max(xs0) when that maximum is
+ * finite and positive; a negative variance or a bad z returns CSR_ROCCO_ERR_VALUE.  None of these calls changes the values of
+ * a resident array of the fit or the record of its last pass; csr_batch_rocco_scores reads the reference-layout copies of xs / Ps
+ * and, where those are not current, first makes them exactly as csr_batch_export with CSR_EXPORT_SMOOTH would (the only side effect:
+ * the arrays count as exported afterwards). */
+int csr_batch_upload_scores(csr_ctx *ctx, int32_t chain, const double *scores);
+int csr_batch_rocco_scores(csr_ctx *ctx, int32_t mode, double z);
+int csr_batch_download_scores(csr_ctx *ctx, int32_t chain, double *host_dst);
+/* cfg / out: n_chains records; chain_mask (n_chains bytes or NULL = all): chains with 0 are not solved and keep their mask. */
+int csr_batch_rocco(csr_ctx *ctx, const csr_rocco_cfg *cfg, const unsigned char *chain_mask, csr_rocco_out *out);
+int csr_batch_rocco_download(csr_ctx *ctx, int32_t chain, uint8_t *solution);
+/* `cBooleanRunBounds` of a chain's mask on the device (flag, scan, compaction): *count = number of runs; the first `capacity`
+ * of them go to starts / ends (inclusive bin indices; both may be NULL with capacity 0). */
+int csr_batch_rocco_runs(csr_ctx *ctx, int32_t chain, int32_t max_gap_bins, int64_t capacity, int64_t *count,
+                         int64_t *starts, int64_t *ends);
+/* Speculation depth D of the calibration (1..8, 0 = default 6); ctx NULL = the default context. */
+int csr_set_rocco_depth(csr_ctx *ctx, int32_t depth);
+int csr_get_rocco_stats(csr_ctx *ctx, csr_rocco_stats *out);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
