@@ -154,6 +154,7 @@ class RoccoStats(C.Structure):
 ROCCO_FIXED_PENALTY, ROCCO_TARGET_COUNT = 0, 1
 ROCCO_SCORE_STATE, ROCCO_SCORE_LOWER_CONFIDENCE = 0, 1
 ROCCO_ERR_VALUE = 2
+DWB_ERR_VALUE = 2
 
 
 class KernelTime(C.Structure):
@@ -260,6 +261,17 @@ SYMBOLS = {
     "csr_batch_rocco_runs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, I64P, I64P, I64P]),
     "csr_set_rocco_depth": (C.c_int, [C.c_void_p, C.c_int32]),
     "csr_get_rocco_stats": (C.c_int, [C.c_void_p, C.POINTER(RoccoStats)]),
+    "csr_dwb_max_lag": (C.c_int, [C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]),
+    "csr_dwb_multipliers": (C.c_int, [DP, C.c_int64, C.c_int32, C.c_char_p, DP]),
+    "csr_dwb_apply": (C.c_int, [DP, C.c_int64, DP, C.c_int64, DP]),
+    "csr_dwb_draw": (C.c_int, [DP, C.c_int64, C.c_int32, C.c_char_p, DP, C.c_int64, DP]),
+    "csr_dwb_panel_begin": (C.c_int, [C.c_void_p, C.c_int32, I64P, C.POINTER(C.c_int32), C.c_char_p, DP, DP, C.c_int64,
+                                      C.c_int32, C.c_int32]),
+    "csr_dwb_panel_order_stats": (C.c_int, [C.c_void_p, C.c_int32, I64P, DP]),
+    "csr_dwb_panel_tail_stats": (C.c_int, [C.c_void_p, C.c_int32, DP, DP, I64P, DP]),
+    "csr_dwb_panel_end": (C.c_int, [C.c_void_p]),
+    "csr_dwb_tail_stats": (C.c_int, [C.c_void_p, DP, C.c_int64, C.c_int32, DP, DP, I64P, DP]),
+    "csr_batch_dwb_observed": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, DP, DP, I64P, DP]),
 }
 
 _lib = None

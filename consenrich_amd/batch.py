@@ -528,6 +528,34 @@ class DeviceBatch:
         L.check(self._lib.csr_get_rocco_stats(self._ctx, C.byref(rs)))
         return {k: getattr(rs, k) for k, _ in L.RoccoStats._fields_ if k != "reserved"}
 
+    # -- stationary-null DWB panel behind the ROCCO budgets (consenrich_amd/dwb.py) -------------------------------------------
+    def dwb_panel(self, templates, null_centers, null_scales, *, threshold_z_grid, tail_quantiles=None, bandwidths,
+                  num_bootstrap=128, kernel="bartlett", random_seed=0, calibration_quantile=0.9, pooled_floors=None,
+                  draws_per_group=0, noise=None):
+        """`dwb.stationary_null_panel` for the batch's chains with the observed statistics taken from the RESIDENT score tracks
+        (rocco_scores / upload_scores): nothing of the fit is downloaded, and no resident array changes."""
+        from . import dwb as W
+
+        batch = self
+
+        class _Resident:
+            def length(self, c):
+                return batch.chain_lens[c]
+
+            def __call__(self, c, thresholds, scales):
+                nz = len(thresholds)
+                off, sc = np.asarray(thresholds, np.float64), np.asarray(scales, np.float64)
+                cnt, soft = np.zeros(nz, np.int64), np.zeros(nz, np.float64)
+                W._call(batch._lib.csr_batch_dwb_observed(batch._ctx, int(c), nz, L.dp(off), L.dp(sc),
+                                                          cnt.ctypes.data_as(L.I64P), L.dp(soft)))
+                return cnt, soft
+
+        return W._run_panel(self._ctx, _Resident(), list(self.chain_lens), templates, null_centers, null_scales,
+                            threshold_z_grid=threshold_z_grid, tail_quantiles=tail_quantiles, bandwidths=bandwidths,
+                            num_bootstrap=num_bootstrap, kernel=kernel, random_seed=random_seed,
+                            calibration_quantile=calibration_quantile, pooled_floors=pooled_floors,
+                            draws_per_group=draws_per_group, noise=noise)
+
     def export(self, what: int):
         L.check(self._lib.csr_batch_export(self._ctx, int(what)))
 

@@ -30,6 +30,7 @@ __all__ = [
     "cforwardPass", "cbackwardPass", "cforwardPassLevel", "cbackwardPassLevel", "cfixedBackgroundECM",
     "cfixedBackgroundECMLevel", "cExpectedTransitionResidualSums", "cExpectedTransitionResidualSumsLevel",
     "csolvePenalizedChainROCCO", "ccalibrateSelectionPenaltyROCCO", "csolveChromROCCOExact",
+    "cGenerateDWBMultipliersFromNoise", "cApplyStationaryNullDWB", "cStationaryNullDWBDraw",
 ]
 
 
@@ -621,4 +622,11 @@ from .rocco import (  # noqa: E402,F401
     ccalibrateSelectionPenaltyROCCO,
     csolveChromROCCOExact,
     csolvePenalizedChainROCCO,
+)
+
+# stationary-null dependent wild bootstrap behind the ROCCO budgets (pyx:9283-9424), implemented in consenrich_amd/dwb.py
+from .dwb import (  # noqa: E402,F401
+    cApplyStationaryNullDWB,
+    cGenerateDWBMultipliersFromNoise,
+    cStationaryNullDWBDraw,
 )

@@ -11,9 +11,11 @@
 #include "csr_objective.h"
 #include "csr_gain.h"
 #include "csr_rocco.h"
+#include "csr_dwb.h"
 
 #include <algorithm>
 #include <array>
+#include <cctype>
 #include <cfloat>
 #include <cmath>
 #include <cstdarg>
@@ -327,6 +329,15 @@ struct csr_ctx {
         DevBuf work, arena, runBuf;
         csr_rocco_stats stats{};
     } rocco;
+    // stationary-null DWB panel (csr_host_dwb.inl): chain table, weights, templates, the seed's noise stream and the rows of one
+    // group of draws; growable, freed by csr_dwb_panel_end and with the context
+    struct Dwb {
+        bool ready = false;
+        std::vector<DwbChain> chains;
+        int64_t rowLen = 0, longest = 0, strideMax = 0, maxChunks = 1;
+        int nDraws = 0, group = 0;
+        DevBuf chainBuf, wtsBuf, tmplBuf, noiseBuf, rowBuf, partBuf, outBuf, vecBuf, xBuf, meanBuf;
+    } dwb;
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -511,7 +522,8 @@ extern "C" void csr_destroy(csr_ctx *c) {
         }
     for (hipEvent_t ev : c->eventPool) (void)hipEventDestroy(ev);
     for (DevBuf *b : {&c->bgBuf, &c->wrBuf, &c->textBuf, &c->qsBuf, &c->qpBuf, &c->stageBuf, &c->rocco.work, &c->rocco.arena,
-                      &c->rocco.runBuf})
+                      &c->rocco.runBuf, &c->dwb.chainBuf, &c->dwb.wtsBuf, &c->dwb.tmplBuf, &c->dwb.noiseBuf, &c->dwb.rowBuf,
+                      &c->dwb.partBuf, &c->dwb.outBuf, &c->dwb.vecBuf, &c->dwb.xBuf, &c->dwb.meanBuf})
         if (b->ptr) { (void)hipFree(b->ptr); b->ptr = nullptr; b->cap = 0; }
     if (c->hMail) (void)hipHostFree(c->hMail);
     if (c->evFork) (void)hipEventDestroy(c->evFork);
@@ -666,3 +678,4 @@ extern "C" int csr_get_run_stats(csr_ctx *c, csr_run_stats *out) {
 #include "csr_host_qseed.inl"
 #include "csr_host_comm.inl"
 #include "csr_host_rocco.inl"
+#include "csr_host_dwb.inl"

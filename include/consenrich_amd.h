@@ -549,6 +549,40 @@ int csr_batch_rocco_runs(csr_ctx *ctx, int32_t chain, int32_t max_gap_bins, int6
 int csr_set_rocco_depth(csr_ctx *ctx, int32_t depth);
 int csr_get_rocco_stats(csr_ctx *ctx, csr_rocco_stats *out);
 
+/* ---- stationary-null dependent wild bootstrap (DWB) behind the ROCCO budgets: pyx:9283-9424 `cGenerateDWBMultipliersFromNoise`,
+ * `cApplyStationaryNullDWB`, `cStationaryNullDWBDraw`; the two bootstrap loops of peaks.py:593-762 ------------------------------
+ * Every value equals the reference's bit for bit.  An argument the reference answers with ValueError returns CSR_DWB_ERR_VALUE
+ * with the reference's message in csr_last_error; such checks run before any launch.  `kernel`: bartlett / triangle / triangular,
+ * parzen, qs / quadratic_spectral (case, surrounding blanks and '-' for '_' do not matter).  A bandwidth below 2 counts as 2;
+ * maxLag = bandwidth, or max(8 bandwidth, 32) for qs, at most 512. */
+enum { CSR_DWB_ERR_VALUE = 2 };
+int csr_dwb_max_lag(int32_t bandwidth, const char *kernel, int32_t *max_lag);
+/* The natives on host arrays (default context).  out: noise_len - 2 maxLag multipliers / n values. */
+int csr_dwb_multipliers(const double *noise, int64_t noise_len, int32_t bandwidth, const char *kernel, double *out);
+int csr_dwb_apply(const double *tmpl, int64_t n, const double *multipliers, int64_t n_multipliers, double *out);
+int csr_dwb_draw(const double *tmpl, int64_t n, int32_t bandwidth, const char *kernel, const double *noise, int64_t noise_len,
+                 double *out);
+/* A panel: n_draws draws of every chain from ONE noise stream (draw b of a chain reads noise[b * stride, (b + 1) * stride),
+ * stride = chain_len + 2 maxLag; noise_len >= n_draws * the largest stride).  ctx NULL = the default context; on a batch context
+ * the panel has buffers of its own and changes neither a resident array of the fit nor the record of its last pass.  templates:
+ * the chains' templates one after the other.  draws_per_group (0 = default: what fits 16 GiB) bounds the working set: the draws of
+ * one group are resident at a time and the second phase makes them again; results do not depend on it.
+ *   order_stats: ranks[chain][n_ranks] (0-based, -1 = unused, n_ranks <= 16) -> out[chain][draw][rank], exact order statistics;
+ *   tail_stats:  offsets / scales [chain][n_z] (n_z <= 16) -> counts[chain][draw][z] = #(draw > offset),
+ *                soft[chain][draw][z] = np.mean(np.clip((draw - offset) / max(scale, DBL_MIN), 0, None)) in NumPy's summation order.
+ * panel_end frees the panel's device memory. */
+int csr_dwb_panel_begin(csr_ctx *ctx, int32_t n_chains, const int64_t *chain_len, const int32_t *bandwidth, const char *kernel,
+                        const double *templates, const double *noise, int64_t noise_len, int32_t n_draws, int32_t draws_per_group);
+int csr_dwb_panel_order_stats(csr_ctx *ctx, int32_t n_ranks, const int64_t *ranks, double *out);
+int csr_dwb_panel_tail_stats(csr_ctx *ctx, int32_t n_z, const double *offsets, const double *scales, int64_t *counts, double *soft);
+int csr_dwb_panel_end(csr_ctx *ctx);
+/* The same tail statistics of one vector: a host array, or a chain's resident score track (csr_batch_rocco_scores /
+ * csr_batch_upload_scores), which is only read.  offsets / scales / counts / soft: n_z values. */
+int csr_dwb_tail_stats(csr_ctx *ctx, const double *x, int64_t n, int32_t n_z, const double *offsets, const double *scales,
+                       int64_t *counts, double *soft);
+int csr_batch_dwb_observed(csr_ctx *ctx, int32_t chain, int32_t n_z, const double *offsets, const double *scales, int64_t *counts,
+                           double *soft);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
