@@ -76,7 +76,6 @@ extern "C" int csr_batch_configure(csr_ctx *c, const csr_model *mdl, int64_t m, 
     free_batch(c);
     c->mdl = *mdl;
     c->m = m;
-    c->chains.clear();
     if (!c->Bfixed || c->B == 0) {
         // enough blocks to occupy the chip (>= ~16k lanes) without inflating the warm-up share more than needed
         int64_t total = 0;
@@ -170,7 +169,6 @@ extern "C" int csr_batch_configure(csr_ctx *c, const csr_model *mdl, int64_t m, 
     CHECK(dalloc(c, &p.tLam, TP)); CHECK(dalloc(c, &p.tKap, TP)); CHECK(dalloc(c, &p.tQs, TP));
     p.tKapOut = p.tKap;
     p.storePP = 1;
-    c->kapScratch[0] = c->kapScratch[1] = nullptr;
     CHECK(dalloc(c, &p.tXin, T)); CHECK(dalloc(c, &p.tPf, T)); CHECK(dalloc(c, &p.tQ, T)); CHECK(dalloc(c, &p.tQ2, T));
     CHECK(dalloc(c, &p.tXf, T)); CHECK(dalloc(c, &p.tD, T)); CHECK(dalloc(c, &p.tPP, T));
     CHECK(dalloc(c, &p.tXs, T)); CHECK(dalloc(c, &p.tPs, T)); CHECK(dalloc(c, &p.tLag, T));
@@ -192,14 +190,7 @@ extern "C" int csr_batch_configure(csr_ctx *c, const csr_model *mdl, int64_t m, 
     p.rerunCountPass = reinterpret_cast<unsigned int *>(c->dMail) + MAIL_DUMMY;
     p.chainSumD = reinterpret_cast<double *>(c->dMail + MAIL_HDR);
     p.chainSumNLL = p.chainSumD + n_chains;
-    for (unsigned int &v : c->lastCnt) v = 0;
-    for (int &v : c->nPasses) v = 1;
-    for (int &v : c->cleanRuns) v = 0;
-    for (DevBuf *b : {&c->bgBuf, &c->wrBuf, &c->textBuf})
-        if (b->ptr) { (void)hipFree(b->ptr); b->ptr = nullptr; b->cap = 0; }
-    if (c->hMail) (void)hipHostFree(c->hMail);
-    c->hMail = nullptr;
-    HIPOK(hipHostMalloc((void **)&c->hMail, c->mailBytes));
+    CHECK(c->hMail.alloc(c->mailBytes, hipHostMallocDefault));
     memset(c->hMail, 0, c->mailBytes);
     char *ci_, *coa, *cob;
     CHECK(dalloc(c, &ci_, nb * 32)); CHECK(dalloc(c, &coa, nb * 32)); CHECK(dalloc(c, &cob, nb * 32));
@@ -210,10 +201,8 @@ extern "C" int csr_batch_configure(csr_ctx *c, const csr_model *mdl, int64_t m, 
         char *b0, *b1;
         CHECK(dalloc(c, &b0, nb * 32)); CHECK(dalloc(c, &b1, nb * 32));
         c->carrySet[0][0] = ci_; c->carrySet[0][1] = coa; c->carrySet[1][0] = b0; c->carrySet[1][1] = b1;
-        c->pendChk = csr_ctx::PendingCheck{};
     }
     c->configured = true;
-    c->rs = csr_run_stats{};
     return 0;
 }
 
@@ -262,7 +251,19 @@ extern "C" int csr_batch_download_inputs(csr_ctx *c, int32_t chain, float *data,
 
 static int grid_slots(csr_ctx *c) { return (int)((c->TN + 255) / 256); }
 
-static int64_t arr_comps(csr_ctx *c, int id);
+// floats per bin of a result array
+static int64_t arr_comps(csr_ctx *c, int id) {
+    const int d = c->mdl.state_dim;
+    switch (id) {
+        case CSR_ARR_D: case CSR_ARR_LAMBDA: case CSR_ARR_KAPPA: case CSR_ARR_QSCALE: case CSR_ARR_SUMGAIN0:
+        case CSR_ARR_SUMGAIN1: case CSR_ARR_EFFQ_LEVEL: case CSR_ARR_EFFQ_TREND: case CSR_ARR_MUNCTRACE:
+        case CSR_ARR_BACKGROUND: case CSR_ARR_BACKGROUND_NEXT: return 1;
+        case CSR_ARR_XF: case CSR_ARR_XS: return d;
+        case CSR_ARR_RESID: return c->m;
+        default: return d * d;
+    }
+}
+
 // Reference-layout ("natural") device arrays of per-bin floats (import / export), allocated at first use.
 // First use zeroes the array on the context's own zeroing stream and WAITS for it on the host before the pointer is handed
 // out: the zeroing is ordered against no caller's stream, so whichever stream `c->stream` is at that moment (step_pipelined
@@ -280,20 +281,6 @@ static int nat_array(csr_ctx *c, int id, float **out) {
     *out = c->nat[id];
     return 0;
 }
-static int64_t arr_comps(csr_ctx *c, int id);
-static int64_t arr_comps_impl(csr_ctx *c, int id) {
-    const int d = c->mdl.state_dim;
-    switch (id) {
-        case CSR_ARR_D: case CSR_ARR_LAMBDA: case CSR_ARR_KAPPA: case CSR_ARR_QSCALE: case CSR_ARR_SUMGAIN0:
-        case CSR_ARR_SUMGAIN1: case CSR_ARR_EFFQ_LEVEL: case CSR_ARR_EFFQ_TREND: case CSR_ARR_MUNCTRACE:
-        case CSR_ARR_BACKGROUND: case CSR_ARR_BACKGROUND_NEXT: return 1;
-        case CSR_ARR_XF: case CSR_ARR_XS: return d;
-        case CSR_ARR_RESID: return c->m;
-        default: return d * d;
-    }
-}
-
-static int64_t arr_comps(csr_ctx *c, int id) { return arr_comps_impl(c, id); }
 
 extern "C" int csr_batch_upload_multipliers(csr_ctx *c, int32_t chain, const float *lambda, const float *kappa,
                                             const float *qscale) {

@@ -60,10 +60,9 @@ struct csr_comm {
     csr_ctx *ctx = nullptr;
     ncclComm_t comm = nullptr;
     int world = 1, rank = 0;
-    double *dScalar = nullptr;      // 2 doubles of device scratch for the scalar collectives
+    DevBuf scalar;                  // 2 doubles of device scratch for the scalar collectives
     DevBuf send, recv;              // gather buffers (grown on demand, freed with the communicator)
-    int64_t *dPackPos = nullptr;    // packed start of every chain of the batch the buffers were sized for
-    int packChains = 0;
+    DevBuf packPos;                 // packed start (int64) of every chain of the batch
 };
 
 extern "C" int csr_comm_unique_id(char *id128) {
@@ -92,8 +91,7 @@ extern "C" csr_comm *csr_comm_create(csr_ctx *c, const char *id128, int32_t worl
         delete k;
         return nullptr;
     }
-    if (hipMalloc((void **)&k->dScalar, 2 * sizeof(double)) != hipSuccess) {
-        fail("hipMalloc failed for the communicator scratch");
+    if (k->scalar.reserve(2 * sizeof(double)) != 0) {
         (void)g_rccl.CommDestroy(k->comm);
         delete k;
         return nullptr;
@@ -108,11 +106,7 @@ extern "C" void csr_comm_destroy(csr_comm *k) {
         (void)hipStreamSynchronize(k->ctx->stream);
     }
     if (k->comm) (void)g_rccl.CommDestroy(k->comm);
-    if (k->dScalar) (void)hipFree(k->dScalar);
-    if (k->dPackPos) (void)hipFree(k->dPackPos);
-    for (DevBuf *b : {&k->send, &k->recv})
-        if (b->ptr) (void)hipFree(b->ptr);
-    delete k;
+    delete k;       // (the context's device is selected: the buffers free themselves)
 }
 
 extern "C" int csr_comm_world(csr_comm *k) { return k ? k->world : 0; }
@@ -125,9 +119,10 @@ static int comm_allreduce(csr_comm *k, double *value, ncclRedOp_t op) {
     csr_ctx *c = k->ctx;
     CHECK(ctx_select(c));
     if (c->configured) CHECK(settle(c));
-    HIPOK(hipMemcpyAsync(k->dScalar, value, sizeof(double), hipMemcpyHostToDevice, c->stream));
-    NCCLOK(g_rccl.AllReduce(k->dScalar, k->dScalar + 1, 1, ncclDouble, op, k->comm, c->stream));
-    HIPOK(hipMemcpyAsync(value, k->dScalar + 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    double *ds = reinterpret_cast<double *>(k->scalar.ptr);
+    HIPOK(hipMemcpyAsync(ds, value, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    NCCLOK(g_rccl.AllReduce(ds, ds + 1, 1, ncclDouble, op, k->comm, c->stream));
+    HIPOK(hipMemcpyAsync(value, ds + 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -177,19 +172,15 @@ extern "C" int csr_batch_gather_tracks(csr_ctx *c, csr_comm *k, int64_t cap_bins
     const size_t sendBytes = sizeof(float2) * (size_t)cap_bins;
     CHECK(k->send.reserve(sendBytes));
     CHECK(k->recv.reserve(sendBytes * (size_t)k->world));
-    if (k->packChains < nc) {
-        if (k->dPackPos) (void)hipFree(k->dPackPos);
-        k->dPackPos = nullptr;
-        HIPOK(hipMalloc((void **)&k->dPackPos, sizeof(int64_t) * (size_t)nc));
-        k->packChains = nc;
-    }
-    HIPOK(hipMemcpyAsync(k->dPackPos, pos.data(), sizeof(int64_t) * (size_t)nc, hipMemcpyHostToDevice, c->stream));
+    CHECK(k->packPos.reserve(sizeof(int64_t) * (size_t)nc));
+    int64_t *dPackPos = reinterpret_cast<int64_t *>(k->packPos.ptr);
+    HIPOK(hipMemcpyAsync(dPackPos, pos.data(), sizeof(int64_t) * (size_t)nc, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemsetAsync(k->send.ptr, 0, sendBytes, c->stream));
     const int d = c->mdl.state_dim;
     {
         Scope sc(c, "gather_pack");
         hipLaunchKernelGGL(k_pack_tracks, dim3((unsigned)((c->Npad + 255) / 256)), dim3(256), 0, c->stream, c->nat[CSR_ARR_XS], d,
-                           c->nat[CSR_ARR_PS], d * d, c->dChainOff, c->dChainLen, k->dPackPos, nc, c->Npad,
+                           c->nat[CSR_ARR_PS], d * d, c->dChainOff, c->dChainLen, dPackPos, nc, c->Npad,
                            reinterpret_cast<float2 *>(k->send.ptr));
     }
     LAUNCH_CHECK("k_pack_tracks");

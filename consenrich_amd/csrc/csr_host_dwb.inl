@@ -351,8 +351,7 @@ extern "C" int csr_dwb_panel_end(csr_ctx *c) {
     csr_ctx::Dwb &d = c->dwb;
     d.ready = false;
     HIPOK(hipStreamSynchronize(c->stream));
-    for (DevBuf *b : {&d.rowBuf, &d.noiseBuf, &d.tmplBuf, &d.partBuf, &d.outBuf, &d.meanBuf})
-        if (b->ptr) { (void)hipFree(b->ptr); b->ptr = nullptr; b->cap = 0; }
+    for (DevBuf *b : {&d.rowBuf, &d.noiseBuf, &d.tmplBuf, &d.partBuf, &d.outBuf, &d.meanBuf}) b->release();
     return 0;
 }
 

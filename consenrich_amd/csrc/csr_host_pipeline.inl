@@ -4,6 +4,13 @@
 // ---------------------------------------------------------------------------------------------------------------
 // compute
 // ---------------------------------------------------------------------------------------------------------------
+// natural-layout records of the superblock state chain ({gain}, {S0u, zbar}), allocated at first use
+static int ensure_sb_nat(csr_ctx *c) {
+    if (c->sbNatGain) return 0;
+    CHECK(dalloc(c, &c->sbNatGain, c->Npad));
+    return dalloc(c, &c->sbNatSZ, c->Npad);
+}
+
 extern "C" int csr_batch_stats(csr_ctx *c) {
     CHECK(need(c));
     CHECK(settle(c));
@@ -15,7 +22,7 @@ extern "C" int csr_batch_stats(csr_ctx *c) {
     const bool natSZ = c->xTolUlps == 0 && c->mdl.state_dim == 2 && !c->seqState;
     p.natSZ = nullptr;
     if (natSZ) {
-        if (!c->sbNatGain) { CHECK(dalloc(c, &c->sbNatGain, c->Npad)); CHECK(dalloc(c, &c->sbNatSZ, c->Npad)); }
+        CHECK(ensure_sb_nat(c));
         p.natSZ = reinterpret_cast<double2 *>(c->sbNatSZ);
     }
     {
@@ -114,7 +121,7 @@ static int read_mail(csr_ctx *c, size_t bytes) {
     return 0;
 }
 static unsigned int take_fresh(csr_ctx *c, int stage) {
-    const unsigned int now = reinterpret_cast<const unsigned int *>(c->hMail)[stage];
+    const unsigned int now = reinterpret_cast<const unsigned int *>(c->hMail.ptr)[stage];
     const unsigned int fresh = now - c->lastCnt[stage];
     c->lastCnt[stage] = now;
     return fresh;
@@ -479,7 +486,7 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
     CHECK(ensure_sb_view(c));
     if (!resume) CHECK(flush_pending_check(c));
     csr_ctx::SbView &v = c->sb;
-    if (!c->sbNatGain) { CHECK(dalloc(c, &c->sbNatGain, c->Npad)); CHECK(dalloc(c, &c->sbNatSZ, c->Npad)); }
+    CHECK(ensure_sb_nat(c));
     float *natXf;
     CHECK(nat_array(c, CSR_ARR_XF, &natXf));
     c->sbp.active = false;
@@ -543,7 +550,7 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
             if (!c->hDone) {
                 // (coherent = fine-grained: a system-scope store of the running kernel is visible to the polling host at once,
                 // whatever HIP_HOST_COHERENT says)
-                HIPOK(hipHostMalloc((void **)&c->hDone, sizeof(unsigned int) * c->chains.size(), hipHostMallocCoherent | hipHostMallocMapped));
+                CHECK(c->hDone.alloc(c->chains.size(), hipHostMallocCoherent | hipHostMallocMapped));
                 HIPOK(hipHostGetDevicePointer((void **)&c->dDone, c->hDone, 0));
             }
             for (size_t i = 0; i < c->chains.size(); ++i) c->hDone[i] = 0u;
@@ -844,7 +851,7 @@ static int forward_impl(csr_ctx *c, const FwdPass &pass) {
                 // the superblock state chain reads its records in the reference layout: the covariance chain writes the gain
                 // records there itself (and Pf, when this pass's Pf is an output), through LDS tiles -- no conversion launch
                 // between the two chains; the NIS epilogue reads P00pred from the compact track instead of the blocked record
-                if (!c->sbNatGain) { CHECK(dalloc(c, &c->sbNatGain, c->Npad)); CHECK(dalloc(c, &c->sbNatSZ, c->Npad)); }
+                CHECK(ensure_sb_nat(c));
                 p.predCompact = 1;
                 pc = p;
                 pc.natOut = 1;
@@ -1536,12 +1543,7 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     int64_t total = 0;
     for (const ChainInfo &ci : c->chains) total += ci.n;
     if (!c->dMask[0]) for (auto &m : c->dMask) CHECK(dalloc(c, &m, nc));
-    if (c->hMaskPinChains < (size_t)nc) {
-        if (c->hMaskPin) HIPOK(hipHostFree(c->hMaskPin));
-        c->hMaskPin = nullptr;
-        HIPOK(hipHostMalloc((void **)&c->hMaskPin, 8 * (size_t)nc, hipHostMallocDefault));
-        c->hMaskPinChains = (size_t)nc;
-    }
+    if (!c->hMaskPin) CHECK(c->hMaskPin.alloc(8 * (size_t)nc, hipHostMallocDefault));
     std::vector<unsigned char> tailed((size_t)nc, 0);
     int phase = 0;
     bool any = false;

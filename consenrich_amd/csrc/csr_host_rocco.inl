@@ -19,7 +19,7 @@ struct RoccoDev {
     unsigned long long *bt;         // one 64-bit word per 32 bins of the concatenated layout
 };
 
-static int rocco_depth(const csr_ctx *c) { return c->rocco.depth > 0 ? c->rocco.depth : 6; }
+static int rocco_depth(const csr_ctx *c) { return c->roccoWs.depth > 0 ? c->roccoWs.depth : 6; }
 
 static int rocco_run(csr_ctx *c, const RoccoDev &dv, std::vector<RoccoChainIn> &chains) {
     const int nc = (int)chains.size();
@@ -42,8 +42,8 @@ static int rocco_run(csr_ctx *c, const RoccoDev &dv, std::vector<RoccoChainIn> &
     const size_t nJobs = (size_t)nc * jobsPer, nPen = (size_t)nc * maxPen + 2 * (size_t)nc;
     const size_t oJob = 0, oPen = (nJobs * sizeof(RoccoJob) + 255) / 256 * 256, oRes = oPen + (nPen * 8 + 255) / 256 * 256,
                  oMm = oRes + (nPen * sizeof(RoccoRes) + 255) / 256 * 256, total = oMm + 16 * (size_t)nc;
-    CHECK(c->rocco.work.reserve(total));
-    char *base = (char *)c->rocco.work.ptr;
+    CHECK(c->roccoWs.work.reserve(total));
+    char *base = (char *)c->roccoWs.work.ptr;
     RoccoJob *dJobs = (RoccoJob *)(base + oJob);
     double *dPen = (double *)(base + oPen);
     RoccoRes *dRes = (RoccoRes *)(base + oRes);
@@ -51,7 +51,7 @@ static int rocco_run(csr_ctx *c, const RoccoDev &dv, std::vector<RoccoChainIn> &
     std::vector<RoccoJob> jobs;
     std::vector<double> pen(nPen);
     std::vector<RoccoRes> res(nPen);
-    csr_rocco_stats &rs = c->rocco.stats;
+    csr_rocco_stats &rs = c->roccoWs.stats;
     rs.depth = D;
 
     // which chains calibrate: clamp the target; target == n is one solve at penalty 0 (pyx:8773-8785)
@@ -249,13 +249,13 @@ extern "C" int csr_set_rocco_depth(csr_ctx *c, int32_t depth) {
     if (!c) c = default_ctx();      // NULL addresses the default context of the host-buffer entry points
     if (!c) return -1;
     if (depth < 0 || depth > ROCCO_MAX_DEPTH) return fail("ROCCO speculation depth must be in 0..%d", ROCCO_MAX_DEPTH);
-    c->rocco.depth = depth;
+    c->roccoWs.depth = depth;
     return 0;
 }
 extern "C" int csr_get_rocco_stats(csr_ctx *c, csr_rocco_stats *out) {
     if (!c) c = default_ctx();
     if (!c || !out) return fail("null argument");
-    *out = c->rocco.stats;
+    *out = c->roccoWs.stats;
     out->depth = rocco_depth(c);
     return 0;
 }
@@ -285,8 +285,8 @@ extern "C" int csr_rocco_solve(int32_t n_chains, const int64_t *chain_len, const
     // device arena: scores | costs | mask | backtrace words
     const size_t oS = 0, oC = oS + 8 * (size_t)pad, oSol = oC + (switch_costs ? 8 * (size_t)pad : 0), oBt = oSol + (size_t)pad,
                  total = oBt + (size_t)pad / 4 + 64;
-    CHECK(c->rocco.arena.reserve(total));
-    char *base = (char *)c->rocco.arena.ptr;
+    CHECK(c->roccoWs.arena.reserve(total));
+    char *base = (char *)c->roccoWs.arena.ptr;
     RoccoDev dv{(const double *)(base + oS), switch_costs ? (const double *)(base + oC) : nullptr, (unsigned char *)(base + oSol),
                 (unsigned long long *)(base + oBt)};
     int64_t so = 0, co = 0;
@@ -303,7 +303,7 @@ extern "C" int csr_rocco_solve(int32_t n_chains, const int64_t *chain_len, const
         }
         so += ch.n;
     }
-    c->rocco.stats.h2d_bytes += 8 * tot + (switch_costs ? 8 * (tot - n_chains) : 0);
+    c->roccoWs.stats.h2d_bytes += 8 * tot + (switch_costs ? 8 * (tot - n_chains) : 0);
     CHECK(rocco_run(c, dv, chains));
     if (solution) {
         so = 0;
@@ -312,7 +312,7 @@ extern "C" int csr_rocco_solve(int32_t n_chains, const int64_t *chain_len, const
             so += chains[i].n;
         }
         HIPOK(hipStreamSynchronize(c->stream));
-        c->rocco.stats.d2h_bytes += tot;
+        c->roccoWs.stats.d2h_bytes += tot;
     }
     return 0;
 }
@@ -441,7 +441,7 @@ extern "C" int csr_batch_rocco_download(csr_ctx *c, int32_t chain, uint8_t *solu
     const ChainInfo &ci = c->chains[chain];
     HIPOK(hipMemcpyAsync(solution, c->rocco.sol + ci.off, (size_t)ci.n, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
-    c->rocco.stats.d2h_bytes += ci.n;
+    c->roccoWs.stats.d2h_bytes += ci.n;
     return 0;
 }
 
@@ -458,8 +458,8 @@ extern "C" int csr_batch_rocco_runs(csr_ctx *c, int32_t chain, int32_t max_gap_b
     const int64_t nb = (ci.n + 1023) / 1024;
     const size_t oB = 0, oS = (8 * (size_t)(nb + 1) + 255) / 256 * 256, oE = oS + (8 * (size_t)capacity + 255) / 256 * 256,
                  total = oE + 8 * (size_t)capacity + 256;
-    CHECK(c->rocco.runBuf.reserve(total));
-    char *base = (char *)c->rocco.runBuf.ptr;
+    CHECK(c->roccoWs.runBuf.reserve(total));
+    char *base = (char *)c->roccoWs.runBuf.ptr;
     RoccoRunArgs a;
     a.sol = c->rocco.sol + ci.off;
     a.n = ci.n;

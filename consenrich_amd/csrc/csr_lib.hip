@@ -94,21 +94,59 @@ struct ProfEntry {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
-// growable device work space owned by a context (freed with it)
+// Growable device work space.  Owns its memory: whoever holds one as a member frees it by being destroyed or assigned to (the device
+// must be selected at that moment, see csr_destroy)
 struct DevBuf {
     void *ptr = nullptr;
     size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : ptr(o.ptr), cap(o.cap) { o.ptr = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { release(); ptr = o.ptr; cap = o.cap; o.ptr = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release() {
         if (ptr) (void)hipFree(ptr);
         ptr = nullptr;
         cap = 0;
+    }
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return 0;
+        release();
         const size_t want = bytes + bytes / 8 + 256;
         hipError_t e = hipMalloc(&ptr, want);
         if (e != hipSuccess) return fail("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
         cap = want;
         return 0;
     }
+};
+// Pinned host memory of `count` elements (hipHostMalloc with the caller's flags), owned the same way; reads like the pointer it holds
+template <class T>
+struct PinBuf {
+    T *ptr = nullptr;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    PinBuf(PinBuf &&o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
+    PinBuf &operator=(PinBuf &&o) noexcept {
+        if (this != &o) { release(); ptr = o.ptr; o.ptr = nullptr; }
+        return *this;
+    }
+    ~PinBuf() { release(); }
+    void release() {
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr;
+    }
+    int alloc(size_t count, unsigned flags) {
+        release();
+        hipError_t e = hipHostMalloc((void **)&ptr, sizeof(T) * count, flags);
+        if (e != hipSuccess) { ptr = nullptr; return fail("hipHostMalloc(%zu bytes) failed: %s", sizeof(T) * count, hipGetErrorString(e)); }
+        return 0;
+    }
+    operator T *() const { return ptr; }
 };
 
 // One forward pass / one smoother pass as its caller describes it (forward_impl, backward_impl).  Everything a pass depends on
@@ -134,41 +172,11 @@ struct BwdPass {
     float *kappaIn = nullptr, *kappaOut = nullptr;      // ECM sweep with the E-step inside the smoother (nullptr: the resident kappa)
 };
 
-struct csr_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    // tuning
-    int B = 0;                 // block length; 0 = chosen from the batch size at configure time
-    // speculative warm-up in bins (multiples of 16).  Defaults follow the validation mode (mode_warm_defaults): bitwise
-    // coalescence of float32-rounded trajectories needs ~4x the window that k-ulp agreement does.
-    int warmP = 256, warmX = 256, warmB = 128;
-    bool pinP = false, pinX = false, pinB = false, pinFM = false;
-    int warmFM = 96;            // fused forward chain with per-bin multipliers (see forward_impl)
-    int *fwdWindow = nullptr;   // window variable of the forward stage being launched (see stage_warm)
-    int *bwdWindow = nullptr;   // ... of the smoother stage (warm-started ECM sweeps)
-    int *lastBwdWindow = nullptr;
-    // Warm-started speculation inside the ECM loop (Prm::ckptIn): a sweep's chains start their windows from the carries the
-    // previous sweep recorded (double-buffered per direction), with windows of wsWarmF / wsWarmB bins instead of the cold
-    // ones.  A failed validation at a wavefront's edge widens them; a window that changed since the checkpoints were
-    // recorded makes the next sweep start cold once.
-    bool wsEnabled = true;      // CONSENRICH_AMD_WARMSTART=0: off
-    bool wsActive = false;      // set by the ECM loop around its sweeps
-    bool wsCold = false;        // replay of a failed iteration: record checkpoints, do not start from them
-    int wsWarmF = 32, wsWarmB = 32;         // warm-started windows (widen themselves when an edge block fails)
-    static constexpr int wsMaxBlock = 32;   // largest block length (= batch size class) that warm-starts
-    int wsSavedF = 0, wsSavedB = 0;         // window length the resident checkpoints were recorded for (0: none)
-    int wsSweepF = 0, wsSweepB = 0;         // parity of the double buffers
-    void *ckF[2] = {nullptr, nullptr}, *ckB[2] = {nullptr, nullptr};
-    int *lastFwdWindow = nullptr;   // ... of the last forward stage launched (a failed settle widens that one)
-    bool Bfixed = false;
-    bool adaptWarm = true;
-    bool useDmaWarm = true;    // ... and, with reference-layout outputs, for its warm-up phase
-    bool useDmaFused = true;   // fused forward chain without reference-layout outputs: LDS-DMA ring
-    bool useDma = true;        // LDS-DMA speculative kernels for the chains that provide them
-    int xTolUlps = 0;           // carry validation: 0 = bit-exact sequential semantics (DEFAULT of every context since round 3: the
-                                // only mode that holds the parity gate through the ECM loop on ill-conditioned data, tests/test_hard_data.py);
-                                // k > 0 = k-ulp acceptance, the opt-in throughput mode (csr_set_validation / CONSENRICH_AMD_XTOL_ULPS)
-    // batch
+// Everything that dies with the configured batch (DESIGN.md "Lifetimes"): the chain table, the kernel parameters, every pointer into
+// memory that dalloc registers in `allocs` or into pinned memory sized by the batch, and every statement about the resident results.
+// free_batch() frees `allocs` and assigns a default-constructed BatchState: a member declared here with its default needs no line
+// anywhere else.
+struct BatchState {
     bool configured = false;
     csr_model mdl{};
     int64_t m = 0;
@@ -193,13 +201,7 @@ struct csr_ctx {
         bool fwdPending = false, bwdPending = false;
         uint32_t exports = 0;
     } last;
-    bool dstatLdsRaised = false;
-    bool natInEnabled = true;           // CONSENRICH_AMD_NATIN=0 (tests): the smoother never reads the reference layout -- blocked copies
-                                        // a forward pass did not write are brought back first (need_blocked)
     bool sideSumsDone = false;          // the pending side-stream work already includes the per-chain sums (join_side only waits)
-    double lastSbLoopUs = 0.0;          // how long the host watched the previous single launch of the state chain (step_pipelined)
-    double lastWaitUs[2] = {0.0, 0.0};  // how long the previous host wait for the stream lasted, per wait site (wait_stream polls around that moment)
-    bool sbAsyncLdsRaised[3] = {false, false, false};   // per context = per device (HIP keeps the attribute per device)
     bool fwdInternal = false;   // forward results were produced by this library (vs imported through csr_backward_pass)
     Prm p{};
     std::vector<void *> allocs;
@@ -212,7 +214,8 @@ struct csr_ctx {
     // mailbox: [20 x u32 monotonic re-run counters: 0-3 cumulative per stage (covariance, state, smoother, debug), 4-15 per
     // stage and validation-pass index, 16 scratch | sumD[nchains] | sumNLL[nchains]] in device memory, mirrored into pinned
     // host memory with ONE copy per settle point
-    char *dMail = nullptr, *hMail = nullptr;
+    char *dMail = nullptr;
+    PinBuf<char> hMail;
     size_t mailBytes = 0;
     unsigned int lastCnt[20] = {0};
     // deferred validation launches nPasses[stage] validation passes back to back; the stage stands iff the LAST of them
@@ -220,7 +223,119 @@ struct csr_ctx {
     // longer memory than the window (small Q0) -- are repaired by pass 1 and confirmed by pass 2 without a pipeline replay.
     int nPasses[3] = {1, 1, 1};
     int cleanRuns[3] = {0, 0, 0};
-    int launchedPasses[3] = {1, 1, 1};
+    // Warm-started speculation inside the ECM loop (csr_ctx::wsEnabled): what the resident checkpoints are
+    bool wsActive = false;      // set by the ECM loop around its sweeps
+    bool wsCold = false;        // replay of a failed iteration: record checkpoints, do not start from them
+    int wsSavedF = 0, wsSavedB = 0;         // window length the resident checkpoints were recorded for (0: none)
+    int wsSweepF = 0, wsSweepB = 0;         // parity of the double buffers
+    void *ckF[2] = {nullptr, nullptr}, *ckB[2] = {nullptr, nullptr};
+    bool natSZValid = false;    // sbNatSZ holds the current statistics of every chain
+    bool gainNat = false;       // this forward pass's covariance chain wrote sbNatGain itself (walk_nat_gain)
+    float4 *sbNatGain = nullptr, *sbNatSZ = nullptr;    // natural-layout records of the systolic walker (ensure_sb_nat)
+    struct SbView {
+        bool ready = false;
+        int B = 0;
+        int64_t NB = 0, NG = 0, TN = 0;
+        int4 *blk = nullptr;
+        int *blkChain = nullptr;
+        int64_t *chainFirst = nullptr;
+        void *carryIn = nullptr, *carryOutA = nullptr, *carryOutB = nullptr;
+        unsigned long long *pub = nullptr;      // k_sb_async: carry[NB], {version, final}[NB], control words
+    } sb;
+    bool sidePending = false;
+    double *dChainQ = nullptr;  // per-chain base process noise (csr_batch_set_chain_q)
+    // ECM with the kappa E-step inside the smoother: a sweep's smoother writes kappa into a scratch buffer (BwdPass::kappaOut),
+    // the next sweep's forward pass reads it (FwdPass::kappaIn); the resident tKap only changes when a whole iteration has been
+    // validated.  Allocated on first use.
+    float *kapScratch[2] = {nullptr, nullptr};
+    bool fwdQCompact = false;   // the resident forward pass stored the diagonal of pNoise (tQ2) instead of pNoise (tQ)
+    bool qDiagonal = true;      // the base process noise in use (model's, or every chain's) is diagonal
+    bool modelQDiagonal = true, chainQDiagonal = true;
+    Prm sidePrm{};              // parameters of the epilogue running on the side stream (its sums follow at the join)
+    // device-resident background update (allocated on first use)
+    struct BgState {
+        bool ready = false, haveCur = false;
+        int Bp = 0;
+        BgPrm prm{};
+        BgBatch bat{};
+        int *dGroupChain = nullptr;
+        double *out1 = nullptr;
+        unsigned char *dActive = nullptr, *dHasSup = nullptr;
+        double *dPen = nullptr;
+        long long *dSelRank = nullptr;
+    } bg;
+    DevBuf bgBuf, wrBuf, textBuf;       // host-buffer background solver / bedGraph writer work space (this device)
+    // Folded validation (Prm::prevKind): a clean optimistic stage leaves its check to the next speculative kernel; the two use
+    // different carry sets.  pendChk = the check that has not been handed to a kernel yet (flushed by read_mail).
+    struct PendingCheck {
+        bool valid = false;
+        int kind = 0, stage = 0;
+        const void *cin = nullptr, *cout = nullptr;
+        const unsigned char *active = nullptr;
+    } pendChk;
+    void *carrySet[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [set][carryIn, carryOutA]
+    int carryToggle = 0;
+    struct SbPending { bool active = false; Prm p{}; } sbp;     // a state chain launched and not yet waited for (step_pipelined)
+    PinBuf<unsigned int> hDone;         // host-visible "chain is final" words (coherent, mapped) ...
+    unsigned int *dDone = nullptr;      // ... and their device alias
+    unsigned char *dMask[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PinBuf<unsigned char> hMaskPin;     // pinned staging of the eight masks (an upload from pageable memory may hold the host)
+    bool pfPending = false;
+    // the reference-layout process-noise array holds the constant fill of THESE values in every row (k_fill_rows): a step with the
+    // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)
+    bool pnFillValid = false;
+    float pnFillQ[4] = {0.f, 0.f, 0.f, 0.f};
+    // ROCCO peak selection (csr_host_rocco.inl): score tracks, masks and backtrace words of the batch's chains (allocated at first
+    // use); its work space is csr_ctx::roccoWs
+    struct Rocco {
+        double *scores = nullptr, *mx = nullptr;
+        unsigned char *sol = nullptr;
+        unsigned long long *bt = nullptr;
+        int *bad = nullptr;
+        std::vector<char> haveScores, haveSol;
+    } rocco;
+    // stats
+    csr_run_stats rs{};
+};
+
+// What lives as long as the context: the device, streams and events, tuning (given, or adapted from what earlier passes saw: it
+// survives a reconfigure), profiling, and work space kept across batches (DevBuf members: they free themselves).
+struct csr_ctx : BatchState {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    // tuning
+    int B = 0;                 // block length; 0 = chosen from the batch size at configure time
+    // speculative warm-up in bins (multiples of 16).  Defaults follow the validation mode (mode_warm_defaults): bitwise
+    // coalescence of float32-rounded trajectories needs ~4x the window that k-ulp agreement does.
+    int warmP = 256, warmX = 256, warmB = 128;
+    bool pinP = false, pinX = false, pinB = false, pinFM = false;
+    int warmFM = 96;            // fused forward chain with per-bin multipliers (see forward_impl)
+    int *fwdWindow = nullptr;   // window variable of the forward stage being launched (see stage_warm)
+    int *bwdWindow = nullptr;   // ... of the smoother stage (warm-started ECM sweeps)
+    int *lastBwdWindow = nullptr;
+    // Warm-started speculation inside the ECM loop (Prm::ckptIn): a sweep's chains start their windows from the carries the
+    // previous sweep recorded (double-buffered per direction, BatchState::ckF / ckB), with windows of wsWarmF / wsWarmB bins
+    // instead of the cold ones.  A failed validation at a wavefront's edge widens them; a window that changed since the
+    // checkpoints were recorded makes the next sweep start cold once.
+    bool wsEnabled = true;      // CONSENRICH_AMD_WARMSTART=0: off
+    int wsWarmF = 32, wsWarmB = 32;         // warm-started windows (widen themselves when an edge block fails)
+    static constexpr int wsMaxBlock = 32;   // largest block length (= batch size class) that warm-starts
+    int *lastFwdWindow = nullptr;   // ... of the last forward stage launched (a failed settle widens that one)
+    bool Bfixed = false;
+    bool adaptWarm = true;
+    bool useDmaWarm = true;    // ... and, with reference-layout outputs, for its warm-up phase
+    bool useDmaFused = true;   // fused forward chain without reference-layout outputs: LDS-DMA ring
+    bool useDma = true;        // LDS-DMA speculative kernels for the chains that provide them
+    int xTolUlps = 0;           // carry validation: 0 = bit-exact sequential semantics (DEFAULT of every context since round 3: the
+                                // only mode that holds the parity gate through the ECM loop on ill-conditioned data, tests/test_hard_data.py);
+                                // k > 0 = k-ulp acceptance, the opt-in throughput mode (csr_set_validation / CONSENRICH_AMD_XTOL_ULPS)
+    bool dstatLdsRaised = false;
+    bool natInEnabled = true;           // CONSENRICH_AMD_NATIN=0 (tests): the smoother never reads the reference layout -- blocked copies
+                                        // a forward pass did not write are brought back first (need_blocked)
+    double lastSbLoopUs = 0.0;          // how long the host watched the previous single launch of the state chain (step_pipelined)
+    double lastWaitUs[2] = {0.0, 0.0};  // how long the previous host wait for the stream lasted, per wait site (wait_stream polls around that moment)
+    bool sbAsyncLdsRaised[3] = {false, false, false};   // per context = per device (HIP keeps the attribute per device)
+    int launchedPasses[3] = {1, 1, 1};  // validation passes the last launch of a stage made (BatchState::nPasses)
     // deferred validation: a stage whose last synchronous run needed no re-run is launched optimistically (speculative
     // pass + one validation pass, no host round trip); the counters are checked at the next settle point and the
     // pipeline is re-run synchronously from the first stage that did re-run blocks.
@@ -229,7 +344,7 @@ struct csr_ctx {
     // bit-exact validation, levelTrend (default): the state chain speculates on SUPERBLOCKS of sbBins bins with an sbWarm-bin
     // window -- two float32-rounded state trajectories need ~10^4 bins to coincide bit for bit (scripts/ubench/merge_time.c),
     // so the batch's own 32..256-bin blocks never validate; the gain / statistics records are re-blocked into a second view
-    // of the batch (own block table and carries) for this one chain and the filtered state is re-blocked back
+    // of the batch (own block table and carries, BatchState::sb) for this one chain and the filtered state is re-blocked back
     // (CONSENRICH_AMD_SEQ_STATE=1 is the sequential yardstick)
     int sbBins = 8192;          // CONSENRICH_AMD_SB_BINS (default: chosen from the batch, ensure_sb_view)
     // k_sb_delta's fallback rule (CONSENRICH_AMD_SB_ADV = "min,from"): walk the rest of a batch when, from round `from` on, the
@@ -242,58 +357,12 @@ struct csr_ctx {
     // barrier-free single launch (k_sb_async); sbSpinLimit bounds every wait inside it (polls of ~2 us; then: bail out to the pass form)
     bool sbAsync = true;
     int sbSpinLimit = 1 << 19;
-    bool natSZValid = false;    // sbNatSZ holds the current statistics of every chain
-    bool gainNat = false;       // this forward pass's covariance chain wrote sbNatGain itself (walk_nat_gain)
-    float4 *sbNatGain = nullptr, *sbNatSZ = nullptr;    // natural-layout records of the systolic walker (freed with the batch)
-    struct SbView {
-        bool ready = false;
-        int B = 0;
-        int64_t NB = 0, NG = 0, TN = 0;
-        int4 *blk = nullptr;
-        int *blkChain = nullptr;
-        int64_t *chainFirst = nullptr;
-        void *carryIn = nullptr, *carryOutA = nullptr, *carryOutB = nullptr;
-        unsigned long long *pub = nullptr;      // k_sb_async: carry[NB], {version, final}[NB], control words
-    } sb;
     // debugging switches, read once from the environment at creation (never on the launch path)
     bool dbgLog = false;
     bool optimistic[3] = {true, true, true};
-    bool sidePending = false;
-    double *dChainQ = nullptr;  // per-chain base process noise (csr_batch_set_chain_q), freed with the batch
-    // ECM with the kappa E-step inside the smoother: a sweep's smoother writes kappa into a scratch buffer (BwdPass::kappaOut),
-    // the next sweep's forward pass reads it (FwdPass::kappaIn); the resident tKap only changes when a whole iteration has been
-    // validated.  Allocated on first use, freed with the batch.
-    float *kapScratch[2] = {nullptr, nullptr};
-    bool fwdQCompact = false;   // the resident forward pass stored the diagonal of pNoise (tQ2) instead of pNoise (tQ)
-    bool qDiagonal = true;      // the base process noise in use (model's, or every chain's) is diagonal
-    bool modelQDiagonal = true, chainQDiagonal = true;
-    Prm sidePrm{};              // parameters of the epilogue running on the side stream (its sums follow at the join)
-    // device-resident background update (allocated on first use, freed with the batch)
-    struct BgState {
-        bool ready = false, haveCur = false;
-        int Bp = 0;
-        BgPrm prm{};
-        BgBatch bat{};
-        int *dGroupChain = nullptr;
-        double *out1 = nullptr;
-        unsigned char *dActive = nullptr, *dHasSup = nullptr;
-        double *dPen = nullptr;
-        long long *dSelRank = nullptr;
-    } bg;
     DevBuf qsBuf, qpBuf;                // Q0-seed work space (sampling / posterior)
     DevBuf stageBuf;                    // host -> device staging of per-bin vectors (csr_batch_upload_multipliers)
-    DevBuf bgBuf, wrBuf, textBuf;       // host-buffer background solver / bedGraph writer work space (this device)
     hipStream_t side = nullptr;         // NIS/NLL epilogue runs here, concurrently with the smoother chain
-    // Folded validation (Prm::prevKind): a clean optimistic stage leaves its check to the next speculative kernel; the two use
-    // different carry sets.  pendChk = the check that has not been handed to a kernel yet (flushed by read_mail).
-    struct PendingCheck {
-        bool valid = false;
-        int kind = 0, stage = 0;
-        const void *cin = nullptr, *cout = nullptr;
-        const unsigned char *active = nullptr;
-    } pendChk;
-    void *carrySet[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [set][carryIn, carryOutA]
-    int carryToggle = 0;
     hipEvent_t evFork = nullptr, evJoin = nullptr;
     hipEvent_t evFork2 = nullptr, evPf = nullptr;      // early covariance exports on the side stream (bit-exact mode)
     // step_pipelined: tails of the chains whose filtered state stands, on a stream of their own while the state chain runs
@@ -303,34 +372,18 @@ struct csr_ctx {
     // handed out: it is ordered against no other stream, so it does not matter which stream the caller is on at that moment
     hipStream_t zeroStream = nullptr;
     hipStream_t mainStream = nullptr;   // what `stream` is outside step_pipelined's tail groups (csr_run_stats.nat_first_use_off_main)
-    struct SbPending { bool active = false; Prm p{}; } sbp;     // a state chain launched and not yet waited for (step_pipelined)
-    unsigned int *hDone = nullptr, *dDone = nullptr;    // host-visible "chain is final" words (pinned; device alias)
-    unsigned char *dMask[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned char *hMaskPin = nullptr;          // pinned staging of the eight masks (an upload from pageable memory may hold the host)
-    size_t hMaskPinChains = 0;
     // CONSENRICH_AMD_TAIL_PCT="first,next": share of the batch's bins a group of finished chains must reach.  Round 4: 60 / 40 (round 3:
     // 50 / 15) -- tail kernels take issue slots from the walking wavefronts, so fewer, later groups win (profiles/r04_tail_sweep.txt)
     int tailFirstPct = 60, tailNextPct = 40;
     bool tailSplit = true;      // CONSENRICH_AMD_TAIL_SPLIT=0: a step's tail follows the state chain for all chains at once
-    bool pfPending = false;
-    // the reference-layout process-noise array holds the constant fill of THESE values in every row (k_fill_rows): a step with the
-    // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)
-    bool pnFillValid = false;
-    float pnFillQ[4] = {0.f, 0.f, 0.f, 0.f};
-    // ROCCO peak selection (csr_host_rocco.inl): score tracks, masks and backtrace words of the batch's chains (allocated at
-    // first use, freed with the batch) and growable work space (freed with the context)
-    struct Rocco {
+    // ROCCO (csr_host_rocco.inl): tuning, counters and growable work space; the batch's tracks are BatchState::rocco
+    struct RoccoWs {
         int depth = 0;          // speculation depth of the calibration (0 = default)
-        double *scores = nullptr, *mx = nullptr;
-        unsigned char *sol = nullptr;
-        unsigned long long *bt = nullptr;
-        int *bad = nullptr;
-        std::vector<char> haveScores, haveSol;
         DevBuf work, arena, runBuf;
         csr_rocco_stats stats{};
-    } rocco;
+    } roccoWs;
     // stationary-null DWB panel (csr_host_dwb.inl): chain table, weights, templates, the seed's noise stream and the rows of one
-    // group of draws; growable, freed by csr_dwb_panel_end and with the context
+    // group of draws; growable, the large ones given back by csr_dwb_panel_end
     struct Dwb {
         bool ready = false;
         std::vector<DwbChain> chains;
@@ -342,8 +395,6 @@ struct csr_ctx {
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
     std::vector<hipEvent_t> eventPool;
-    // stats
-    csr_run_stats rs{};
 };
 
 static int settle(csr_ctx *c);
@@ -395,41 +446,12 @@ static int dalloc(csr_ctx *c, T **ptr, int64_t count) {
     return 0;
 }
 
+// Ends the configured batch: its device memory is freed and every BatchState member is back at its default (DevBuf / PinBuf members
+// free what they own when they are assigned to).  The device must be selected.
 static void free_batch(csr_ctx *c) {
-    for (void *q : c->allocs) (void)hipFree(q);
-    c->allocs.clear();
-    c->configured = false;
-    c->statsValid = c->haveFwd = c->haveBwd = false;
-    drop_pending(c);
-    c->sidePending = false;
-    c->dMail = nullptr;
-    c->dChainQ = nullptr;
-    c->pendChk = csr_ctx::PendingCheck{};
-    c->carrySet[0][0] = c->carrySet[0][1] = c->carrySet[1][0] = c->carrySet[1][1] = nullptr;
-    c->kapScratch[0] = c->kapScratch[1] = nullptr;
-    c->bg = csr_ctx::BgState{};
-    c->dActive = nullptr;
-    c->sb = csr_ctx::SbView{};
-    c->sbNatGain = c->sbNatSZ = nullptr;
-    c->natSZValid = false;
     if (c->tail) (void)hipStreamSynchronize(c->tail);
-    if (c->hDone) { (void)hipHostFree(c->hDone); c->hDone = nullptr; c->dDone = nullptr; }
-    if (c->hMaskPin) { (void)hipHostFree(c->hMaskPin); c->hMaskPin = nullptr; c->hMaskPinChains = 0; }
-    for (auto &m : c->dMask) m = nullptr;
-    c->sbp.active = false;
-    c->pfPending = false;
-    c->where = {};      // (the reference-layout arrays are gone)
-    c->pnFillValid = false;
-    c->ckF[0] = c->ckF[1] = c->ckB[0] = c->ckB[1] = nullptr;
-    c->wsSavedF = c->wsSavedB = 0;
-    c->wsActive = c->wsCold = false;
-    for (auto &n : c->nat) n = nullptr;
-    c->rocco.scores = c->rocco.mx = nullptr;
-    c->rocco.sol = nullptr;
-    c->rocco.bt = nullptr;
-    c->rocco.bad = nullptr;
-    c->rocco.haveScores.clear();
-    c->rocco.haveSol.clear();
+    for (void *q : c->allocs) (void)hipFree(q);
+    static_cast<BatchState &>(*c) = BatchState{};
 }
 
 // Warm-up windows that gave zero re-runs on the bench workload with margin (hg38 x 32 synthetic: the state chain needs
@@ -521,23 +543,16 @@ extern "C" void csr_destroy(csr_ctx *c) {
             (void)hipEventDestroy(pr.second);
         }
     for (hipEvent_t ev : c->eventPool) (void)hipEventDestroy(ev);
-    for (DevBuf *b : {&c->bgBuf, &c->wrBuf, &c->textBuf, &c->qsBuf, &c->qpBuf, &c->stageBuf, &c->rocco.work, &c->rocco.arena,
-                      &c->rocco.runBuf, &c->dwb.chainBuf, &c->dwb.wtsBuf, &c->dwb.tmplBuf, &c->dwb.noiseBuf, &c->dwb.rowBuf,
-                      &c->dwb.partBuf, &c->dwb.outBuf, &c->dwb.vecBuf, &c->dwb.xBuf, &c->dwb.meanBuf})
-        if (b->ptr) { (void)hipFree(b->ptr); b->ptr = nullptr; b->cap = 0; }
-    if (c->hMail) (void)hipHostFree(c->hMail);
     if (c->evFork) (void)hipEventDestroy(c->evFork);
     if (c->evJoin) (void)hipEventDestroy(c->evJoin);
     if (c->evFork2) (void)hipEventDestroy(c->evFork2);
     if (c->evPf) (void)hipEventDestroy(c->evPf);
     if (c->evTailJoin) (void)hipEventDestroy(c->evTailJoin);
     if (c->tail) { (void)hipStreamSynchronize(c->tail); (void)hipStreamDestroy(c->tail); }
-    if (c->hDone) (void)hipHostFree(c->hDone);
-    if (c->hMaskPin) (void)hipHostFree(c->hMaskPin);
     if (c->zeroStream) (void)hipStreamDestroy(c->zeroStream);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;       // (the device is still selected: the work buffers free themselves)
 }
 
 extern "C" int csr_set_tuning(csr_ctx *c, int32_t block_len, int32_t warm_p, int32_t warm_x, int32_t warm_b) {
@@ -658,7 +673,7 @@ extern "C" int csr_get_run_stats(csr_ctx *c, csr_run_stats *out) {
     out->warm_x = c->warmX;
     out->warm_b = c->warmB;
     out->x_tol_ulps = c->xTolUlps;
-    out->local_repairs = c->hMail ? (int64_t)reinterpret_cast<const unsigned int *>(c->hMail)[MAIL_LOCAL] : 0;
+    out->local_repairs = c->hMail ? (int64_t)reinterpret_cast<const unsigned int *>(c->hMail.ptr)[MAIL_LOCAL] : 0;
     out->ws_warm_f = c->wsWarmF;
     out->ws_warm_b = c->wsWarmB;
     return 0;

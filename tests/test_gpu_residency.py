@@ -301,3 +301,107 @@ def test_every_call_sequence_launches_the_recorded_conversions(product, monkeypa
     if not switched:
         assert got == want
         assert all(r.get("pipeline_redos", 0) == 0 for r in got.values())
+
+
+def _same(got, ref, msg):
+    """bit for bit, through lists / dicts of arrays and numbers"""
+    if isinstance(ref, dict):
+        assert sorted(got) == sorted(ref), msg
+        for k in ref:
+            _same(got[k], ref[k], f"{msg} {k}")
+    elif isinstance(ref, (list, tuple)):
+        assert len(got) == len(ref), msg
+        for i, (g, r) in enumerate(zip(got, ref)):
+            _same(g, r, f"{msg} [{i}]")
+    else:
+        np.testing.assert_array_equal(got, ref, err_msg=msg)
+
+
+def test_batches_of_other_shapes_on_one_context_equal_fresh_contexts(product):
+    """Nothing of a batch survives `csr_batch_configure` -- by construction (every per-batch member of the context is one struct that
+    configure resets as a whole), checked here with the calls that allocate at first use: ONE exact-mode `DeviceBatch` runs batch A
+    (levelTrend, m = 5, chains [1000, 70, 64]), then batch B (level, m = 3, chains [300, 130]), then A again, and every segment
+    equals, bit for bit, the same calls on a fresh context: the resident inputs, every array `download` hands out, the sums, the
+    scores and the ROCCO solutions.  B after A leaves the old batch's first-use buffers (the latent track of `synthesize` first)
+    larger than needed, A after B smaller; the shapes are the smallest with more than one chain, a chain of exactly one 64-bin
+    block, a chain that ends inside a block, and a change of m, of the state dimension and of the padded size in both directions.
+    After a reconfigure there are no scores and no ROCCO solution until they are produced again, and the run counters start at zero.
+
+    (`background_apply` declares the resident fit stale, so `rocco_scores` needs a fit after it: A fits again -- a second `step`, on
+    the data minus the applied background -- between the two.)"""
+    from consenrich_amd import _lib as L
+    from consenrich_amd.batch import _ARR, DeviceBatch, ModelParams
+    from oracle import background as bgo
+
+    lam_first, lam = bgo.penalties(60, 2.0)
+    what = L.EXPORT_FORWARD | L.EXPORT_SMOOTH | L.EXPORT_RESID
+    counters = ("fix_launches", "reruns_p", "reruns_x", "reruns_b", "pipeline_redos", "local_repairs", "sb_bailouts", "tail_groups",
+                "nat_first_use_off_main")
+
+    def collect(b, out):
+        nc = len(b.chain_lens)
+        out["inputs"] = [b.download_inputs(c) for c in range(nc)]
+        arrays = []
+        for c in range(nc):
+            per = {}
+            for name in _ARR:
+                try:
+                    per[name] = b.download(c, name)
+                except L.ConsenrichAMDError as e:
+                    assert "was not exported" in str(e), (name, str(e))
+            arrays.append(per)
+        assert {"xs", "Ps", "lag"} <= set(arrays[0]), sorted(arrays[0])
+        out["arrays"] = arrays
+        out["sums"] = b.sums()
+        out["scores"] = [b.download_scores(c) for c in range(nc)]
+        out["solution"] = [b.rocco_solution(c) for c in range(nc)]
+        return out
+
+    def after_configure(b, reconfigured):
+        if not reconfigured:
+            return
+        with pytest.raises(L.ConsenrichAMDError, match="no scores"):
+            b.download_scores(0)
+        with pytest.raises(L.ConsenrichAMDError, match="no ROCCO solution"):
+            b.rocco_solution(0)
+        rs = b.run_stats()
+        assert [rs[k] for k in counters] == [0] * len(counters), rs
+
+    def score_and_select(b, out):
+        b.rocco_scores("state")
+        with pytest.raises(L.ConsenrichAMDError, match="no ROCCO solution"):
+            b.rocco_solution(0)
+        out["rocco"] = b.rocco(budget=0.1, gamma=0.5)
+
+    def batch_a(b, reconfigured):
+        out = {}
+        b.configure(ModelParams(state_dim=2), 5, [1000, 70, 64])
+        after_configure(b, reconfigured)
+        b.synthesize(11)
+        out["step"] = b.step(L.RETURN_NLL, what)
+        outs, path = b.ecm(max_iters=2, inner_iters=2, rtol=0.0, use_kappa=True)
+        out["ecm"] = [[o.iters_done for o in outs], [o.final_nll for o in outs], path]
+        out["bg"] = b.background_update(lam_first, lam, raise_on_error=False)
+        b.background_apply()
+        out["refit"] = b.step(L.RETURN_NLL, what)
+        score_and_select(b, out)
+        return collect(b, out)
+
+    def batch_b(b, reconfigured):
+        out = {}
+        b.configure(ModelParams(state_dim=1), 3, [300, 130])
+        after_configure(b, reconfigured)
+        b.synthesize(12)
+        b.stats()
+        out["fb"] = b.forward_backward(L.RETURN_NLL)
+        score_and_select(b, out)
+        return collect(b, out)
+
+    fresh = {}
+    for name, run in (("A", batch_a), ("B", batch_b)):
+        with DeviceBatch(0, x_tol_ulps=0) as b:
+            fresh[name] = run(b, False)
+    with DeviceBatch(0, x_tol_ulps=0) as b:
+        _same(batch_a(b, False), fresh["A"], "A on a new context")
+        _same(batch_b(b, True), fresh["B"], "B after A")
+        _same(batch_a(b, True), fresh["A"], "A after B")
