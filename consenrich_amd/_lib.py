@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libconsenrich_amd.so")
 FP = C.POINTER(C.c_float)
 DP = C.POINTER(C.c_double)
 I64P = C.POINTER(C.c_int64)
+I32P = C.POINTER(C.c_int32)
 
 # flag bits (include/consenrich_amd.h)
 USE_LAMBDA, USE_KAPPA, USE_QSCALE, USE_APN, RETURN_NLL, NLL_IN_D = (1 << i for i in range(6))
@@ -155,6 +156,7 @@ ROCCO_FIXED_PENALTY, ROCCO_TARGET_COUNT = 0, 1
 ROCCO_SCORE_STATE, ROCCO_SCORE_LOWER_CONFIDENCE = 0, 1
 ROCCO_ERR_VALUE = 2
 DWB_ERR_VALUE = 2
+SEG_ERR_VALUE = 2
 
 
 class KernelTime(C.Structure):
@@ -272,6 +274,15 @@ SYMBOLS = {
     "csr_dwb_panel_end": (C.c_int, [C.c_void_p]),
     "csr_dwb_tail_stats": (C.c_int, [C.c_void_p, DP, C.c_int64, C.c_int32, DP, DP, I64P, DP]),
     "csr_batch_dwb_observed": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, DP, DP, I64P, DP]),
+    "csr_segments_run": (C.c_int, [C.c_void_p, DP, C.c_int64, C.c_int32, I64P, C.c_int32, DP, C.c_int32, DP, C.c_int32, C.c_int32,
+                                   C.c_int32, I64P, I64P, I32P]),
+    "csr_batch_segments_run": (C.c_int, [C.c_void_p, I32P, I64P, I32P, DP, DP, C.c_int32, C.c_int32, C.c_int32, I64P, I64P, I32P]),
+    "csr_dwb_panel_segments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, I32P, I64P, I32P, DP, DP, C.c_int32, C.c_int32,
+                                         C.c_int32, I64P, I64P, I32P]),
+    "csr_segments_flagged": (C.c_int, [C.c_void_p, C.c_int32, I32P, I32P, I32P, I64P]),
+    "csr_segments_flagged_fetch": (C.c_int, [C.c_void_p, C.c_int32, DP, I64P]),
+    "csr_segments_flagged_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, I64P]),
+    "csr_segments_fetch": (C.c_int, [C.c_void_p, I64P, I64P, I64P, I64P, DP, DP, DP, DP]),
 }
 
 _lib = None

@@ -556,6 +556,51 @@ class DeviceBatch:
                             calibration_quantile=calibration_quantile, pooled_floors=pooled_floors,
                             draws_per_group=draws_per_group, noise=noise)
 
+    # -- multiscale candidate segments of the resident scores and of null replays (consenrich_amd/segments.py) --------------
+    def _segment_tracks(self, views, scales, min_run, gap, total_cap, view_cap):
+        from . import segments as S
+
+        n_s, sc_all, n_v, thr_all, ns_all = S.pack(scales, [v.threshold for v in views], [v.null_scale for v in views])
+        nc = len(self.chain_lens)
+        rows, counters, flagged = np.zeros(nc, np.int64), np.zeros(3 * nc, np.int64), C.c_int32(0)
+        cap = 0 if view_cap is None else view_cap
+        S._call(self._lib.csr_batch_segments_run(self._ctx, n_s.ctypes.data_as(L.I32P), sc_all.ctypes.data_as(L.I64P),
+                                                 n_v.ctypes.data_as(L.I32P), L.dp(thr_all), L.dp(ns_all), min_run, gap, cap,
+                                                 rows.ctypes.data_as(L.I64P), counters.ctypes.data_as(L.I64P), C.byref(flagged)))
+        tracks = S.collect(self._ctx, rows, counters, flagged.value, cap)
+        return [S.compose(tracks[c], views[c], total_cap, view_cap) for c in range(nc)]
+
+    def segment_candidates(self, threshold_views, *, scale_bins=None, dependence_spans=None, min_run_bins=1, max_gap_bins=0,
+                           max_segments=20000, max_segments_per_view=1000):
+        """`segments.multiscale_candidates` of every chain's RESIDENT score track (rocco_scores / upload_scores) in one call:
+        (candidates, diagnostics) per chain.  threshold_views: one set per chain; scale_bins: for all chains, one list per
+        chain, or None for the reference's five scales at the chain's dependence span.  Reads the tracks; no resident array
+        changes and nothing of the fit is downloaded."""
+        from . import segments as S
+
+        nc = len(self.chain_lens)
+        if len(threshold_views) != nc:
+            raise ValueError("one set of threshold views per chain")
+        views = [S.Views(v) for v in threshold_views]
+        spans = dependence_spans if dependence_spans is not None and np.ndim(dependence_spans) else [dependence_spans] * nc
+        per_chain = scale_bins is not None and len(scale_bins) > 0 and np.ndim(scale_bins[0]) > 0
+        scales = [S.resolve_scales(self.chain_lens[c], scale_bins[c] if per_chain else scale_bins, spans[c]) for c in range(nc)]
+        total_cap, view_cap = S._caps(max_segments, max_segments_per_view)
+        return self._segment_tracks(views, scales, max(int(min_run_bins), 1), max(int(max_gap_bins), 0), total_cap, view_cap)
+
+    def dwb_replay(self, templates, threshold_views, *, bandwidths, num_replay=64, kernel="bartlett", random_seed=0,
+                   scale_bins=None, min_run_bins=1, max_gap_bins=0, max_segments=20000, max_segments_per_view=1000,
+                   draws_per_group=0, noise=None):
+        """`dwb.null_replay_candidates` for the batch's chains with the observed candidates taken from the RESIDENT score
+        tracks; the replays use buffers of the panel's own.  No resident array changes."""
+        from . import dwb as W
+
+        return W._run_replays(self._ctx, self._segment_tracks, list(self.chain_lens), templates, threshold_views,
+                              bandwidths=bandwidths, num_replay=num_replay, kernel=kernel, random_seed=random_seed,
+                              scale_bins=scale_bins, min_run_bins=min_run_bins, max_gap_bins=max_gap_bins,
+                              max_segments=max_segments, max_segments_per_view=max_segments_per_view,
+                              draws_per_group=draws_per_group, noise=noise)
+
     def export(self, what: int):
         L.check(self._lib.csr_batch_export(self._ctx, int(what)))
 

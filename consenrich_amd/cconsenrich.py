@@ -630,3 +630,6 @@ from .dwb import (  # noqa: E402,F401
     cGenerateDWBMultipliersFromNoise,
     cStationaryNullDWBDraw,
 )
+
+# multiscale candidate segments of a score track or a null replay (pyx:9460-9669), implemented in consenrich_amd/segments.py
+from .segments import cMultiscaleCandidateSegmentStats  # noqa: E402,F401

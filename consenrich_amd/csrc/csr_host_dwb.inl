@@ -6,6 +6,8 @@
 // working set is draws_per_group x (padded bins of all chains) doubles whatever n_draws is, at the price of a second stencil and
 // walk per draw.
 
+static void seg_release(csr_ctx *c);     // csr_host_segments.inl
+
 static int dwb_value_error(const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -352,6 +354,7 @@ extern "C" int csr_dwb_panel_end(csr_ctx *c) {
     d.ready = false;
     HIPOK(hipStreamSynchronize(c->stream));
     for (DevBuf *b : {&d.rowBuf, &d.noiseBuf, &d.tmplBuf, &d.partBuf, &d.outBuf, &d.meanBuf}) b->release();
+    seg_release(c);     // the work space of csr_dwb_panel_segments goes with the panel
     return 0;
 }
 

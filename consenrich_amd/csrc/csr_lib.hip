@@ -12,6 +12,7 @@
 #include "csr_gain.h"
 #include "csr_rocco.h"
 #include "csr_dwb.h"
+#include "csr_segments.h"
 
 #include <algorithm>
 #include <array>
@@ -391,6 +392,24 @@ struct csr_ctx : BatchState {
         int nDraws = 0, group = 0;
         DevBuf chainBuf, wtsBuf, tmplBuf, noiseBuf, rowBuf, partBuf, outBuf, vecBuf, xBuf, meanBuf;
     } dwb;
+    // multiscale candidate segments (csr_host_segments.inl): growable work space and the result of the last run, which stays
+    // until the next run so that the caller can resolve flagged views and fetch the rows
+    struct Seg {
+        DevBuf chainBuf, prefixBuf, excessBuf, exPrefixBuf, cntBuf, runBuf, keepBuf, statBuf, metaBuf, baseBuf, outBuf, xBuf;
+        bool have = false;
+        int cap = 0;
+        std::vector<int64_t> rowsPerTrack, counters;    // [track], [track][3]
+        std::vector<int64_t> oStart, oEnd, oScale, oView;
+        std::vector<double> oScore, oInteg, oMean, oMax;
+        struct Flagged {        // a view over the cap whose chosen set the values alone do not determine
+            int track, scaleIndex, view;
+            int64_t base;       // its `cap` output rows
+            std::vector<int64_t> start, end;
+            std::vector<double> score, integ, mean, mx;
+            bool resolved;
+        };
+        std::vector<Flagged> flagged;
+    } seg;
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -694,3 +713,4 @@ extern "C" int csr_get_run_stats(csr_ctx *c, csr_run_stats *out) {
 #include "csr_host_comm.inl"
 #include "csr_host_rocco.inl"
 #include "csr_host_dwb.inl"
+#include "csr_host_segments.inl"

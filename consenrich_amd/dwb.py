@@ -289,3 +289,118 @@ def stationary_null_panel(score_tracks, templates, null_centers, null_scales, *,
                       num_bootstrap=num_bootstrap, kernel=kernel, random_seed=random_seed,
                       calibration_quantile=calibration_quantile, pooled_floors=pooled_floors, draws_per_group=draws_per_group,
                       noise=noise)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# null replays scored as candidate segments (peaks.py:2858-2922): a third phase of the panel
+# ---------------------------------------------------------------------------------------------------------------
+SEGMENT_GROUP_BYTES = 16 << 30      # device memory a group of replay draws may take (rows + segment work space)
+SEGMENT_MAX_JOBS = 65535            # (draw, scale, view) jobs per chain of one device run (include/consenrich_amd.h)
+
+
+def _replay_group(lens, n_scales, n_views, num_replay, draws_per_group):
+    """Draws per group: the caller's, or what fits SEGMENT_GROUP_BYTES by the bound of include/consenrich_amd.h."""
+    s, v = max(max(n_scales), 1), max(max(n_views), 1)
+    most = min(num_replay, SEGMENT_MAX_JOBS // (s * v))     # draws x scales x views per chain: one grid dimension
+    if draws_per_group and int(draws_per_group) > 0:
+        return min(int(draws_per_group), most)
+    per_draw = sum(lens) * (16.0 + 16.0 * v + 24.5 * s * v)
+    return int(min(max(SEGMENT_GROUP_BYTES // max(per_draw, 1.0), 1), most))
+
+
+def _run_replays(ctx, observed, lens, templates, threshold_views, *, bandwidths, num_replay, kernel, random_seed, scale_bins,
+                 min_run_bins, max_gap_bins, max_segments, max_segments_per_view, draws_per_group, noise):
+    from . import segments as S
+
+    nc = len(lens)
+    kernel_code(kernel)
+    R = int(num_replay)
+    if R <= 0:
+        raise ValueError("num_replay must be positive")
+    total_cap, view_cap = S._caps(max_segments, max_segments_per_view)
+    if view_cap is None:
+        raise ValueError("null replays on the device need max_segments_per_view > 0")
+    bws = [_c_int(b) for b in (bandwidths if np.ndim(bandwidths) else [bandwidths] * nc)]
+    if not (len(bws) == len(templates) == len(threshold_views) == nc):
+        raise ValueError("one bandwidth, template and set of threshold views per chain")
+    tmpl = [_f64(t) for t in templates]
+    for c in range(nc):
+        if tmpl[c].shape[0] != lens[c] or lens[c] <= 0:
+            raise ValueError("a template must be as long as its chain's score track and not empty")
+        if not np.all(np.isfinite(tmpl[c])):
+            raise ValueError("`template` contains non-finite values")
+    views = [S.Views(v) for v in threshold_views]
+    replay_views = [v.for_replay() for v in views]
+    per_chain_bins = scale_bins is not None and len(scale_bins) > 0 and np.ndim(scale_bins[0]) > 0
+    scales = [S.resolve_scales(lens[c], scale_bins[c] if per_chain_bins else scale_bins, bws[c]) for c in range(nc)]
+    min_run, gap = max(int(min_run_bins), 1), max(int(max_gap_bins), 0)
+    strides = [lens[c] + 2 * max_lag(bws[c], kernel) for c in range(nc)]
+    need = R * max(strides)
+    z_stream = noise_stream(random_seed, need) if noise is None else _f64(noise)
+    if z_stream.shape[0] < need:
+        raise ValueError("noise length is too short for the requested DWB bandwidth")
+    L.require_gpu()
+    lib = L.lib()
+    group = _replay_group(lens, [len(s) for s in scales], [len(v.keys) for v in views], R, draws_per_group)
+    n_arr, bw_arr = np.asarray(lens, np.int64), np.asarray(bws, np.int32)
+    t_all = np.ascontiguousarray(np.concatenate(tmpl))
+    n_s, sc_all, n_v, thr_all, ns_all = S.pack(scales, [v.threshold for v in replay_views], [v.null_scale for v in replay_views])
+    replays = [[None] * R for _ in range(nc)]
+    capped = fallback = 0
+    _call(lib.csr_dwb_panel_begin(ctx, nc, n_arr.ctypes.data_as(L.I64P), bw_arr.ctypes.data_as(C.POINTER(C.c_int32)), _kname(kernel),
+                                  L.dp(t_all), L.dp(z_stream), z_stream.shape[0], R, group))
+    try:
+        for d0 in range(0, R, group):
+            g = min(group, R - d0)
+            rows, counters, flagged = np.zeros(nc * g, np.int64), np.zeros(nc * g * 3, np.int64), C.c_int32(0)
+            S._call(lib.csr_dwb_panel_segments(ctx, d0, g, n_s.ctypes.data_as(L.I32P), sc_all.ctypes.data_as(L.I64P),
+                                               n_v.ctypes.data_as(L.I32P), L.dp(thr_all), L.dp(ns_all), min_run, gap, view_cap,
+                                               rows.ctypes.data_as(L.I64P), counters.ctypes.data_as(L.I64P), C.byref(flagged)))
+            # the flagged views of this group are resolved before the next group overwrites its rows
+            tracks = S.collect(ctx, rows, counters, flagged.value, view_cap)
+            capped += S.last_run_stats()["capped_views"]
+            fallback += S.last_run_stats()["fallback_views"]
+            for c in range(nc):
+                for b in range(g):
+                    cands, diag = S.compose(tracks[c * g + b], replay_views[c], total_cap, view_cap)
+                    replays[c][d0 + b] = dict(
+                        candidate_count=len(cands), diagnostics=diag,
+                        score=np.asarray([k["score"] for k in cands], np.float64),
+                        integrated_excess=np.asarray([k["integrated_excess"] for k in cands], np.float64),
+                        max_excess=np.asarray([k["max_excess"] for k in cands], np.float64))
+    finally:
+        L.check(lib.csr_dwb_panel_end(ctx))
+    obs = observed(views, scales, min_run, gap, total_cap, view_cap)
+    return [dict(observed=obs[c], replays=replays[c], scale_bins=scales[c], draws_per_group=group, capped_views=capped,
+                 fallback_views=fallback) for c in range(nc)]
+
+
+def null_replay_candidates(score_tracks, templates, threshold_views, *, bandwidths, num_replay=64, kernel="bartlett", random_seed=0,
+                           scale_bins=None, min_run_bins=1, max_gap_bins=0, max_segments=20000, max_segments_per_view=1000,
+                           draws_per_group=0, noise=None):
+    """The candidate side of the reference's DWB peak scoring (peaks.py:2685, 2858-2922) for every chain of one seed.
+
+    threshold_views: per chain, a mapping key -> view or a sequence of views -- dicts with threshold_z, threshold, null_scale and
+    null_center, e.g. what `stationary_null_panel` returns for the chain.  scale_bins: explicit scales for all chains, one list
+    per chain, or None for the reference's five scales at dependence span = the chain's bandwidth.  The replays are draws
+    0 .. num_replay - 1 of the seed's noise stream, exactly the panel's, scored against the views shifted by their null centre
+    (`_thresholdViewsForNullReplay`); draws_per_group (0 = what fits 16 GiB) bounds the device working set and changes no result.
+
+    Returns, per chain, a dict: observed = (candidates, diagnostics) of the score track as `segments.multiscale_candidates`
+    gives them; replays = per draw a dict with candidate_count, the metric arrays score / integrated_excess / max_excess of its
+    candidates and the cap diagnostics; scale_bins; capped_views / fallback_views of all replays (views over the per-view cap,
+    and those of them NumPy decided on the host)."""
+    from . import segments as S
+
+    tracks = [_f64(s) for s in score_tracks]
+
+    def observed(views, scales, min_run, gap, total_cap, view_cap):
+        return [S.compose(S.cMultiscaleCandidateSegmentStats(tracks[c], np.asarray(scales[c], np.int64),
+                                                             np.asarray(views[c].threshold, np.float64),
+                                                             np.asarray(views[c].null_scale, np.float64), min_run, gap, view_cap),
+                          views[c], total_cap, view_cap) for c in range(len(tracks))]
+
+    return _run_replays(None, observed, [s.shape[0] for s in tracks], templates, threshold_views, bandwidths=bandwidths,
+                        num_replay=num_replay, kernel=kernel, random_seed=random_seed, scale_bins=scale_bins,
+                        min_run_bins=min_run_bins, max_gap_bins=max_gap_bins, max_segments=max_segments,
+                        max_segments_per_view=max_segments_per_view, draws_per_group=draws_per_group, noise=noise)

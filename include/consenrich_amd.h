@@ -583,6 +583,57 @@ int csr_dwb_tail_stats(csr_ctx *ctx, const double *x, int64_t n, int32_t n_z, co
 int csr_batch_dwb_observed(csr_ctx *ctx, int32_t chain, int32_t n_z, const double *offsets, const double *scales, int64_t *counts,
                            double *soft);
 
+/* ---- multiscale candidate segments: pyx:9460-9669 `cMultiscaleCandidateSegmentStats`, which the reference's DWB peak scoring
+ * (peaks.py:2359-2481, 2605-3020) calls on the observed score track and on every null replay ------------------------------------
+ * Every returned value equals the reference's bit for bit.  A TRACK is one vector of values: the host vector, a chain's resident
+ * score track, or one draw of one chain of the DWB panel.  Per track: scales (window widths in bins, clamped to [1, n]; at most
+ * 16) and views ((threshold, null scale) pairs, null scales raised to DBL_MIN; at most 16).  min_run_bins below 1 counts as 1,
+ * max_gap_bins below 0 as 0, max_segments_per_view <= 0 as "no cap".  Rows are ordered by track, scale, view, start; the `scale`
+ * column holds the clamped width, the `view` column the index of the view.  counters: per track 3 values -- eligible candidates,
+ * views that hit the cap, candidates the cap discarded.
+ *
+ * Two phases, so that no output size has to be guessed.  Phase 1 (a *_run entry, or csr_dwb_panel_segments) computes everything,
+ * keeps the rows in the context and returns the row counts and counters.  Phase 2 (csr_segments_fetch) copies the eight row
+ * arrays; it addresses the context's LAST run.  ctx NULL = the default context.
+ *
+ * The cap.  The reference keeps np.argpartition(-score, cap - 1)[:cap] of a view's candidates, ordered by start.  That set is
+ * determined by the values only if every candidate score of the view is finite and the cap-th and (cap + 1)-th largest differ;
+ * then the device selects it exactly.  Otherwise the view is FLAGGED: *n_flagged counts such views, csr_segments_flagged names
+ * one (track, index into the track's scales, view, number of candidates), csr_segments_flagged_fetch returns its candidates'
+ * score and start, and the caller passes the chosen `cap` candidates in output order to csr_segments_flagged_select (the Python
+ * layer uses the reference's own two NumPy calls).  csr_segments_fetch fails while a flagged view is unresolved.
+ *
+ * Device memory of a run with R rows (tracks per chain), N bins per row (all chains), S scales and V views:
+ * about R * N * (8 + 16 V + 24.5 S V) bytes (562 bytes per bin and row at 5 scales x 4 views): the arrays are sized for the worst
+ * case of n / 2 runs per (row, scale, view).  It is kept for the next run and freed by csr_dwb_panel_end (with the panel's own
+ * buffers) or with the context.  A run's maximum is taken by eight lanes, so a single run costs length / 8 dependent loads: one
+ * run as long as a chromosome (a scale of n, or a threshold below the whole track) is a loop of n / 8 steps of one lane group.
+ * R * S * V may not exceed 65535.  The reference's one ValueError (different numbers of thresholds and null scales) returns
+ * CSR_SEG_ERR_VALUE before any launch; n, n_scales or n_thresholds <= 0 gives no rows and zero counters. */
+enum { CSR_SEG_ERR_VALUE = 2 };
+int csr_segments_run(csr_ctx *ctx, const double *scores, int64_t n, int32_t n_scales, const int64_t *scales, int32_t n_thresholds,
+                     const double *thresholds, int32_t n_null_scales, const double *null_scales, int32_t min_run_bins,
+                     int32_t max_gap_bins, int32_t max_segments_per_view, int64_t *n_rows, int64_t *counters, int32_t *n_flagged);
+/* The resident score tracks of a batch (every chain needs one: csr_batch_rocco_scores / csr_batch_upload_scores); they are only
+ * read and no resident array changes.  n_scales / n_views: one count per chain; scales, thresholds and null_scales: the chains'
+ * values one after the other.  rows[chain], counters[chain][3]; track = chain. */
+int csr_batch_segments_run(csr_ctx *ctx, const int32_t *n_scales, const int64_t *scales, const int32_t *n_views,
+                           const double *thresholds, const double *null_scales, int32_t min_run_bins, int32_t max_gap_bins,
+                           int32_t max_segments_per_view, int64_t *rows, int64_t *counters, int32_t *n_flagged);
+/* A third phase of the DWB panel, between csr_dwb_panel_begin and csr_dwb_panel_end, in any order with the other two: draws
+ * first_draw .. first_draw + n_draws - 1 of every chain (n_draws at most the panel's draws per group) are made as in the other
+ * phases and read.  Needs max_segments_per_view > 0.  rows[chain][draw], counters[chain][draw][3]; track = chain * n_draws + draw.
+ * The caller resolves the flagged views of this group and fetches its rows before it asks for the next group. */
+int csr_dwb_panel_segments(csr_ctx *ctx, int32_t first_draw, int32_t n_draws, const int32_t *n_scales, const int64_t *scales,
+                           const int32_t *n_views, const double *thresholds, const double *null_scales, int32_t min_run_bins,
+                           int32_t max_gap_bins, int32_t max_segments_per_view, int64_t *rows, int64_t *counters,
+                           int32_t *n_flagged);
+int csr_segments_flagged(csr_ctx *ctx, int32_t k, int32_t *track, int32_t *scale_index, int32_t *view, int64_t *n_candidates);
+int csr_segments_flagged_fetch(csr_ctx *ctx, int32_t k, double *score, int64_t *start);
+int csr_segments_flagged_select(csr_ctx *ctx, int32_t k, int64_t n_selected, const int64_t *selected);
+int csr_segments_fetch(csr_ctx *ctx, int64_t *start, int64_t *end, int64_t *scale, int64_t *view, double *score,
+                       double *integrated, double *mean, double *max_excess);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
