@@ -302,11 +302,8 @@ extern "C" int csr_batch_upload_multipliers(csr_ctx *c, int32_t chain, const flo
         HIPOK(hipMemcpyAsync(scr + ci.off, src[k], sizeof(float) * ci.n, hipMemcpyHostToDevice, c->stream));
         Prm p = c->p;
         p.chainActive = c->dActive;
-        {
-            Scope sc(c, "import_f32");
-            hipLaunchKernelGGL(k_import_f32, dim3(grid_slots(c)), dim3(256), 0, c->stream, p, scr, 1, 0, dst[k], 1, 0);
-        }
-        LAUNCH_CHECK("k_import_f32");
+        CHECK(launch(c, "import_f32", "k_import_f32", k_import_f32, dim3(grid_slots(c)), dim3(256), 0, c->stream, p, scr, 1, 0, dst[k], 1,
+                     0));
         HIPOK(hipStreamSynchronize(c->stream));
     }
     multipliers_changed(c);

@@ -177,13 +177,9 @@ extern "C" int csr_batch_gather_tracks(csr_ctx *c, csr_comm *k, int64_t cap_bins
     HIPOK(hipMemcpyAsync(dPackPos, pos.data(), sizeof(int64_t) * (size_t)nc, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemsetAsync(k->send.ptr, 0, sendBytes, c->stream));
     const int d = c->mdl.state_dim;
-    {
-        Scope sc(c, "gather_pack");
-        hipLaunchKernelGGL(k_pack_tracks, dim3((unsigned)((c->Npad + 255) / 256)), dim3(256), 0, c->stream, c->nat[CSR_ARR_XS], d,
-                           c->nat[CSR_ARR_PS], d * d, c->dChainOff, c->dChainLen, dPackPos, nc, c->Npad,
-                           reinterpret_cast<float2 *>(k->send.ptr));
-    }
-    LAUNCH_CHECK("k_pack_tracks");
+    CHECK(launch(c, "gather_pack", "k_pack_tracks", k_pack_tracks, dim3((unsigned)((c->Npad + 255) / 256)), dim3(256), 0, c->stream,
+                 c->nat[CSR_ARR_XS], d, c->nat[CSR_ARR_PS], d * d, c->dChainOff, c->dChainLen, dPackPos, nc, c->Npad,
+                 reinterpret_cast<float2 *>(k->send.ptr)));
     {
         Scope sc(c, "gather_allgather");
         NCCLOK(g_rccl.AllGather(k->send.ptr, k->recv.ptr, (size_t)cap_bins * 2, ncclFloat, k->comm, c->stream));

@@ -104,11 +104,9 @@ static int dwb_make_rows(csr_ctx *c, int64_t d0, int g, bool stencil, bool stand
     csr_ctx::Dwb &d = c->dwb;
     const int nc = (int)d.chains.size();
     if (stencil) {
-        Scope sc(c, "dwb_movsum");
         const dim3 grid((unsigned)((d.longest + DWB_ST - 1) / DWB_ST), (unsigned)g, (unsigned)nc);
-        hipLaunchKernelGGL(k_dwb_movsum, grid, dim3(DWB_ST), 0, c->stream, (const DwbChain *)d.chainBuf.ptr,
-                           (const double *)d.noiseBuf.ptr, (const double *)d.wtsBuf.ptr, (double *)d.rowBuf.ptr, d.rowLen, d0);
-        LAUNCH_CHECK("k_dwb_movsum");
+        CHECK(launch(c, "dwb_movsum", "k_dwb_movsum", k_dwb_movsum, grid, dim3(DWB_ST), 0, c->stream, (const DwbChain *)d.chainBuf.ptr,
+                     (const double *)d.noiseBuf.ptr, (const double *)d.wtsBuf.ptr, (double *)d.rowBuf.ptr, d.rowLen, d0));
     }
     DwbWalkArgs a;
     a.chains = (const DwbChain *)d.chainBuf.ptr;
@@ -122,12 +120,11 @@ static int dwb_make_rows(csr_ctx *c, int64_t d0, int g, bool stencil, bool stand
     a.apply = apply;
     {
         Scope sc(c, "dwb_walk");
-        hipLaunchKernelGGL(k_dwb_walk, dim3((unsigned)((g + DWB_WR - 1) / DWB_WR), (unsigned)nc), dim3(64), 0, c->stream, a);
+        CHECK(launch(c, nullptr, "k_dwb_walk", k_dwb_walk, dim3((unsigned)((g + DWB_WR - 1) / DWB_WR), (unsigned)nc), dim3(64), 0, c->stream, a));
         if (apply)
-            hipLaunchKernelGGL(k_dwb_centre, dim3((unsigned)((d.longest + 255) / 256), (unsigned)g, (unsigned)nc), dim3(256), 0,
-                               c->stream, a.chains, a.rows, (const double *)a.means, a.rowLen, g);
+            CHECK(launch(c, nullptr, "k_dwb_centre", k_dwb_centre, dim3((unsigned)((d.longest + 255) / 256), (unsigned)g, (unsigned)nc),
+                         dim3(256), 0, c->stream, a.chains, a.rows, (const double *)a.means, a.rowLen, g));
     }
-    LAUNCH_CHECK("k_dwb_walk");
     return 0;
 }
 
@@ -156,11 +153,10 @@ static int dwb_tail_rows(csr_ctx *c, const double *rows, int64_t rowLen, const D
     {
         Scope sc(c, "dwb_tail");
         const dim3 grid((unsigned)((maxChunks * nZ + 63) / 64), (unsigned)g, (unsigned)nc);
-        hipLaunchKernelGGL(k_dwb_tail, grid, dim3(64), 0, c->stream, a);
+        CHECK(launch(c, nullptr, "k_dwb_tail", k_dwb_tail, grid, dim3(64), 0, c->stream, a));
         const int64_t total = (int64_t)nc * g * nZ;
-        hipLaunchKernelGGL(k_dwb_tail_fold, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, c->stream, a, nc);
+        CHECK(launch(c, nullptr, "k_dwb_tail_fold", k_dwb_tail_fold, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, c->stream, a, nc));
     }
-    LAUNCH_CHECK("k_dwb_tail");
     return 0;
 }
 
@@ -304,13 +300,9 @@ extern "C" int csr_dwb_panel_order_stats(csr_ctx *c, int32_t n_ranks, const int6
     for (int64_t d0 = 0; d0 < d.nDraws; d0 += d.group) {
         const int g = (int)std::min<int64_t>(d.group, d.nDraws - d0);
         CHECK(dwb_make_rows(c, d0, g, true, true, true));
-        {
-            Scope sc(c, "dwb_select");
-            hipLaunchKernelGGL(k_dwb_select, dim3((unsigned)g, (unsigned)nc), dim3(256), 0, c->stream, (const DwbChain *)d.chainBuf.ptr,
-                               (const double *)d.rowBuf.ptr, d.rowLen, (const long long *)dRank, (int)n_ranks, dOut,
-                               (int64_t)d.nDraws, d0);
-        }
-        LAUNCH_CHECK("k_dwb_select");
+        CHECK(launch(c, "dwb_select", "k_dwb_select", k_dwb_select, dim3((unsigned)g, (unsigned)nc), dim3(256), 0, c->stream,
+                     (const DwbChain *)d.chainBuf.ptr, (const double *)d.rowBuf.ptr, d.rowLen, (const long long *)dRank, (int)n_ranks,
+                     dOut, (int64_t)d.nDraws, d0));
     }
     HIPOK(hipMemcpyAsync(out, dOut, 8 * nOut, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));

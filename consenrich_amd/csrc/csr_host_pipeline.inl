@@ -25,15 +25,11 @@ extern "C" int csr_batch_stats(csr_ctx *c) {
         CHECK(ensure_sb_nat(c));
         p.natSZ = reinterpret_cast<double2 *>(c->sbNatSZ);
     }
-    {
-        // 16-byte loads, four bins per thread; 64-bin tiles (32 when the block length is not a multiple of 64)
-        Scope sc(c, "stats");
-        const int ts = (c->B % 64 == 0) ? 64 : 32;
-        const int grid = (int)(c->NG * (c->B / ts) * (ts == 64 ? 4 : 2));
-        if (ts == 64) hipLaunchKernelGGL((k_stats_v4<64, 4>), dim3(grid), dim3(256), 0, c->stream, p);
-        else hipLaunchKernelGGL((k_stats_v4<32, 4>), dim3(grid), dim3(256), 0, c->stream, p);
-    }
-    LAUNCH_CHECK("k_stats");
+    // 16-byte loads, four bins per thread; 64-bin tiles (32 when the block length is not a multiple of 64)
+    const int ts = (c->B % 64 == 0) ? 64 : 32;
+    const int grid = (int)(c->NG * (c->B / ts) * (ts == 64 ? 4 : 2));
+    void (*const kernel)(Prm) = ts == 64 ? &k_stats_v4<64, 4> : &k_stats_v4<32, 4>;
+    CHECK(launch(c, "stats", "k_stats_v4", kernel, dim3(grid), dim3(256), 0, c->stream, p));
     c->statsValid = true;
     c->natSZValid = natSZ;
     c->haveFwd = c->haveBwd = false;
@@ -108,9 +104,7 @@ static int flush_pending_check(csr_ctx *c) {
     Prm p = c->p;
     p.xTolUlps = c->xTolUlps;           // the acceptance rule of the stage that is being checked
     take_pending_check(c, p);
-    Scope sc(c, "chain_check");
-    hipLaunchKernelGGL(k_chain_check, dim3((int)c->NG), dim3(64), 0, c->stream, p);
-    LAUNCH_CHECK("k_chain_check");
+    CHECK(launch(c, "chain_check", "k_chain_check", k_chain_check, dim3((int)c->NG), dim3(64), 0, c->stream, p));
     c->rs.fix_launches++;
     return 0;
 }
@@ -147,6 +141,17 @@ static bool unit_f(const Prm &p) { return p.F00 == 1.0 && p.F10 == 0.0 && p.F11 
 // ---- launch idioms shared by the passes ---------------------------------------------------------------------------
 // one workgroup per 32-bin tile of every wavefront-group (the tiled conversions between the two layouts)
 static dim3 tile_grid(const csr_ctx *c) { return dim3((int)(c->NG * (c->B / 32))); }
+// one more array for a tiled conversion launch (k_export_tiled): n of the E components of every `src` record go to `dst`
+static ExpDesc &exp_add(ExpList &L, const float *src, float *dst, int E, int n, int skipLast = 0) {
+    ExpDesc &d = L.d[L.count++];
+    memset(&d, 0, sizeof(d));
+    d.src = src;
+    d.dst = dst;
+    d.E = E;
+    d.n = n;
+    d.skipLast = skipLast;
+    return d;
+}
 // the side stream continues from this point of the main stream
 static int fork_side(csr_ctx *c, hipEvent_t ev) {
     HIPOK(hipEventRecord(ev, c->stream));
@@ -155,18 +160,14 @@ static int fork_side(csr_ctx *c, hipEvent_t ev) {
 }
 // NIS / NLL epilogue (D in the reference layout goes through one LDS tile per block)
 static int launch_dstat(csr_ctx *c, const Prm &p, hipStream_t st) {
-    {
-        Scope sc(c, "fwd_dstat", st);
-        if (p.natD) hipLaunchKernelGGL(k_fwd_dstat<true>, dim3((int)c->NG), dim3(256), sizeof(float) * 64 * (c->B + 1), st, p);
-        else hipLaunchKernelGGL(k_fwd_dstat<false>, dim3((int)c->NG), dim3(256), 0, st, p);
-    }
-    LAUNCH_CHECK("k_fwd_dstat");
-    return 0;
+    void (*const kernel)(Prm) = p.natD ? &k_fwd_dstat<true> : &k_fwd_dstat<false>;
+    const size_t lds = p.natD ? sizeof(float) * 64 * (c->B + 1) : 0;
+    return launch(c, "fwd_dstat", "k_fwd_dstat", kernel, dim3((int)c->NG), dim3(256), lds, st, p);
 }
 // per-chain sums of the per-block sums the epilogue (or the chain itself) left
-static void launch_chain_sums(csr_ctx *c, const Prm &p, hipStream_t st) {
-    Scope sc(c, "chain_sums", st);
-    hipLaunchKernelGGL(k_chain_sums, dim3((int)c->chains.size()), dim3(1024), 0, st, p, c->dChainFirst, c->dChainNb);
+static int launch_chain_sums(csr_ctx *c, const Prm &p, hipStream_t st) {
+    return launch(c, "chain_sums", "k_chain_sums", k_chain_sums, dim3((int)c->chains.size()), dim3(1024), 0, st, p, c->dChainFirst,
+                  c->dChainNb);
 }
 // blocked copy of the filtered state from the reference-layout one (which the bit-exact state chain wrote), for `groups`
 // wavefront-groups from g0 on; profiled = false: the launch is not counted under a profile scope
@@ -174,14 +175,89 @@ static int import_xf_blocked(csr_ctx *c, const Prm &p, hipStream_t st, int64_t g
     float *natXf;
     CHECK(nat_array(c, CSR_ARR_XF, &natXf));
     const dim3 grid((int)(groups * (c->B / 32)));
-    if (profiled) {
-        Scope sc(c, "state_reblock_out", st);
-        hipLaunchKernelGGL(k_import_tiled<float2>, grid, dim3(256), 0, st, p, reinterpret_cast<const float2 *>(natXf), p.tXf, g0);
+    return launch(c, profiled ? "state_reblock_out" : nullptr, "k_import_tiled<float2>", k_import_tiled<float2>, grid, dim3(256), 0, st, p,
+                  reinterpret_cast<const float2 *>(natXf), p.tXf, g0);
+}
+
+// ---- which instance walks a chain ---------------------------------------------------------------------------------
+// dynamic LDS of the LDS-DMA ring of a chain policy
+template <class DCH>
+static constexpr size_t ring_bytes() { return sizeof(unsigned) * DMA_R * DCH::NW * 64; }
+struct SpecKernel {
+    void (*fn)(Prm) = nullptr;
+    size_t lds = 0;
+};
+// The speculative kernel of chain policy CH for the pass `p` describes (p.warm is set), and its dynamic LDS.  The first test that
+// holds decides, and the order matters where noted; pcq (per-chain base process noise) disables every LDS-DMA and
+// reference-layout-input form.
+// (round 6: the LDS-DMA ring and the reference-layout-input forms exist for F = [[1, f], [0, 1]] only -- what the reference's
+// constructMatrixF builds; any other `matrixF` runs the plain-load general instances: same results, fewer kernels to build)
+template <class CH>
+static SpecKernel spec_kernel(const csr_ctx *c, const Prm &p, bool pcq) {
+    if constexpr (CH::DMA) {
+        if (c->useDma) return {&k_chain_spec_dma<CH>, ring_bytes<CH>()};
+        return {&k_chain_spec<CH>, 0};
     } else {
-        hipLaunchKernelGGL(k_import_tiled<float2>, grid, dim3(256), 0, st, p, reinterpret_cast<const float2 *>(natXf), p.tXf, g0);
+        const uint32_t mm = p.flags & (F_LAMBDA | F_KAPPA | F_QSCALE);      // which per-bin multipliers the ring carries
+        if constexpr (CH::FAMILY == FAM_FWD_FUSED && CH::UNITF) {
+            using D0 = FwdTrendFusedDma<0, true>;
+            using D1 = FwdTrendFusedDma<1, true>;
+            using D2 = FwdTrendFusedDma<2, true>;
+            const size_t tl = sizeof(NatTilesFwd);
+            if (c->useDmaFused && c->useDmaWarm && p.natOut && !pcq && p.warm > 0) {
+                // reference-layout outputs: ring for the warm-up only, tile walker for the main phase
+                if (mm == 0) return {&k_chain_spec_dmawarm_natfwd<D0>, std::max(ring_bytes<D0>(), tl)};
+                if (mm == F_KAPPA) return {&k_chain_spec_dmawarm_natfwd<D1>, std::max(ring_bytes<D1>(), tl)};
+                return {&k_chain_spec_dmawarm_natfwd<D2>, std::max(ring_bytes<D2>(), tl)};
+            }
+            if (c->useDmaFused && !p.natOut && !pcq && p.ckptOut != nullptr) {
+                // warm-started ECM sweep (kappa only is the reference's default loop).  There is no instance without
+                // multipliers: mm == 0 runs <2> like everything that is not kappa alone
+                if (mm == F_KAPPA) return {&k_chain_spec_dma<D1, true>, ring_bytes<D1>()};
+                return {&k_chain_spec_dma<D2, true>, ring_bytes<D2>()};
+            }
+            if (c->useDmaFused && !p.natOut && !pcq) {
+                // ECM sweeps and other passes without reference-layout outputs: inputs through the LDS-DMA ring
+                if (mm == 0) return {&k_chain_spec_dma<D0>, ring_bytes<D0>()};
+                if (mm == F_KAPPA) return {&k_chain_spec_dma<D1>, ring_bytes<D1>()};
+                return {&k_chain_spec_dma<D2>, ring_bytes<D2>()};
+            }
+        }
+        if constexpr (CH::FAMILY == FAM_BWD_TREND && CH::UNITF) {
+            using DQ = BwdTrendDma<true, true>;
+            using DN = BwdTrendDma<false, true>;
+            // reference-layout inputs AND outputs, both through the LDS tiles (the forward pass wrote no blocked xf / Pf): wins over
+            // the ring warm-up below, whatever the window
+            if (p.natIn && p.natOut && !pcq) {
+                if (p.qFromMult) return {&k_smooth_natin<CH, false>, sizeof(NatTiles)};
+                return {&k_smooth_natin<CH, true>, sizeof(NatTiles)};
+            }
+            // smoother with reference-layout outputs: warm-up through the ring, from 64-bin blocks on
+            // (32-bin blocks: measured slower, 0.063 vs 0.057 ms -- the ring's fill and drain weigh more than they hide)
+            if (c->useDmaFused && c->useDmaWarm && p.natOut && !pcq && p.warm > 0 && c->B >= 64) {
+                if (p.qFromMult) return {&k_chain_spec_dmawarm_natbwd<DN>, std::max(ring_bytes<DN>(), sizeof(NatTiles))};
+                return {&k_chain_spec_dmawarm_natbwd<DQ>, std::max(ring_bytes<DQ>(), sizeof(NatTiles))};
+            }
+        }
+        if constexpr (CH::NATOUT || CH::NATOUT_FWD) {
+            if (p.natOut) {
+                if (pcq) return {&k_chain_spec<CH, true, true>, sizeof(NatTiles)};
+                return {&k_chain_spec<CH, true, false>, sizeof(NatTiles)};
+            }
+        }
+        if (pcq) return {&k_chain_spec<CH, false, true>, 0};
+        // (recording checkpoints has an instance of its own only without per-chain Q: pcq is tested first)
+        if (p.ckptOut != nullptr) return {&k_chain_spec<CH, false, false, true>, 0};
+        return {&k_chain_spec<CH, false, false>, 0};
     }
-    LAUNCH_CHECK("k_import_tiled_f2");
-    return 0;
+}
+// ... and the validation / fix-up kernel that goes with it
+template <class CH>
+static auto fix_kernel(const Prm &p, bool pcq) -> void (*)(Prm, int) {
+    if constexpr (CH::NATOUT || CH::NATOUT_FWD) {
+        if (p.natOut) return pcq ? &k_chain_fix<CH, true, true> : &k_chain_fix<CH, true, false>;
+    }
+    return pcq ? &k_chain_fix<CH, false, true> : &k_chain_fix<CH, false, false>;
 }
 
 // Speculative pass + validation/fix-up.  defer = true: launch the speculative pass and ONE validation pass and return
@@ -202,110 +278,17 @@ static int run_chain(csr_ctx *c, Prm p, const char *name, const char *fixName, i
     p.carryIn = c->carrySet[cset][0];
     p.carryOutA = c->carrySet[cset][1];
     take_pending_check(c, p);
-    {
-        Scope sc(c, name);
-        if constexpr (CH::DMA) {
-            if (c->useDma)
-                hipLaunchKernelGGL(k_chain_spec_dma<CH>, dim3(grid), dim3(64), sizeof(unsigned) * DMA_R * CH::NW * 64,
-                                   c->stream, p);
-            else hipLaunchKernelGGL(k_chain_spec<CH>, dim3(grid), dim3(64), 0, c->stream, p);
-        } else {
-            bool launched = false;
-            // (round 6: the LDS-DMA ring and the reference-layout-input forms exist for F = [[1, f], [0, 1]] only -- what the reference's
-            // constructMatrixF builds; any other `matrixF` runs the plain-load general instances: same results, fewer kernels to build)
-            if constexpr (CH::FAMILY == FAM_FWD_FUSED && CH::UNITF) {
-                // ECM sweeps and other passes without reference-layout outputs: inputs through the LDS-DMA ring
-                if (c->useDmaFused && c->useDmaWarm && p.natOut && !pcq && p.warm > 0) {
-                    // reference-layout outputs: ring for the warm-up only, tile walker for the main phase
-                    const uint32_t mm = p.flags & (F_LAMBDA | F_KAPPA | F_QSCALE);
-                    const size_t tl = sizeof(NatTilesFwd);
-                    if (mm == 0)
-                        hipLaunchKernelGGL((k_chain_spec_dmawarm_natfwd<FwdTrendFusedDma<0, CH::UNITF>>), dim3(grid), dim3(64),
-                                           std::max(sizeof(unsigned) * DMA_R * 4 * 64, tl), c->stream, p);
-                    else if (mm == F_KAPPA)
-                        hipLaunchKernelGGL((k_chain_spec_dmawarm_natfwd<FwdTrendFusedDma<1, CH::UNITF>>), dim3(grid), dim3(64),
-                                           std::max(sizeof(unsigned) * DMA_R * 5 * 64, tl), c->stream, p);
-                    else
-                        hipLaunchKernelGGL((k_chain_spec_dmawarm_natfwd<FwdTrendFusedDma<2, CH::UNITF>>), dim3(grid), dim3(64),
-                                           std::max(sizeof(unsigned) * DMA_R * 7 * 64, tl), c->stream, p);
-                    launched = true;
-                } else if (c->useDmaFused && !p.natOut && !pcq && p.ckptOut != nullptr) {
-                    // warm-started ECM sweep (kappa only is the reference's default loop)
-                    const uint32_t mm = p.flags & (F_LAMBDA | F_KAPPA | F_QSCALE);
-                    if (mm == F_KAPPA)
-                        hipLaunchKernelGGL((k_chain_spec_dma<FwdTrendFusedDma<1, CH::UNITF>, true>), dim3(grid), dim3(64),
-                                           sizeof(unsigned) * DMA_R * 5 * 64, c->stream, p);
-                    else
-                        hipLaunchKernelGGL((k_chain_spec_dma<FwdTrendFusedDma<2, CH::UNITF>, true>), dim3(grid), dim3(64),
-                                           sizeof(unsigned) * DMA_R * 7 * 64, c->stream, p);
-                    launched = true;
-                } else if (c->useDmaFused && !p.natOut && !pcq) {
-                    const uint32_t mm = p.flags & (F_LAMBDA | F_KAPPA | F_QSCALE);
-                    if (mm == 0)
-                        hipLaunchKernelGGL((k_chain_spec_dma<FwdTrendFusedDma<0, CH::UNITF>>), dim3(grid), dim3(64),
-                                           sizeof(unsigned) * DMA_R * 4 * 64, c->stream, p);
-                    else if (mm == F_KAPPA)
-                        hipLaunchKernelGGL((k_chain_spec_dma<FwdTrendFusedDma<1, CH::UNITF>>), dim3(grid), dim3(64),
-                                           sizeof(unsigned) * DMA_R * 5 * 64, c->stream, p);
-                    else
-                        hipLaunchKernelGGL((k_chain_spec_dma<FwdTrendFusedDma<2, CH::UNITF>>), dim3(grid), dim3(64),
-                                           sizeof(unsigned) * DMA_R * 7 * 64, c->stream, p);
-                    launched = true;
-                }
-            }
-            if constexpr (CH::FAMILY == FAM_BWD_TREND && CH::UNITF) {
-                if (p.natIn && p.natOut && !pcq) {
-                    // reference-layout inputs AND outputs, both through the LDS tiles (the forward pass wrote no blocked xf / Pf)
-                    if (p.qFromMult) hipLaunchKernelGGL((k_smooth_natin<CH, false>), dim3(grid), dim3(64), sizeof(NatTiles), c->stream, p);
-                    else hipLaunchKernelGGL((k_smooth_natin<CH, true>), dim3(grid), dim3(64), sizeof(NatTiles), c->stream, p);
-                    launched = true;
-                }
-                // smoother with reference-layout outputs: warm-up through the ring
-                // (32-bin blocks: measured slower, 0.063 vs 0.057 ms -- the ring's fill and drain weigh more than they hide)
-                if (!launched && c->useDmaFused && c->useDmaWarm && p.natOut && !pcq && p.warm > 0 && c->B >= 64) {
-                    if (p.qFromMult)
-                        hipLaunchKernelGGL((k_chain_spec_dmawarm_natbwd<BwdTrendDma<false, CH::UNITF>>), dim3(grid), dim3(64),
-                                           std::max(sizeof(unsigned) * DMA_R * 6 * 64, sizeof(NatTiles)), c->stream, p);
-                    else
-                        hipLaunchKernelGGL((k_chain_spec_dmawarm_natbwd<BwdTrendDma<true, CH::UNITF>>), dim3(grid), dim3(64),
-                                           std::max(sizeof(unsigned) * DMA_R * 10 * 64, sizeof(NatTiles)), c->stream, p);
-                    launched = true;
-                }
-            }
-            if constexpr (CH::NATOUT || CH::NATOUT_FWD) {
-                if (!launched && p.natOut) {
-                    if (pcq) hipLaunchKernelGGL((k_chain_spec<CH, true, true>), dim3(grid), dim3(64), sizeof(NatTiles), c->stream, p);
-                    else hipLaunchKernelGGL((k_chain_spec<CH, true, false>), dim3(grid), dim3(64), sizeof(NatTiles), c->stream, p);
-                    launched = true;
-                }
-            }
-            if (!launched) {
-                if (pcq) hipLaunchKernelGGL((k_chain_spec<CH, false, true>), dim3(grid), dim3(64), 0, c->stream, p);
-                else if (p.ckptOut != nullptr) hipLaunchKernelGGL((k_chain_spec<CH, false, false, true>), dim3(grid), dim3(64), 0, c->stream, p);
-                else hipLaunchKernelGGL((k_chain_spec<CH, false, false>), dim3(grid), dim3(64), 0, c->stream, p);
-            }
-        }
-    }
-    LAUNCH_CHECK(name);
+    const SpecKernel spec = spec_kernel<CH>(c, p, pcq);
+    CHECK(launch(c, name, name, spec.fn, dim3(grid), dim3(64), spec.lds, c->stream, p));
     int which = 0;
     unsigned int *const cnt = reinterpret_cast<unsigned int *>(c->dMail);
-    auto launch_fix = [&](unsigned int *passCounter) {
-        Scope sc(c, fixName);
+    void (*const fix)(Prm, int) = fix_kernel<CH>(p, pcq);
+    auto launch_fix = [&](unsigned int *passCounter) -> int {
         p.rerunCountPass = passCounter;
-        bool launched = false;
-        if constexpr (CH::NATOUT || CH::NATOUT_FWD) {
-            if (p.natOut) {
-                if (pcq) hipLaunchKernelGGL((k_chain_fix<CH, true, true>), dim3(grid), dim3(64), 0, c->stream, p, which);
-                else hipLaunchKernelGGL((k_chain_fix<CH, true, false>), dim3(grid), dim3(64), 0, c->stream, p, which);
-                launched = true;
-            }
-        }
-        if (!launched) {
-            if (pcq) hipLaunchKernelGGL((k_chain_fix<CH, false, true>), dim3(grid), dim3(64), 0, c->stream, p, which);
-            else hipLaunchKernelGGL((k_chain_fix<CH, false, false>), dim3(grid), dim3(64), 0, c->stream, p, which);
-        }
+        CHECK(launch(c, fixName, fixName, fix, dim3(grid), dim3(64), 0, c->stream, p, which));
         c->rs.fix_launches++;
         which ^= 1;
+        return 0;
     };
     if (defer && c->nPasses[stage] <= 1) {
         // clean so far: no validation kernel -- the next speculative kernel (or read_mail) checks this stage's carries
@@ -323,8 +306,7 @@ static int run_chain(csr_ctx *c, Prm p, const char *name, const char *fixName, i
         // nothing (checked at the next settle point through its own counter)
         p.debugForce = 0;
         const int np = std::max(1, std::min(MAX_DEFER_PASSES, c->nPasses[stage]));
-        for (int j = 0; j < np; ++j) launch_fix(cnt + MAIL_PASS0 + 4 * stage + j);
-        LAUNCH_CHECK(fixName);
+        for (int j = 0; j < np; ++j) CHECK(launch_fix(cnt + MAIL_PASS0 + 4 * stage + j));
         c->launchedPasses[stage] = np;
         return 0;
     }
@@ -335,8 +317,7 @@ static int run_chain(csr_ctx *c, Prm p, const char *name, const char *fixName, i
     int burst = 1;
     for (int64_t it = 0; it <= c->NB + 1; ++it) {
         p.debugForce = 0;
-        for (int rep = 0; rep < burst; ++rep) launch_fix(cnt + MAIL_DUMMY);
-        LAUNCH_CHECK(fixName);
+        for (int rep = 0; rep < burst; ++rep) CHECK(launch_fix(cnt + MAIL_DUMMY));
         CHECK(read_mail(c, MAIL_HDR));
         const unsigned int fresh = take_fresh(c, stage);
         if (c->dbgLog) fprintf(stderr, "[csr] %s iter %lld reruns %u\n", fixName, (long long)it, fresh);
@@ -355,6 +336,15 @@ static int run_chain(csr_ctx *c, Prm p, const char *name, const char *fixName, i
         burst = it == 0 ? 2 : std::min(32, burst * 2);
     }
     return fail("%s: speculative fix-up did not reach a fixed point", name);
+}
+
+// The chain policy of the model: levelTrend with F = [[1, f], [0, 1]] runs TrendT<true>, any other levelTrend TrendT<false>, the
+// level model Level
+template <template <bool> class TrendT, class Level>
+static int run_policy(csr_ctx *c, const Prm &p, const char *name, const char *fixName, int stage, bool defer) {
+    if (c->mdl.state_dim != 2) return run_chain<Level>(c, p, name, fixName, stage, defer);
+    if (unit_f(p)) return run_chain<TrendT<true>>(c, p, name, fixName, stage, defer);
+    return run_chain<TrendT<false>>(c, p, name, fixName, stage, defer);
 }
 
 // ---- warm-started speculation of the ECM sweeps (Prm::ckptIn) -----------------------------------------------------
@@ -460,14 +450,13 @@ static int need_blocked(csr_ctx *c, std::initializer_list<int> ids, const unsign
         if (c->where[id].blocked) continue;
         const float *src = c->nat[id];
         if (id == CSR_ARR_XF || id == CSR_ARR_XS)
-            hipLaunchKernelGGL(k_import_tiled<float2>, grid, dim3(256), 0, c->stream, p, reinterpret_cast<const float2 *>(src),
-                               id == CSR_ARR_XF ? p.tXf : p.tXs, (int64_t)0);
+            CHECK(launch(c, nullptr, "k_import_tiled<float2>", k_import_tiled<float2>, grid, dim3(256), 0, c->stream, p,
+                         reinterpret_cast<const float2 *>(src), id == CSR_ARR_XF ? p.tXf : p.tXs, (int64_t)0));
         else
-            hipLaunchKernelGGL(k_import_tiled<float4>, grid, dim3(256), 0, c->stream, p, reinterpret_cast<const float4 *>(src),
-                               id == CSR_ARR_PF ? p.tPf : (id == CSR_ARR_PS ? p.tPs : p.tLag), (int64_t)0);
+            CHECK(launch(c, nullptr, "k_import_tiled<float4>", k_import_tiled<float4>, grid, dim3(256), 0, c->stream, p,
+                         reinterpret_cast<const float4 *>(src), id == CSR_ARR_PF ? p.tPf : (id == CSR_ARR_PS ? p.tPs : p.tLag), (int64_t)0));
         if (active == nullptr) c->where[id].blocked = true;
     }
-    LAUNCH_CHECK("k_import_tiled");
     return 0;
 }
 
@@ -491,27 +480,20 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
     CHECK(nat_array(c, CSR_ARR_XF, &natXf));
     c->sbp.active = false;
     if (!resume && !(c->gainNat && c->natSZValid)) {
-        Scope sc(c, "state_records_natural");
         ExpList L;
         memset(&L, 0, sizeof(L));
         // the gain records of this pass unless the covariance chain wrote them in the reference layout itself (forward_impl); the
         // statistics records {S0, zbar} only when the statistics changed since they were last converted (csr_batch_stats): the
         // sweeps of an ECM iteration share them
-        L.count = 0;
-        if (!c->gainNat) {
-            L.count = 1;
-            L.d[0].src = reinterpret_cast<const float *>(p.tXin); L.d[0].dst = reinterpret_cast<float *>(c->sbNatGain); L.d[0].E = 4; L.d[0].n = 4;
-        }
+        if (!c->gainNat) exp_add(L, reinterpret_cast<const float *>(p.tXin), reinterpret_cast<float *>(c->sbNatGain), 4, 4);
         Prm pe = p;
         if (!c->natSZValid) {
-            ExpDesc &e = L.d[L.count++];
-            e.src = reinterpret_cast<const float *>(p.tSZ); e.dst = reinterpret_cast<float *>(c->sbNatSZ); e.E = 4; e.n = 4;
+            exp_add(L, reinterpret_cast<const float *>(p.tSZ), reinterpret_cast<float *>(c->sbNatSZ), 4, 4);
             pe.chainActive = nullptr;       // the statistics of EVERY chain (csr_batch_stats computed them all), whatever this pass masks
             c->natSZValid = true;
         }
-        hipLaunchKernelGGL(k_export_tiled, tile_grid(c), dim3(256), 0, c->stream, pe, L);
+        CHECK(launch(c, "state_records_natural", "k_export_tiled (state records)", k_export_tiled, tile_grid(c), dim3(256), 0, c->stream, pe, L));
     }
-    LAUNCH_CHECK("k_export_tiled (state records)");
     if (earlyExports && !resume) CHECK(early_cov_exports(c, p, flags, true));
     Prm q = p;
     q.B = v.B; q.NB = v.NB; q.NG = v.NG; q.blk = v.blk; q.blkChain = v.blkChain;
@@ -523,19 +505,14 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
     const int mode = unit_f(p) ? (p.F01 == 1.0 ? 2 : 1) : 0;     // F01 == 1: the walker's predicted level is one float32 add
     const int grid = (int)((v.NB + 3) / 4);
     q.sbDbg = nullptr;
-    auto launch = [&](int which, int fix) {
-        float2 *xf = reinterpret_cast<float2 *>(natXf);
-        if (fix) {        // repair passes in delta form (k_sb_delta)
-            const int spec = (c->sbAdvMin << 8) | (c->sbAdvFrom << 16);
-            if (mode == 2) hipLaunchKernelGGL(k_sb_delta<2>, dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf, which, spec);
-            else if (mode == 1) hipLaunchKernelGGL(k_sb_delta<1>, dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf, which, spec);
-            else hipLaunchKernelGGL(k_sb_delta<0>, dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf, which, spec);
-            return;
-        }
-        if (mode == 2) hipLaunchKernelGGL(k_sb_sys<2>, dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf);
-        else if (mode == 1) hipLaunchKernelGGL(k_sb_sys<1>, dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf);
-        else hipLaunchKernelGGL(k_sb_sys<0>, dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf);
-    };
+    // the three forms of the chain, each in the instance of this pass's `mode`
+    using SysFn = void (*)(Prm, const float4 *, const float4 *, float2 *);
+    using DeltaFn = void (*)(Prm, const float4 *, const float4 *, float2 *, int, int);
+    using AsyncFn = void (*)(Prm, const float4 *, const float4 *, float2 *, SbAsync);
+    const SysFn sysFns[3] = {&k_sb_sys<0>, &k_sb_sys<1>, &k_sb_sys<2>};
+    const DeltaFn deltaFns[3] = {&k_sb_delta<0>, &k_sb_delta<1>, &k_sb_delta<2>};
+    const AsyncFn asyncFns[3] = {&k_sb_async<0, false>, &k_sb_async<1, false>, &k_sb_async<2, false>};
+    float2 *const xf = reinterpret_cast<float2 *>(natXf);
     bool done = false;
     if (c->sbAsync) {
         // the whole chain in one launch, no barrier between passes (k_sb_async); a bail-out (a bounded wait ran out) falls
@@ -558,19 +535,14 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
         }
         if (!resume) {
             HIPOK(hipMemsetAsync(v.pub, 0, sizeof(unsigned long long) * (size_t)(2 * v.NB + 2), c->stream));
-            Scope sc(c, "fwd_state_chain");
-            float2 *xf = reinterpret_cast<float2 *>(natXf);
             // (the repair runs' LDS ring: > 64 KB of dynamic LDS has to be asked for once per kernel)
-            using KFn = void (*)(Prm, const float4 *, const float4 *, float2 *, SbAsync);
-            const KFn fns[3] = {&k_sb_async<0, false>, &k_sb_async<1, false>, &k_sb_async<2, false>};
-            const int which = mode;
-            if (!c->sbAsyncLdsRaised[which]) {
-                HIPOK(hipFuncSetAttribute(reinterpret_cast<const void *>(fns[which]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_ASYNC_LDS));
-                c->sbAsyncLdsRaised[which] = true;
+            if (!c->sbAsyncLdsRaised[mode]) {
+                HIPOK(hipFuncSetAttribute(reinterpret_cast<const void *>(asyncFns[mode]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_ASYNC_LDS));
+                c->sbAsyncLdsRaised[mode] = true;
             }
-            hipLaunchKernelGGL(fns[which], dim3(grid), dim3(256), SB_ASYNC_LDS, c->stream, q, c->sbNatGain, c->sbNatSZ, xf, a);
+            CHECK(launch(c, "fwd_state_chain", "k_sb_async", asyncFns[mode], dim3(grid), dim3(256), SB_ASYNC_LDS, c->stream, q, c->sbNatGain,
+                         c->sbNatSZ, xf, a));
         }
-        LAUNCH_CHECK("k_sb_async");
         if (phase == 1) {
             c->sbp.active = true;
             c->sbp.p = p;
@@ -592,22 +564,21 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
             if (resume && c->tail) HIPOK(hipStreamSynchronize(c->tail));
         }
     }
-    if (!done) {
-        Scope sc(c, "fwd_state_chain");
-        launch(0, 0);
-    }
-    LAUNCH_CHECK("k_sb_sys");
+    if (!done)
+        CHECK(launch(c, "fwd_state_chain", "k_sb_sys", sysFns[mode], dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf));
     int which = 0, burst = 2;
+    const int adv = (c->sbAdvMin << 8) | (c->sbAdvFrom << 16);
     for (int64_t it = 0; it <= v.NB + 1 && !done; ++it) {
         {
+            // repair passes in delta form (k_sb_delta): a burst of them under ONE profile scope
             Scope sc(c, "fwd_state_fix");
             for (int rep = 0; rep < burst; ++rep) {
-                launch(which, 1);
+                CHECK(launch(c, nullptr, "k_sb_delta", deltaFns[mode], dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf,
+                             which, adv));
                 which ^= 1;
                 c->rs.fix_launches++;
             }
         }
-        LAUNCH_CHECK("k_sb_sys (repair)");
         CHECK(read_mail(c, MAIL_HDR));
         const unsigned int fresh = take_fresh(c, ST_X);
         if (c->dbgLog) fprintf(stderr, "[csr] fwd_state_fix (systolic superblocks) iter %lld reruns %u\n", (long long)it, fresh);
@@ -624,13 +595,14 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
 // Join the side stream.  The per-chain sums (22 workgroups of 1024 threads, ~10 us) run on the main stream after the
 // join: left on the side stream behind the epilogue they starve for whole-CU slots while a bandwidth-bound kernel of the
 // main stream keeps the chip full (measured 0.64 ms instead of 0.01).
-static void join_side(csr_ctx *c) {
+static int join_side(csr_ctx *c) {
     if (c->sidePending) {
         (void)hipStreamWaitEvent(c->stream, c->evJoin, 0);
         c->sidePending = false;
-        if (c->sideSumsDone) { c->sideSumsDone = false; return; }    // the side stream ran the per-chain sums itself
-        launch_chain_sums(c, c->sidePrm, c->stream);
+        if (c->sideSumsDone) { c->sideSumsDone = false; return 0; }    // the side stream ran the per-chain sums itself
+        CHECK(launch_chain_sums(c, c->sidePrm, c->stream));
     }
+    return 0;
 }
 
 // NIS/NLL epilogue; side = true runs it on the side stream (forked after the state chain) so that it overlaps the
@@ -638,7 +610,7 @@ static void join_side(csr_ctx *c) {
 static int forward_epilogue(csr_ctx *c, const Prm &p, bool side) {
     hipStream_t st = c->stream;
     if (side) {
-        join_side(c);
+        CHECK(join_side(c));
         CHECK(fork_side(c, c->evFork));
         st = c->side;
     }
@@ -649,9 +621,7 @@ static int forward_epilogue(csr_ctx *c, const Prm &p, bool side) {
         c->sidePrm = p;                 // k_chain_sums follows on the main stream at the join
         return 0;
     }
-    launch_chain_sums(c, p, st);
-    LAUNCH_CHECK("k_chain_sums");
-    return 0;
+    return launch_chain_sums(c, p, st);
 }
 
 // main stream waits for the early covariance exports of the side stream (early_cov_exports)
@@ -678,10 +648,9 @@ static int launch_pn_fill(csr_ctx *c, const Prm &p, float *dst, hipStream_t st) 
     const unsigned grid = (unsigned)std::min<int64_t>((c->Npad + 255) / 256, 8192);
     float q[4];
     pn_fill_values(c, p, q);
-    Scope sc(c, "export_natural", st);
-    if (nm == 4) hipLaunchKernelGGL(k_fill_rows<4>, dim3(grid), dim3(256), 0, st, dst, c->Npad, q[0], q[1], q[2], q[3]);
-    else hipLaunchKernelGGL(k_fill_rows<1>, dim3(grid), dim3(256), 0, st, dst, c->Npad, q[0], 0.f, 0.f, 0.f);
-    LAUNCH_CHECK("k_fill_rows");
+    // (a level model's row is q[0] alone: pn_fill_values left the other three at zero)
+    void (*const kernel)(float *, int64_t, float, float, float, float) = nm == 4 ? &k_fill_rows<4> : &k_fill_rows<1>;
+    CHECK(launch(c, "export_natural", "k_fill_rows", kernel, dim3(grid), dim3(256), 0, st, dst, c->Npad, q[0], q[1], q[2], q[3]));
     memcpy(c->pnFillQ, q, sizeof(q));
     c->pnFillValid = true;
     return 0;
@@ -711,25 +680,13 @@ static int early_cov_exports(csr_ctx *c, const Prm &p, uint32_t flags, bool with
     if (doPf || convQ) {
         ExpList L;
         memset(&L, 0, sizeof(L));
-        L.count = 0;
-        if (doPf) {
-            L.count = 1;
-            L.d[0].src = reinterpret_cast<const float *>(p.tPf); L.d[0].dst = dstPf; L.d[0].E = 4; L.d[0].n = nm;
-        }
+        if (doPf) exp_add(L, reinterpret_cast<const float *>(p.tPf), dstPf, 4, nm);
         if (convQ) {            // (as export_impl describes it)
-            ExpDesc &e = L.d[L.count++];
-            e.src = constFlags ? nullptr : reinterpret_cast<const float *>(p.tQ); e.dst = dstPn; e.E = 4; e.n = nm; e.skipLast = 1;
-            if (constFlags) {
-                e.cval[0] = (float)p.Q00;
-                e.cval[1] = c->mdl.state_dim == 2 ? (float)p.Q01 : 0.f;
-                e.cval[2] = c->mdl.state_dim == 2 ? (float)p.Q10 : 0.f;
-                e.cval[3] = c->mdl.state_dim == 2 ? (float)p.Q11 : 0.f;
-            }
+            ExpDesc &e = exp_add(L, constFlags ? nullptr : reinterpret_cast<const float *>(p.tQ), dstPn, 4, nm, 1);
+            if (constFlags) pn_fill_values(c, p, e.cval);
         }
-        Scope sc(c, "export_natural", c->side);
-        hipLaunchKernelGGL(k_export_tiled, tile_grid(c), dim3(256), 0, c->side, p, L);
+        CHECK(launch(c, "export_natural", "k_export_tiled (early Pf)", k_export_tiled, tile_grid(c), dim3(256), 0, c->side, p, L));
     }
-    LAUNCH_CHECK("k_export_tiled (early Pf)");
     if (doPf) c->where[CSR_ARR_PF].nat = true;
     if (convQ) { produced(c, {CSR_ARR_PNOISE}, W_BLOCKED | W_NAT); c->pnFillValid = false; }
     if (fill) CHECK(launch_pn_fill(c, p, dstPn, c->side));
@@ -770,10 +727,8 @@ static int forward_impl(csr_ctx *c, const FwdPass &pass) {
     c->last.fwd = pass;
     const bool seq = (flags & F_APN) && !(flags & F_QSCALE);
     if (seq) {
-        Scope sc(c, "fwd_apn_sequential");
-        hipLaunchKernelGGL(k_fwd_apn, dim3(((int)c->chains.size() + 63) / 64), dim3(64), 0, c->stream, p, c->dChainFirst,
-                           c->dChainNb);
-        LAUNCH_CHECK("k_fwd_apn");
+        CHECK(launch(c, "fwd_apn_sequential", "k_fwd_apn", k_fwd_apn, dim3(((int)c->chains.size() + 63) / 64), dim3(64), 0, c->stream, p,
+                     c->dChainFirst, c->dChainNb));
     } else {
         bool dP = defer && c->optimistic[ST_P], dX = defer && c->optimistic[ST_X];
         bool nisInChain = false;
@@ -832,9 +787,7 @@ static int forward_impl(csr_ctx *c, const FwdPass &pass) {
                     produced(c, {CSR_ARR_XF, CSR_ARR_PF}, W_NAT);
                 }
             }
-            if (c->mdl.state_dim == 2 && unit_f(p)) CHECK(run_chain<FwdTrendFusedT<true>>(c, p, "fwd_chain", "fwd_fix", ST_P, dP));
-            else if (c->mdl.state_dim == 2) CHECK(run_chain<FwdTrendFused>(c, p, "fwd_chain", "fwd_fix", ST_P, dP));
-            else CHECK(run_chain<FwdLevelFused>(c, p, "fwd_chain", "fwd_fix", ST_P, dP));
+            CHECK((run_policy<FwdTrendFusedT, FwdLevelFused>(c, p, "fwd_chain", "fwd_fix", ST_P, dP)));
             ws_launched(c, p, true);
             p.ckptIn = nullptr; p.ckptOut = nullptr; p.ckptSaveWarm = 0;
             c->lastFwdWindow = c->fwdWindow;
@@ -869,19 +822,13 @@ static int forward_impl(csr_ctx *c, const FwdPass &pass) {
                 }
                 c->gainNat = true;
             }
-            if (unit_f(p)) CHECK(run_chain<FwdPTrendT<true>>(c, pc, "fwd_cov_chain", "fwd_cov_fix", ST_P, dP));
-            else CHECK(run_chain<FwdPTrend>(c, pc, "fwd_cov_chain", "fwd_cov_fix", ST_P, dP));
+            CHECK((run_policy<FwdPTrendT, FwdPLevel>(c, pc, "fwd_cov_chain", "fwd_cov_fix", ST_P, dP)));     // (state_dim is 2 here)
             if (seqX) {
                 // bit-exact mode: the state recursion cannot be validated speculatively in reasonable time (see
                 // k_state_seq_trend) -- one wavefront per chain runs it sequentially on the validated gains
-                Scope sc(c, "fwd_state_seq");
-                if (p.F00 == 1.0 && p.F10 == 0.0 && p.F11 == 1.0)
-                    hipLaunchKernelGGL(k_state_seq_trend<true>, dim3((unsigned)c->chains.size()), dim3(64), 0, c->stream, p,
-                                       c->dChainFirst, c->dChainNb);
-                else
-                    hipLaunchKernelGGL(k_state_seq_trend<false>, dim3((unsigned)c->chains.size()), dim3(64), 0, c->stream, p,
-                                       c->dChainFirst, c->dChainNb);
-                LAUNCH_CHECK("k_state_seq_trend");
+                void (*const kernel)(Prm, const int64_t *, const int64_t *) = unit_f(p) ? &k_state_seq_trend<true> : &k_state_seq_trend<false>;
+                CHECK(launch(c, "fwd_state_seq", "k_state_seq_trend", kernel, dim3((unsigned)c->chains.size()), dim3(64), 0, c->stream, p,
+                             c->dChainFirst, c->dChainNb));
                 dX = false;
             } else {
                 // (the early covariance exports fork off behind the state chain's own record conversion)
@@ -896,14 +843,13 @@ static int forward_impl(csr_ctx *c, const FwdPass &pass) {
         if (wantD && nisInChain) {
             // the chain kernels left D and the per-block sums: only the per-chain reduction follows -- beside the smoother (side
             // stream) when one follows, so that its few microseconds leave the critical path
-            join_side(c);
+            CHECK(join_side(c));
             hipStream_t st = c->stream;
             if (side && c->deferEnabled) {
                 CHECK(fork_side(c, c->evFork));
                 st = c->side;
             }
-            launch_chain_sums(c, p, st);
-            LAUNCH_CHECK("k_chain_sums");
+            CHECK(launch_chain_sums(c, p, st));
             if (st == c->side) {
                 HIPOK(hipEventRecord(c->evJoin, c->side));
                 c->sidePending = true;
@@ -970,15 +916,9 @@ static int backward_impl(csr_ctx *c, const BwdPass &pass) {
         c->bwdWindow = w;
     }
     struct BwdWindowReset { csr_ctx *c; ~BwdWindowReset() { c->bwdWindow = nullptr; } } bwdWindowReset{c};
-    if (p.qFromKappa && !natOut) {
-        if (c->mdl.state_dim == 2 && unit_f(p)) CHECK(run_chain<BwdTrendQ2T<true>>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
-        else if (c->mdl.state_dim == 2) CHECK(run_chain<BwdTrendQ2>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
-        else CHECK(run_chain<BwdLevelQ2>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
-    } else if (p.qFromKappa) {
-        return fail("internal: compact process noise is only produced by ECM sweeps (no reference-layout outputs)");
-    } else if (c->mdl.state_dim == 2 && unit_f(p)) CHECK(run_chain<BwdTrendT<true>>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
-    else if (c->mdl.state_dim == 2) CHECK(run_chain<BwdTrend>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
-    else CHECK(run_chain<BwdLevel>(c, p, "bwd_chain", "bwd_fix", ST_B, dB));
+    if (p.qFromKappa && natOut) return fail("internal: compact process noise is only produced by ECM sweeps (no reference-layout outputs)");
+    if (p.qFromKappa) CHECK((run_policy<BwdTrendQ2T, BwdLevelQ2>(c, p, "bwd_chain", "bwd_fix", ST_B, dB)));
+    else CHECK((run_policy<BwdTrendT, BwdLevel>(c, p, "bwd_chain", "bwd_fix", ST_B, dB)));
     ws_launched(c, p, false);
     c->lastBwdWindow = c->bwdWindow;
     if (dB) c->last.bwdPending = true;
@@ -1041,7 +981,7 @@ static int check_stages(csr_ctx *c) {
 }
 
 static int settle(csr_ctx *c) {
-    join_side(c);
+    CHECK(join_side(c));
     join_pf(c);
     if (!anything_pending(c)) return 0;
     CHECK(read_mail(c, c->mailBytes));
@@ -1254,9 +1194,8 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
                     } else {
                         Prm p = c->p;
                         p.chainActive = c->dActive;
-                        Scope sc(c, "ecm_commit_kappa");
-                        hipLaunchKernelGGL(k_copy_active_f32, dim3(grid_slots(c)), dim3(256), 0, c->stream, p, iterKappa, c->p.tKap);
-                        LAUNCH_CHECK("k_copy_active_f32");
+                        CHECK(launch(c, "ecm_commit_kappa", "k_copy_active_f32", k_copy_active_f32, dim3(grid_slots(c)), dim3(256), 0, c->stream, p,
+                                     iterKappa, c->p.tKap));
                     }
                 }
                 for (int i = 0; i < nc; ++i) nll[i] = mailSums[nc + i];
@@ -1269,16 +1208,10 @@ extern "C" int csr_batch_ecm_masked(csr_ctx *c, const csr_ecm_cfg *cfg, uint32_t
                     Prm p = c->p;
                     p.flags = fl;
                     p.chainActive = c->dActive;
-                    if (cfg->use_lambda) {
-                        Scope sc(c, "estep_lambda");
-                        hipLaunchKernelGGL(k_estep_lambda, dim3(grid_slots(c)), dim3(256), 0, c->stream, p);
-                        LAUNCH_CHECK("k_estep_lambda");
-                    }
-                    if (cfg->use_kappa) {
-                        Scope sc(c, "estep_kappa");
-                        hipLaunchKernelGGL(k_estep_kappa, dim3(grid_slots(c)), dim3(256), 0, c->stream, p);
-                        LAUNCH_CHECK("k_estep_kappa");
-                    }
+                    if (cfg->use_lambda)
+                        CHECK(launch(c, "estep_lambda", "k_estep_lambda", k_estep_lambda, dim3(grid_slots(c)), dim3(256), 0, c->stream, p));
+                    if (cfg->use_kappa)
+                        CHECK(launch(c, "estep_kappa", "k_estep_kappa", k_estep_kappa, dim3(grid_slots(c)), dim3(256), 0, c->stream, p));
                 }
                 CHECK(forward_impl(c, {.flags = fl | F_NLL, .wantD = true, .active = c->dActive, .defer = true}));    // pyx:8300
                 CHECK(read_sums(c, nullptr, nll.data()));
@@ -1343,11 +1276,7 @@ extern "C" int csr_batch_sums(csr_ctx *c, double *sum_d, double *sum_nll) {
 
 static int flush_export(csr_ctx *c, ExpList &L) {
     if (L.count == 0) return 0;
-    {
-        Scope sc(c, "export_natural");
-        hipLaunchKernelGGL(k_export_tiled, tile_grid(c), dim3(256), 0, c->stream, c->p, L);
-    }
-    LAUNCH_CHECK("k_export_tiled");
+    CHECK(launch(c, "export_natural", "k_export_tiled", k_export_tiled, tile_grid(c), dim3(256), 0, c->stream, c->p, L));
     L.count = 0;
     return 0;
 }
@@ -1358,9 +1287,7 @@ static int need_natural(csr_ctx *c, ExpList &L, int id, const float *src, int E,
     if (L.count == 8) CHECK(flush_export(c, L));       // one launch converts up to eight arrays
     float *dst;
     CHECK(nat_array(c, id, &dst));
-    ExpDesc &d = L.d[L.count++];
-    memset(&d, 0, sizeof(d));
-    d.src = src; d.dst = dst; d.E = E; d.n = n; d.skipLast = skipLast;
+    exp_add(L, src, dst, E, n, skipLast);
     c->where[id].nat = keep;
     return 0;
 }
@@ -1377,7 +1304,6 @@ static int launch_resid(csr_ctx *c, int64_t off, int64_t nb, bool foldCheck) {
     float *xs, *res;
     CHECK(nat_array(c, CSR_ARR_XS, &xs));
     CHECK(nat_array(c, CSR_ARR_RESID, &res));
-    Scope sc(c, "residuals");
     Prm pr = c->p;
     pr.xTolUlps = c->xTolUlps;
     pr.prevKind = CK_NONE;
@@ -1387,20 +1313,19 @@ static int launch_resid(csr_ctx *c, int64_t off, int64_t nb, bool foldCheck) {
     if (pr.bg) pr.bg += off;
     xs += off * d;
     res += off * c->m;
+    // K 64-bin sub-tiles per workgroup, rows of m floats padded by `padRows` rows in LDS: the 16-byte form (m a multiple of 4)
+    // with K = 2 (measured best: 0.665 vs 0.684 ms with 1 or 4, round 3) while its tile fits 64 KB, else with K = 1
+    void (*kernel)(Prm, const float *, int, float *, int64_t) = &k_resid;
+    int K = 1, padRows = 1;
     if ((c->m & 3) == 0) {
-        constexpr int K = 2;        // 64-bin sub-tiles per workgroup: 2 measured best (0.665 vs 0.684 ms with 1 or 4, round 3)
-        const size_t lds = sizeof(float) * (size_t)(K * 64 + 4) * c->m;
-        const dim3 grid((unsigned)((nb + K * 64 - 1) / (K * 64)));
-        if (lds <= 65536)
-            hipLaunchKernelGGL(k_resid_v4<2>, grid, dim3(256), lds, c->stream, pr, xs, d, res, nb);
-        else
-            hipLaunchKernelGGL(k_resid_v4<1>, dim3((unsigned)((nb + 63) / 64)), dim3(256), sizeof(float) * 68 * c->m,
-                               c->stream, pr, xs, d, res, nb);
-    } else
-        hipLaunchKernelGGL(k_resid, dim3((int)((nb + 63) / 64)), dim3(256), sizeof(float) * 65 * c->m, c->stream,
-                           pr, xs, d, res, nb);
-    LAUNCH_CHECK("k_resid");
-    return 0;
+        padRows = 4;
+        const bool two = sizeof(float) * (size_t)(2 * 64 + 4) * c->m <= 65536;
+        K = two ? 2 : 1;
+        kernel = two ? &k_resid_v4<2> : &k_resid_v4<1>;
+    }
+    const size_t lds = sizeof(float) * (size_t)(K * 64 + padRows) * c->m;
+    const dim3 grid((unsigned)((nb + K * 64 - 1) / (K * 64)));
+    return launch(c, "residuals", "k_resid", kernel, grid, dim3(256), lds, c->stream, pr, xs, d, res, nb);
 }
 
 static int export_impl(csr_ctx *c, uint32_t what) {
@@ -1417,7 +1342,7 @@ static int export_impl(csr_ctx *c, uint32_t what) {
                        c->Npad >= ((int64_t)4 << 20);
     // D is current in the reference layout (the epilogue wrote it there itself): nothing in this export depends on the side
     // stream; it is joined at the next settle point (sums, download, device_array, synchronize)
-    if (!lateD && !natD) join_side(c);
+    if (!lateD && !natD) CHECK(join_side(c));
     if (what & CSR_EXPORT_FORWARD) {
         if (!c->haveFwd) return fail("no forward results to export");
         join_pf(c);
@@ -1437,13 +1362,8 @@ static int export_impl(csr_ctx *c, uint32_t what) {
         } else {
             CHECK(need_natural(c, L, CSR_ARR_PNOISE, constQ ? nullptr : (const float *)p.tQ, 4, nm, 1, false));
             c->pnFillValid = false;
-        }
-        if (constQ && p.chainQ != nullptr) {
-            ExpDesc &e = L.d[L.count - 1];
-            e.cval[0] = (float)p.Q00;
-            e.cval[1] = d == 2 ? (float)p.Q01 : 0.f;
-            e.cval[2] = d == 2 ? (float)p.Q10 : 0.f;
-            e.cval[3] = d == 2 ? (float)p.Q11 : 0.f;
+            // (constant flags with per-chain base matrices: the descriptor just queued carries the model's row, as early_cov_exports' does)
+            if (constQ) pn_fill_values(c, p, L.d[L.count - 1].cval);
         }
     }
     if (what & (CSR_EXPORT_SMOOTH | CSR_EXPORT_RESID)) {
@@ -1459,7 +1379,7 @@ static int export_impl(csr_ctx *c, uint32_t what) {
     CHECK(flush_export(c, L));
     if (what & CSR_EXPORT_RESID) CHECK(launch_resid(c, 0, c->Npad, true));
     if (lateD) {
-        join_side(c);
+        CHECK(join_side(c));
         CHECK(need_natural(c, L, CSR_ARR_D, p.tD, 1, 1, 0, false));
         CHECK(flush_export(c, L));
     }
@@ -1614,8 +1534,7 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     HIPOK(hipStreamWaitEvent(mainStream, c->evTailJoin, 0));
     Prm ps = pf;
     ps.chainActive = nullptr;
-    launch_chain_sums(c, ps, c->stream);
-    LAUNCH_CHECK("k_chain_sums");
+    CHECK(launch_chain_sums(c, ps, c->stream));
     replay_covers_every_chain(c);
     if (c->last.bwdPending) reexport_on_replay(c, what);
     c->rs.tail_groups += phase;
@@ -1701,12 +1620,8 @@ extern "C" int csr_batch_synthesize(csr_ctx *c, uint64_t seed) {
         }
     }
     HIPOK(hipMemcpy(c->dLatent, lat.data(), sizeof(float) * c->Npad, hipMemcpyHostToDevice));
-    {
-        Scope sc(c, "synthesize");
-        hipLaunchKernelGGL(k_synth, dim3((int)((c->Npad + 255) / 256)), dim3(256), 0, c->stream, c->p, c->dLatent,
-                           const_cast<float *>(c->p.data), const_cast<float *>(c->p.munc), seed, c->Npad);
-    }
-    LAUNCH_CHECK("k_synth");
+    CHECK(launch(c, "synthesize", "k_synth", k_synth, dim3((int)((c->Npad + 255) / 256)), dim3(256), 0, c->stream, c->p, c->dLatent,
+                 const_cast<float *>(c->p.data), const_cast<float *>(c->p.munc), seed, c->Npad));
     HIPOK(hipStreamSynchronize(c->stream));
     c->statsValid = c->haveFwd = c->haveBwd = false;
     return 0;

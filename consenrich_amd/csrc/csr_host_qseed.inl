@@ -63,11 +63,8 @@ static int qs_posterior_device(csr_ctx *c, const std::vector<QpHostJob> &in, con
     QpCfg k;
     k.q_floor = cf.q_floor; k.q_cap = cf.q_cap; k.robust_t_nu = cf.robust_t_nu; k.q_seed_prior_level = cf.q_seed_prior_level;
     k.prior_log_sd = cf.prior_log_sd; k.default_t_nu = cf.default_t_nu; k.min_transitions = cf.min_transitions; k.grid_size = G;
-    {
-        Scope sc_(c, "qseed_posterior");
-        hipLaunchKernelGGL(k_qs_posterior, dim3((unsigned)nj), dim3(1024), 0, c->stream, (const QpJob *)(base + oJobs), k);
-    }
-    LAUNCH_CHECK("k_qs_posterior");
+    CHECK(launch(c, "qseed_posterior", "k_qs_posterior", k_qs_posterior, dim3((unsigned)nj), dim3(1024), 0, c->stream,
+                 (const QpJob *)(base + oJobs), k));
     std::vector<int> st(nj);
     HIPOK(hipMemcpyAsync(outs, base + oOut, sizeof(csr_qseed_post) * nj, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(st.data(), base + oSt, sizeof(int) * nj, hipMemcpyDeviceToHost, c->stream));
@@ -161,12 +158,11 @@ static int qs_same_track(csr_ctx *c, std::vector<QsJob> &jobs, const csr_qseed_s
             a.raw = (double *)(base + jb.oRaw);
             a.work = (double *)(base + oWork);
             HIPOK(hipMemsetAsync(a.firstErr, 0xFF, 8, c->stream));
-            hipLaunchKernelGGL(k_qs_count, dim3((unsigned)((sc + 255) / 256)), dim3(256), 0, c->stream, a);
-            hipLaunchKernelGGL(k_qs_scan, dim3(1), dim3(1024), 0, c->stream, a);
+            CHECK(launch(c, nullptr, "k_qs_count", k_qs_count, dim3((unsigned)((sc + 255) / 256)), dim3(256), 0, c->stream, a));
+            CHECK(launch(c, nullptr, "k_qs_scan", k_qs_scan, dim3(1), dim3(1024), 0, c->stream, a));
             HIPOK(hipMemcpyAsync(&scal[i], v, 16, hipMemcpyDeviceToHost, c->stream));
         }
     }
-    LAUNCH_CHECK("k_qs_count");
     HIPOK(hipStreamSynchronize(c->stream));
     // phase B: the precision sample stays on the device; its two quantiles (pyx:1658-1662: median and cap quantile, linear
     // interpolation between order statistics) come from exact rank selection (k_qs_select), four ranks per chain
@@ -188,7 +184,7 @@ static int qs_same_track(csr_ctx *c, std::vector<QsJob> &jobs, const csr_qseed_s
             jb.dg.pair_count = jb.dg.sampled_pair_count = a.nPairs;
             jb.dg.precision_sample_count = a.sampleCount;
             if (a.sampleCount <= 0) continue;
-            hipLaunchKernelGGL(k_qs_sample, dim3((unsigned)((a.sampleCount + 255) / 256)), dim3(256), 0, c->stream, a);
+            CHECK(launch(c, nullptr, "k_qs_sample", k_qs_sample, dim3((unsigned)((a.sampleCount + 255) / 256)), dim3(256), 0, c->stream, a));
             sel[i].v = a.raw;
             sel[i].n = a.sampleCount;
             const double qs[2] = {0.5, cf.precision_cap_quantile};
@@ -203,18 +199,13 @@ static int qs_same_track(csr_ctx *c, std::vector<QsJob> &jobs, const csr_qseed_s
             ++nSel;
         }
     }
-    LAUNCH_CHECK("k_qs_sample");
     std::vector<double> caps(jobs.size(), NAN);
     if (nSel > 0) {
         const size_t oSel = (need_ + 255) / 256 * 256;          // behind everything laid out above (qsBuf was sized with it)
         char *sb = base + oSel;
         for (size_t i = 0; i < jobs.size(); ++i) sel[i].out = (double *)(sb + sizeof(QsSelJob) * jobs.size()) + 4 * i;
         HIPOK(hipMemcpyAsync(sb, sel.data(), sizeof(QsSelJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
-        {
-            Scope sc_(c, "qseed_select");
-            hipLaunchKernelGGL(k_qs_select, dim3((unsigned)jobs.size()), dim3(1024), 0, c->stream, (const QsSelJob *)sb);
-        }
-        LAUNCH_CHECK("k_qs_select");
+        CHECK(launch(c, "qseed_select", "k_qs_select", k_qs_select, dim3((unsigned)jobs.size()), dim3(1024), 0, c->stream, (const QsSelJob *)sb));
         std::vector<double> osel(4 * jobs.size(), 0.0);
         HIPOK(hipMemcpyAsync(osel.data(), sb + sizeof(QsSelJob) * jobs.size(), 8 * osel.size(), hipMemcpyDeviceToHost, c->stream));
         HIPOK(hipStreamSynchronize(c->stream));
@@ -240,17 +231,17 @@ static int qs_same_track(csr_ctx *c, std::vector<QsJob> &jobs, const csr_qseed_s
             a.cap = caps[i];
             jb.dg.precision_cap = caps[i];
             const size_t sc = (size_t)a.scanCount;
-            if ((size_t)a.m * 3 * 64 * 8 <= 65536)      // default dynamic-LDS limit of a workgroup
-                hipLaunchKernelGGL(k_qs_transitions<true>, dim3((unsigned)((sc + 63) / 64)), dim3(64),
-                                   (size_t)a.m * 3 * 64 * 8, c->stream, a);
-            else
-                hipLaunchKernelGGL(k_qs_transitions<false>, dim3((unsigned)((sc + 255) / 256)), dim3(256), 0, c->stream, a);
+            // the LDS-tile form (64 threads) while its tile fits the default dynamic-LDS limit of a workgroup
+            const size_t tile = (size_t)a.m * 3 * 64 * 8;
+            const bool tiled = tile <= 65536;
+            const unsigned block = tiled ? 64 : 256;
+            CHECK(launch(c, nullptr, "k_qs_transitions", tiled ? &k_qs_transitions<true> : &k_qs_transitions<false>,
+                         dim3((unsigned)((sc + block - 1) / block)), dim3(block), tiled ? tile : 0, c->stream, a));
             // deltas | svar | weights | sig | cnt | cappedCnt are contiguous on the device: one copy per chain
             down[i].buf.resize(40 * sc);
             HIPOK(hipMemcpyAsync(down[i].buf.data(), a.deltas, 40 * sc, hipMemcpyDeviceToHost, c->stream));
         }
     }
-    LAUNCH_CHECK("k_qs_transitions");
     HIPOK(hipStreamSynchronize(c->stream));
     qs_parallel_for((int)jobs.size(), [&](int i) {
         QsJob &jb = jobs[i];
@@ -302,11 +293,7 @@ static int qs_pooled(csr_ctx *c, QsArgs a, std::vector<double> &deltas, std::vec
     a.pooledMean = (double *)(base + 256);
     a.pooledVar = a.pooledMean + n;
     HIPOK(hipMemsetAsync(a.firstErr, 0xFF, 8, c->stream));
-    {
-        Scope sc_(c, "qseed_pooled");
-        hipLaunchKernelGGL(k_qs_pooled, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, a);
-    }
-    LAUNCH_CHECK("k_qs_pooled");
+    CHECK(launch(c, "qseed_pooled", "k_qs_pooled", k_qs_pooled, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, a));
     std::vector<double> pm(n), pv(n);
     unsigned long long err = 0;
     HIPOK(hipMemcpyAsync(pm.data(), a.pooledMean, 8 * n, hipMemcpyDeviceToHost, c->stream));
@@ -340,7 +327,7 @@ static int qs_median_obsvar(csr_ctx *c, QsArgs a, double *median, int64_t *count
         unsigned prefix = 0, mask = 0;
         for (int shift = 24; shift >= 0; shift -= 8) {
             HIPOK(hipMemsetAsync(hist, 0, sizeof(h), c->stream));
-            hipLaunchKernelGGL(k_qs_hist, dim3(grid), dim3(256), 0, c->stream, a, shift, mask, prefix, hist);
+            CHECK(launch(c, nullptr, "k_qs_hist", k_qs_hist, dim3(grid), dim3(256), 0, c->stream, a, shift, mask, prefix, hist));
             HIPOK(hipMemcpyAsync(h, hist, sizeof(h), hipMemcpyDeviceToHost, c->stream));
             HIPOK(hipStreamSynchronize(c->stream));
             if (shift == 24) {

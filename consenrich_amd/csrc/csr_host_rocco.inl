@@ -79,11 +79,8 @@ static int rocco_run(csr_ctx *c, const RoccoDev &dv, std::vector<RoccoChainIn> &
         jobs.clear();
         for (int i : cal) jobs.push_back(RoccoJob{chains[i].off, chains[i].n, 0.0, 0, 0});
         HIPOK(hipMemcpyAsync(dJobs, jobs.data(), jobs.size() * sizeof(RoccoJob), hipMemcpyHostToDevice, c->stream));
-        {
-            Scope sc(c, "rocco_minmax");
-            hipLaunchKernelGGL(k_rocco_minmax, dim3((unsigned)jobs.size()), dim3(256), 0, c->stream, dJobs, dv.scores, dMm);
-        }
-        LAUNCH_CHECK("k_rocco_minmax");
+        CHECK(launch(c, "rocco_minmax", "k_rocco_minmax", k_rocco_minmax, dim3((unsigned)jobs.size()), dim3(256), 0, c->stream, dJobs,
+                     dv.scores, dMm));
         std::vector<double> mm(2 * cal.size());
         HIPOK(hipMemcpyAsync(mm.data(), dMm, 16 * cal.size(), hipMemcpyDeviceToHost, c->stream));
         // switchSum: the reference's SEQUENTIAL float64 sum of the n - 1 costs (pyx:8794-8795), here while the reduction runs
@@ -159,26 +156,16 @@ static int rocco_run(csr_ctx *c, const RoccoDev &dv, std::vector<RoccoChainIn> &
         HIPOK(hipMemcpyAsync(dJobs, jobs.data(), jobs.size() * sizeof(RoccoJob), hipMemcpyHostToDevice, c->stream));
         HIPOK(hipMemcpyAsync(dPen, pen.data(), np * 8, hipMemcpyHostToDevice, c->stream));
         rs.h2d_bytes += (int64_t)(jobs.size() * sizeof(RoccoJob) + np * 8);
+        // (the first template argument: the costs are derived from the scores, there is no cost track)
         if (nCountJobs) {
-            Scope sc(c, "rocco_count");
-            if (dv.costs)
-                hipLaunchKernelGGL((k_rocco_chain<false, false>), dim3((unsigned)nCountJobs), dim3(64), 0, c->stream, dJobs, dv.scores,
-                                   dv.costs, dPen, dRes, dv.bt, dv.sol);
-            else
-                hipLaunchKernelGGL((k_rocco_chain<true, false>), dim3((unsigned)nCountJobs), dim3(64), 0, c->stream, dJobs, dv.scores,
-                                   dv.costs, dPen, dRes, dv.bt, dv.sol);
-            LAUNCH_CHECK("k_rocco_chain (count)");
+            CHECK(launch(c, "rocco_count", "k_rocco_chain (count)", dv.costs ? &k_rocco_chain<false, false> : &k_rocco_chain<true, false>,
+                         dim3((unsigned)nCountJobs), dim3(64), 0, c->stream, dJobs, dv.scores, dv.costs, dPen, dRes, dv.bt, dv.sol));
             ++rs.launches;
         }
         if (!btJobs.empty()) {
-            Scope sc(c, "rocco_backtrace");
-            if (dv.costs)
-                hipLaunchKernelGGL((k_rocco_chain<false, true>), dim3((unsigned)btJobs.size()), dim3(64), 0, c->stream,
-                                   dJobs + nCountJobs, dv.scores, dv.costs, dPen, dRes, dv.bt, dv.sol);
-            else
-                hipLaunchKernelGGL((k_rocco_chain<true, true>), dim3((unsigned)btJobs.size()), dim3(64), 0, c->stream,
-                                   dJobs + nCountJobs, dv.scores, dv.costs, dPen, dRes, dv.bt, dv.sol);
-            LAUNCH_CHECK("k_rocco_chain (backtrace)");
+            CHECK(launch(c, "rocco_backtrace", "k_rocco_chain (backtrace)", dv.costs ? &k_rocco_chain<false, true> : &k_rocco_chain<true, true>,
+                         dim3((unsigned)btJobs.size()), dim3(64), 0, c->stream, dJobs + nCountJobs, dv.scores, dv.costs, dPen, dRes, dv.bt,
+                         dv.sol));
             ++rs.launches;
         }
         HIPOK(hipMemcpyAsync(res.data(), dRes, np * sizeof(RoccoRes), hipMemcpyDeviceToHost, c->stream));
@@ -381,10 +368,9 @@ extern "C" int csr_batch_rocco_scores(csr_ctx *c, int32_t mode, double z) {
     const dim3 grid((unsigned)std::min<int64_t>((longest + 255) / 256, 1024), (unsigned)nc);
     {
         Scope sc(c, "rocco_scores");
-        hipLaunchKernelGGL(k_rocco_scores, grid, dim3(256), 0, c->stream, a);
-        if (a.lower) hipLaunchKernelGGL(k_rocco_floor, grid, dim3(256), 0, c->stream, a);
+        CHECK(launch(c, nullptr, "k_rocco_scores", k_rocco_scores, grid, dim3(256), 0, c->stream, a));
+        if (a.lower) CHECK(launch(c, nullptr, "k_rocco_floor", k_rocco_floor, grid, dim3(256), 0, c->stream, a));
     }
-    LAUNCH_CHECK("k_rocco_scores");
     std::vector<int> bad((size_t)nc, 0);
     HIPOK(hipMemcpyAsync(bad.data(), r.bad, 4 * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
@@ -470,11 +456,10 @@ extern "C" int csr_batch_rocco_runs(csr_ctx *c, int32_t chain, int32_t max_gap_b
     a.capacity = capacity;
     {
         Scope sc(c, "rocco_runs");
-        hipLaunchKernelGGL(k_rocco_run_count, dim3((unsigned)nb), dim3(1024), 0, c->stream, a);
-        hipLaunchKernelGGL(k_rocco_run_scan, dim3(1), dim3(1024), 0, c->stream, a, nb);
-        if (capacity > 0) hipLaunchKernelGGL(k_rocco_run_write, dim3((unsigned)nb), dim3(1024), 0, c->stream, a);
+        CHECK(launch(c, nullptr, "k_rocco_run_count", k_rocco_run_count, dim3((unsigned)nb), dim3(1024), 0, c->stream, a));
+        CHECK(launch(c, nullptr, "k_rocco_run_scan", k_rocco_run_scan, dim3(1), dim3(1024), 0, c->stream, a, nb));
+        if (capacity > 0) CHECK(launch(c, nullptr, "k_rocco_run_write", k_rocco_run_write, dim3((unsigned)nb), dim3(1024), 0, c->stream, a));
     }
-    LAUNCH_CHECK("k_rocco_run");
     unsigned long long tot = 0;
     HIPOK(hipMemcpyAsync(&tot, a.blockSum + nb, 8, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));

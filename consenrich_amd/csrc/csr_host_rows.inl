@@ -23,11 +23,7 @@ static int launch_diag(csr_ctx *c, uint32_t flags, bool usePnoise) {
     a.nchains = (int)c->chains.size();
     Prm p = c->p;
     p.chainActive = nullptr;
-    {
-        Scope sc(c, "diagnostics");
-        hipLaunchKernelGGL(k_diag_natural, dim3((int)((c->Npad + 255) / 256)), dim3(256), 0, c->stream, p, a);
-    }
-    LAUNCH_CHECK("k_diag_natural");
+    CHECK(launch(c, "diagnostics", "k_diag_natural", k_diag_natural, dim3((int)((c->Npad + 255) / 256)), dim3(256), 0, c->stream, p, a));
     return 0;
 }
 
@@ -109,27 +105,15 @@ static void bg_partition(const std::vector<int64_t> &off, const std::vector<int6
 }
 
 template <int NR>
-static void launch_bg(csr_ctx *c, const BgPrm &p, bool center) {
-    {
-        Scope sc(c, "bg_local");
-        hipLaunchKernelGGL(k_bg_local<NR>, dim3((int)p.NGk), dim3(64), 0, c->stream, p);
-    }
-    {
-        Scope sc(c, "bg_sep_assemble");
-        hipLaunchKernelGGL(k_bg_sep_assemble<NR>, dim3((int)((p.NBk + 255) / 256)), dim3(256), 0, c->stream, p);
-    }
-    {
-        Scope sc(c, "bg_reduced");
-        hipLaunchKernelGGL(k_bg_reduced<NR>, dim3(p.nchains), dim3(64), 0, c->stream, p);
-    }
-    {
-        Scope sc(c, "bg_combine");
-        hipLaunchKernelGGL(k_bg_combine<NR>, dim3((int)((p.NGk * p.SB * 64 + 255) / 256)), dim3(256), 0, c->stream, p);
-    }
-    if (center) {
-        Scope sc(c, "bg_center");
-        hipLaunchKernelGGL(k_bg_center, dim3(p.nchains), dim3(1024), 0, c->stream, p);
-    }
+static int launch_bg(csr_ctx *c, const BgPrm &p, bool center) {
+    CHECK(launch(c, "bg_local", "k_bg_local<NR>", k_bg_local<NR>, dim3((int)p.NGk), dim3(64), 0, c->stream, p));
+    CHECK(launch(c, "bg_sep_assemble", "k_bg_sep_assemble<NR>", k_bg_sep_assemble<NR>, dim3((int)((p.NBk + 255) / 256)), dim3(256), 0,
+                 c->stream, p));
+    CHECK(launch(c, "bg_reduced", "k_bg_reduced<NR>", k_bg_reduced<NR>, dim3(p.nchains), dim3(64), 0, c->stream, p));
+    CHECK(launch(c, "bg_combine", "k_bg_combine<NR>", k_bg_combine<NR>, dim3((int)((p.NGk * p.SB * 64 + 255) / 256)), dim3(256), 0,
+                 c->stream, p));
+    if (center) CHECK(launch(c, "bg_center", "k_bg_center", k_bg_center, dim3(p.nchains), dim3(1024), 0, c->stream, p));
+    return 0;
 }
 
 extern "C" int csr_solve_background(int32_t n_chains, const int64_t *n, const double *weight, const double *rhs,
@@ -197,9 +181,7 @@ extern "C" int csr_solve_background(int32_t n_chains, const int64_t *n, const do
     HIPOK(hipMemcpyAsync(base + oBlk, blk.data(), sizeof(int4) * blk.size(), hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemcpyAsync(base + oW, weight, 8 * N, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemcpyAsync(base + oR, rhs, 8 * N, hipMemcpyHostToDevice, c->stream));
-    if (NR == 2) launch_bg<2>(c, p, true);
-    else launch_bg<1>(c, p, false);
-    LAUNCH_CHECK("background solve");
+    CHECK(NR == 2 ? launch_bg<2>(c, p, true) : launch_bg<1>(c, p, false));
     std::vector<int64_t> cbi(n_chains);
     std::vector<double> cbv(n_chains);
     HIPOK(hipMemcpyAsync(out, p.out0, 8 * N, hipMemcpyDeviceToHost, c->stream));
@@ -239,11 +221,8 @@ extern "C" int csr_background_weighted_stats(int64_t m, int64_t n, const float *
     HIPOK(hipMemcpyAsync(dr, resid, mat, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemcpyAsync(di, inv_var, mat, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemsetAsync(ds, 0, 8, c->stream));
-    {
-        Scope sc(c, "bg_weighted_stats");
-        hipLaunchKernelGGL(k_bg_weighted_stats, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, m, n, dr, di, dw, dh, ds);
-    }
-    LAUNCH_CHECK("k_bg_weighted_stats");
+    CHECK(launch(c, "bg_weighted_stats", "k_bg_weighted_stats", k_bg_weighted_stats, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream,
+                 m, n, dr, di, dw, dh, ds));
     unsigned long long sup = 0;
     HIPOK(hipMemcpyAsync(weight, dw, vec, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(rhs, dh, vec, hipMemcpyDeviceToHost, c->stream));
@@ -340,10 +319,7 @@ static int bg_solve_active(csr_ctx *c, const csr_bg_cfg *cfg) {
     p.w = S.bat.wAdj; p.rhs = S.bat.rhs;
     p.out0 = S.bat.sol; p.out1 = S.out1;
     p.active = S.dActive;
-    if (p.NR == 2) launch_bg<2>(c, p, true);
-    else launch_bg<1>(c, p, false);
-    LAUNCH_CHECK("background solve");
-    return 0;
+    return p.NR == 2 ? launch_bg<2>(c, p, true) : launch_bg<1>(c, p, false);
 }
 
 extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, csr_bg_out *out) {
@@ -377,17 +353,14 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
     a.padf = (float)c->mdl.pad; a.wMinf = (float)c->mdl.w_min; a.wMaxf = (float)c->mdl.w_max;
     a.bgCur = S.haveCur ? c->nat[CSR_ARR_BACKGROUND] : nullptr;
     Prm p = c->p;
-    {
-        Scope sc(c, "bg_batch_stats");
-        hipLaunchKernelGGL(k_bg_batch_stats, dim3(gridN), dim3(256), 0, c->stream, p, a);
-    }
+    CHECK(launch(c, "bg_batch_stats", "k_bg_batch_stats", k_bg_batch_stats, dim3(gridN), dim3(256), 0, c->stream, p, a));
     const int gridW = (a.NW + 3) / 4;
-    auto wave_pass = [&](int what, int bit, const unsigned char *hs) {
-        hipLaunchKernelGGL(k_bg_wave_pass, dim3(gridW), dim3(256), 0, c->stream, p, a, what, bit, hs);
-        hipLaunchKernelGGL(k_bg_wave_fold, dim3(nc), dim3(64), 0, c->stream, a, what, bit);
+    // (no profile scope of its own: the median selection runs its 63 passes under one)
+    auto wave_pass = [&](int what, int bit, const unsigned char *hs) -> int {
+        CHECK(launch(c, nullptr, "k_bg_wave_pass", k_bg_wave_pass, dim3(gridW), dim3(256), 0, c->stream, p, a, what, bit, hs));
+        return launch(c, nullptr, "k_bg_wave_fold", k_bg_wave_fold, dim3(nc), dim3(64), 0, c->stream, a, what, bit);
     };
-    wave_pass(0, 0, nullptr);
-    LAUNCH_CHECK("background statistics");
+    CHECK(wave_pass(0, 0, nullptr));
     std::vector<double> cs(5 * (size_t)nc);
     HIPOK(hipMemcpyAsync(cs.data(), a.chainSum, 8 * 5 * nc, hipMemcpyDeviceToHost, c->stream));
     HIPOK(wait_stream(c));
@@ -426,9 +399,8 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
         HIPOK(hipMemsetAsync(a.selAns, 0, 8 * 2 * nc, c->stream));
         {
             Scope sc(c, "bg_median_select");
-            for (int bit = 62; bit >= 0; --bit) wave_pass(1, bit, nullptr);
+            for (int bit = 62; bit >= 0; --bit) CHECK(wave_pass(1, bit, nullptr));
         }
-        LAUNCH_CHECK("median select");
         std::vector<double> mid(2 * (size_t)nc, 0.0);
         HIPOK(hipMemcpyAsync(mid.data(), a.selAns, 8 * 2 * nc, hipMemcpyDeviceToHost, c->stream));
         HIPOK(wait_stream(c));
@@ -447,10 +419,10 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
     // first solve (core.py:8306-8324)
     const bool useInit = irls && (cfg->use_initial & CSR_BG_INIT_FROM_CURRENT) != 0;
     if (useInit) {
-        hipLaunchKernelGGL(k_bg_mask, dim3(gridN), dim3(256), 0, c->stream, p, a, 0);
+        CHECK(launch(c, nullptr, "k_bg_mask", k_bg_mask, dim3(gridN), dim3(256), 0, c->stream, p, a, 0));
         for (int i = 0; i < nc; ++i) prevValid[i] = 1;
     }
-    hipLaunchKernelGGL(k_bg_adjust, dim3(gridN), dim3(256), 0, c->stream, p, a, useInit ? 1 : 0);
+    CHECK(launch(c, nullptr, "k_bg_adjust", k_bg_adjust, dim3(gridN), dim3(256), 0, c->stream, p, a, useInit ? 1 : 0));
     CHECK(bg_solve_active(c, cfg));
     auto harvest_bad = [&]() -> int {
         std::vector<int64_t> bi(nc);
@@ -472,7 +444,7 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
         for (int pass = 0; pass < maxPasses; ++pass) {
             CHECK(harvest_bad());
             HIPOK(hipMemcpyAsync(S.dActive, act.data(), nc, hipMemcpyHostToDevice, c->stream));
-            wave_pass(2, 0, nullptr);
+            CHECK(wave_pass(2, 0, nullptr));
             std::vector<unsigned int> fl(nc);
             HIPOK(hipMemcpyAsync(fl.data(), a.flags, sizeof(unsigned int) * nc, hipMemcpyDeviceToHost, c->stream));
             HIPOK(wait_stream(c));
@@ -489,8 +461,8 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
             }
             if (!any) break;
             HIPOK(hipMemcpyAsync(S.dActive, act.data(), nc, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_bg_mask, dim3(gridN), dim3(256), 0, c->stream, p, a, 2);
-            hipLaunchKernelGGL(k_bg_adjust, dim3(gridN), dim3(256), 0, c->stream, p, a, 1);
+            CHECK(launch(c, nullptr, "k_bg_mask", k_bg_mask, dim3(gridN), dim3(256), 0, c->stream, p, a, 2));
+            CHECK(launch(c, nullptr, "k_bg_adjust", k_bg_adjust, dim3(gridN), dim3(256), 0, c->stream, p, a, 1));
             CHECK(bg_solve_active(c, cfg));
         }
     }
@@ -501,7 +473,7 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
         std::vector<unsigned char> all(nc);
         for (int i = 0; i < nc; ++i) all[i] = sup[i];
         HIPOK(hipMemcpyAsync(S.dActive, all.data(), nc, hipMemcpyHostToDevice, c->stream));
-        wave_pass(2, 0, nullptr);
+        CHECK(wave_pass(2, 0, nullptr));
         std::vector<unsigned int> fl(nc);
         HIPOK(hipMemcpyAsync(fl.data(), a.flags, sizeof(unsigned int) * nc, hipMemcpyDeviceToHost, c->stream));
         HIPOK(wait_stream(c));
@@ -510,8 +482,7 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
     }
     for (int i = 0; i < nc; ++i) sup[i] = (out[i].status == CSR_BG_OK) ? 1 : 0;
     HIPOK(hipMemcpyAsync(S.dHasSup, sup.data(), nc, hipMemcpyHostToDevice, c->stream));
-    wave_pass(3, 0, S.dHasSup);
-    LAUNCH_CHECK("k_bg_finish");
+    CHECK(wave_pass(3, 0, S.dHasSup));
     HIPOK(hipMemcpyAsync(cs.data(), a.chainSum, 8 * 5 * nc, hipMemcpyDeviceToHost, c->stream));
     HIPOK(wait_stream(c));
     for (int i = 0; i < nc; ++i) {
@@ -596,9 +567,9 @@ static int64_t bedgraph_impl(csr_ctx *c, BgwArgs a, const int64_t *hStarts, cons
     }
     {
         Scope sc(c, "bedgraph_len_scan");
-        hipLaunchKernelGGL(k_bgw_len, dim3((int)nb), dim3(1024), 0, c->stream, a);
-        hipLaunchKernelGGL(k_bgw_scan_blocks, dim3(1), dim3(1024), 0, c->stream, a, nb);
-        hipLaunchKernelGGL(k_bgw_scan_rows, dim3((int)nb), dim3(1024), 0, c->stream, a);
+        CHECK(launch(c, nullptr, "k_bgw_len", k_bgw_len, dim3((int)nb), dim3(1024), 0, c->stream, a));
+        CHECK(launch(c, nullptr, "k_bgw_scan_blocks", k_bgw_scan_blocks, dim3(1), dim3(1024), 0, c->stream, a, nb));
+        CHECK(launch(c, nullptr, "k_bgw_scan_rows", k_bgw_scan_rows, dim3((int)nb), dim3(1024), 0, c->stream, a));
     }
     int64_t total = 0;
     if (!H(hipMemcpyAsync(&total, a.blockSum + nb, 8, hipMemcpyDeviceToHost, c->stream))) return -1;
@@ -615,11 +586,7 @@ static int64_t bedgraph_impl(csr_ctx *c, BgwArgs a, const int64_t *hStarts, cons
     } else {
         a.out = base + oText;
     }
-    {
-        Scope sc(c, "bedgraph_write");
-        hipLaunchKernelGGL(k_bgw_write, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a);
-    }
-    if (hipGetLastError() != hipSuccess) { fail("bedGraph writer launch failed"); return -1; }
+    CHECK(launch(c, "bedgraph_write", "k_bgw_write", k_bgw_write, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a));
     if (!H(hipMemcpyAsync(out, a.out, (size_t)total, hipMemcpyDeviceToHost, c->stream))) return -1;
     if (!H(hipStreamSynchronize(c->stream))) return -1;
     return total;
@@ -698,11 +665,7 @@ extern "C" int64_t csr_batch_bigwig_sections(csr_ctx *c, int32_t chain, int32_t 
     a.chromId = chrom_id; a.itemsPerSection = items_per_section;
     a.out = (unsigned char *)c->wrBuf.ptr;
     a.part = (double *)((char *)c->wrBuf.ptr + (full + 255) / 256 * 256);
-    {
-        Scope sc(c, "bigwig_sections");
-        hipLaunchKernelGGL(k_bw_sections, dim3((unsigned)grid), dim3(256), 0, c->stream, a);
-    }
-    if (hipGetLastError() != hipSuccess) { fail("bigWig sections launch failed"); return -1; }
+    CHECK(launch(c, "bigwig_sections", "k_bw_sections", k_bw_sections, dim3((unsigned)grid), dim3(256), 0, c->stream, a));
     std::vector<double> part(6 * (size_t)grid);
     if (hipMemcpyAsync(out, a.out, (size_t)bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipMemcpyAsync(part.data(), a.part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -733,11 +696,7 @@ extern "C" int64_t csr_batch_bigwig_zoom(csr_ctx *c, int32_t chain, int32_t arra
     if (out_capacity < bytes) { fail("bigWig zoom: output buffer too small"); return -1; }
     if (c->wrBuf.reserve((size_t)bytes + 256) != 0) return -1;
     a.chromId = chrom_id; a.binsPerRecord = bins_per_record; a.out = (unsigned char *)c->wrBuf.ptr;
-    {
-        Scope sc(c, "bigwig_zoom");
-        hipLaunchKernelGGL(k_bw_zoom, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->stream, a, nrec);
-    }
-    if (hipGetLastError() != hipSuccess) { fail("bigWig zoom launch failed"); return -1; }
+    CHECK(launch(c, "bigwig_zoom", "k_bw_zoom", k_bw_zoom, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->stream, a, nrec));
     if (hipMemcpyAsync(out, a.out, (size_t)bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) { fail("bigWig zoom: copy failed"); return -1; }
     return bytes;
@@ -784,21 +743,20 @@ extern "C" int csr_batch_objective_terms(csr_ctx *c, const csr_objective_cfg *cf
     const int gridW = (a.NW + 3) / 4;
     {
         Scope sc(c, "objective_terms");
-        hipLaunchKernelGGL(k_obj_wave, dim3(gridW), dim3(256), 0, c->stream, c->p, a, o);
-        hipLaunchKernelGGL(k_obj_fold, dim3(nc), dim3(64), 0, c->stream, a, o);
+        CHECK(launch(c, nullptr, "k_obj_wave", k_obj_wave, dim3(gridW), dim3(256), 0, c->stream, c->p, a, o));
+        CHECK(launch(c, nullptr, "k_obj_fold", k_obj_fold, dim3(nc), dim3(64), 0, c->stream, a, o));
     }
-    LAUNCH_CHECK("k_obj_wave");
     std::vector<double> t(6 * (size_t)nc);
     HIPOK(hipMemcpyAsync(t.data(), o.chainOut, 8 * 6 * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
     std::vector<double> scale(nc, 1.0);
     if (negActive) {      // median of the positive float64 weights (core.py:4437-4446), same selection passes as the update
         a.w = o.w64;
-        auto wave_pass = [&](int what, int bit) {
-            hipLaunchKernelGGL(k_bg_wave_pass, dim3(gridW), dim3(256), 0, c->stream, c->p, a, what, bit,
-                               (const unsigned char *)nullptr);
-            hipLaunchKernelGGL(k_bg_wave_fold, dim3(nc), dim3(64), 0, c->stream, a, what, bit);
+        auto wave_pass = [&](int what, int bit) -> int {
+            CHECK(launch(c, nullptr, "k_bg_wave_pass", k_bg_wave_pass, dim3(gridW), dim3(256), 0, c->stream, c->p, a, what, bit,
+                         (const unsigned char *)nullptr));
+            return launch(c, nullptr, "k_bg_wave_fold", k_bg_wave_fold, dim3(nc), dim3(64), 0, c->stream, a, what, bit);
         };
-        wave_pass(0, 0);
+        CHECK(wave_pass(0, 0));
         std::vector<double> cs(5 * (size_t)nc);
         HIPOK(hipMemcpyAsync(cs.data(), a.chainSum, 8 * 5 * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
         HIPOK(wait_stream(c));
@@ -816,9 +774,8 @@ extern "C" int csr_batch_objective_terms(csr_ctx *c, const csr_objective_cfg *cf
             HIPOK(hipMemsetAsync(a.selAns, 0, 8 * 2 * (size_t)nc, c->stream));
             {
                 Scope sc(c, "objective_median");
-                for (int bit = 62; bit >= 0; --bit) wave_pass(1, bit);
+                for (int bit = 62; bit >= 0; --bit) CHECK(wave_pass(1, bit));
             }
-            LAUNCH_CHECK("objective median");
             std::vector<double> mid(2 * (size_t)nc, 0.0);
             HIPOK(hipMemcpyAsync(mid.data(), a.selAns, 8 * 2 * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
             HIPOK(wait_stream(c));
@@ -885,11 +842,7 @@ extern "C" int csr_batch_phase_tracks(csr_ctx *c, int32_t chain, int32_t use_lam
     CHECK(c->qsBuf.reserve(2 * bytesD + (size_t)n * 4));
     char *base = (char *)c->qsBuf.ptr;
     a.rel = (double *)base; a.fit = (double *)(base + bytesD); a.cnt = (int *)(base + 2 * bytesD);
-    {
-        Scope sc(c, "phase_tracks");
-        hipLaunchKernelGGL(k_phase_tracks, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a);
-    }
-    LAUNCH_CHECK("k_phase_tracks");
+    CHECK(launch(c, "phase_tracks", "k_phase_tracks", k_phase_tracks, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a));
     HIPOK(hipMemcpyAsync(rel, a.rel, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (withFit) {
         HIPOK(hipMemcpyAsync(fit, a.fit, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -938,15 +891,14 @@ extern "C" int csr_batch_gain_summary(csr_ctx *c, int32_t chain, int32_t use_lam
     {
         Scope sc(c, "gain_summary");
         for (int phase = 0; phase < 2; ++phase) {
-            hipLaunchKernelGGL(k_gain_moments, grid, dim3(256), 0, c->stream, a, phase);
-            hipLaunchKernelGGL(k_gain_fold, dim3((unsigned)m), dim3(64), 0, c->stream, a, phase);
+            CHECK(launch(c, nullptr, "k_gain_moments", k_gain_moments, grid, dim3(256), 0, c->stream, a, phase));
+            CHECK(launch(c, nullptr, "k_gain_fold", k_gain_fold, dim3((unsigned)m), dim3(64), 0, c->stream, a, phase));
         }
         for (int pass = 0; pass < 8; ++pass) {
-            hipLaunchKernelGGL(k_gain_hist, grid, dim3(256), 0, c->stream, a, pass);
-            hipLaunchKernelGGL(k_gain_pick, dim3((unsigned)m), dim3(64), 0, c->stream, a, pass);
+            CHECK(launch(c, nullptr, "k_gain_hist", k_gain_hist, grid, dim3(256), 0, c->stream, a, pass));
+            CHECK(launch(c, nullptr, "k_gain_pick", k_gain_pick, dim3((unsigned)m), dim3(64), 0, c->stream, a, pass));
         }
     }
-    LAUNCH_CHECK("k_gain_*");
     HIPOK(hipMemcpyAsync(out, a.out, bOut, hipMemcpyDeviceToHost, c->stream));
     HIPOK(wait_stream(c));
     return 0;
@@ -984,11 +936,7 @@ extern "C" int csr_observation_total_information(int64_t m, int64_t n, const voi
     a.m = m; a.n = n; a.stride = n; a.munc = base + oM; a.muncF64 = munc_is_f64 ? 1 : 0; a.hasActive = 1;
     a.active = (const uint8_t *)(base + oA); a.useLambda = lambda ? 1 : 0; a.lambda = (const double *)(base + oL);
     a.pad = pad; a.rho = rho; a.total = (double *)(base + oT);
-    {
-        Scope sc(c, "fold_total");
-        hipLaunchKernelGGL(k_fold_total, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a);
-    }
-    LAUNCH_CHECK("k_fold_total");
+    CHECK(launch(c, "fold_total", "k_fold_total", k_fold_total, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a));
     HIPOK(hipMemcpyAsync(total, a.total, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
     return 0;
@@ -1031,11 +979,7 @@ extern "C" int csr_fold_mask_and_information(int64_t m, int64_t n, int64_t block
     a.pad = pad; a.rho = rho; a.wantNominal = nominal ? 1 : 0;
     a.mask = (uint8_t *)(base + oK); a.kept = (double *)(base + oKe); a.heldout = (double *)(base + oHe);
     a.h = (double *)(base + oH); a.nominal = (double *)(base + oNo);
-    {
-        Scope sc(c, "fold_mask");
-        hipLaunchKernelGGL(k_fold_mask, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a);
-    }
-    LAUNCH_CHECK("k_fold_mask");
+    CHECK(launch(c, "fold_mask", "k_fold_mask", k_fold_mask, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a));
     HIPOK(hipMemcpyAsync(mask, a.mask, mn, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(kept, a.kept, nv, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(heldout, a.heldout, nv, hipMemcpyDeviceToHost, c->stream));
@@ -1088,10 +1032,9 @@ extern "C" int csr_batch_make_fold(csr_ctx *c, int32_t src, int32_t dst, int64_t
     a.maskedVariance = masked_variance;
     {
         Scope sc(c, "fold_make");
-        hipLaunchKernelGGL(k_fold_total, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a);
-        hipLaunchKernelGGL(k_fold_mask, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a);
+        CHECK(launch(c, nullptr, "k_fold_total", k_fold_total, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a));
+        CHECK(launch(c, nullptr, "k_fold_mask", k_fold_mask, dim3((int)((n + 255) / 256)), dim3(256), 0, c->stream, a));
     }
-    LAUNCH_CHECK("k_fold_mask");
     HIPOK(hipMemcpyAsync(kept, a.kept, nv, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(heldout, a.heldout, nv, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipMemcpyAsync(h, a.h, nv, hipMemcpyDeviceToHost, c->stream));

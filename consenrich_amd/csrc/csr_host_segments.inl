@@ -136,43 +136,21 @@ static int seg_run(csr_ctx *c, const double *dRows, int64_t rowLen, int nRows, c
     HIPOK(hipMemsetAsync(g.metaBuf.ptr, 0, oMeta + sizeof(SegMeta) * nJobs, c->stream));
     const dim3 jobs((unsigned)J, (unsigned)nc);
     {
-        Scope sc(c, "seg_walk_track");
         SegWalkArgs w{a.chains, dRows, rowLen, a.prefix, pLen, nRows, 1};
-        hipLaunchKernelGGL(k_seg_walk, dim3((unsigned)((nRows + SEG_WR - 1) / SEG_WR), (unsigned)nc), dim3(64), 0, c->stream, w);
+        CHECK(launch(c, "seg_walk_track", "k_seg_walk", k_seg_walk, dim3((unsigned)((nRows + SEG_WR - 1) / SEG_WR), (unsigned)nc), dim3(64), 0,
+                     c->stream, w));
     }
-    LAUNCH_CHECK("k_seg_walk");
+    CHECK(launch(c, "seg_excess", "k_seg_excess", k_seg_excess, dim3((unsigned)((longest + 255) / 256), (unsigned)(nRows * V),
+                 (unsigned)nc), dim3(256), 0, c->stream, a));
     {
-        Scope sc(c, "seg_excess");
-        hipLaunchKernelGGL(k_seg_excess, dim3((unsigned)((longest + 255) / 256), (unsigned)(nRows * V), (unsigned)nc), dim3(256), 0,
-                           c->stream, a);
-    }
-    LAUNCH_CHECK("k_seg_excess");
-    {
-        Scope sc(c, "seg_walk_excess");
         SegWalkArgs w{a.chains, a.excess, rowLen, a.exPrefix, pLen, nRows * V, V};
-        hipLaunchKernelGGL(k_seg_walk, dim3((unsigned)((nRows * V + SEG_WR - 1) / SEG_WR), (unsigned)nc), dim3(64), 0, c->stream, w);
+        CHECK(launch(c, "seg_walk_excess", "k_seg_walk", k_seg_walk, dim3((unsigned)((nRows * V + SEG_WR - 1) / SEG_WR), (unsigned)nc), dim3(64),
+                     0, c->stream, w));
     }
-    LAUNCH_CHECK("k_seg_walk");
-    {
-        Scope sc(c, "seg_count");
-        hipLaunchKernelGGL(k_seg_count, jobs, dim3(256), 0, c->stream, a);
-    }
-    LAUNCH_CHECK("k_seg_count");
-    {
-        Scope sc(c, "seg_runs");
-        hipLaunchKernelGGL(k_seg_runs, jobs, dim3(256), 0, c->stream, a);
-    }
-    LAUNCH_CHECK("k_seg_runs");
-    {
-        Scope sc(c, "seg_stats");
-        hipLaunchKernelGGL(k_seg_stats, dim3(SEG_STAT_BLOCKS, (unsigned)J, (unsigned)nc), dim3(256), 0, c->stream, a);
-    }
-    LAUNCH_CHECK("k_seg_stats");
-    {
-        Scope sc(c, "seg_select");
-        hipLaunchKernelGGL(k_seg_select, jobs, dim3(256), 0, c->stream, a);
-    }
-    LAUNCH_CHECK("k_seg_select");
+    CHECK(launch(c, "seg_count", "k_seg_count", k_seg_count, jobs, dim3(256), 0, c->stream, a));
+    CHECK(launch(c, "seg_runs", "k_seg_runs", k_seg_runs, jobs, dim3(256), 0, c->stream, a));
+    CHECK(launch(c, "seg_stats", "k_seg_stats", k_seg_stats, dim3(SEG_STAT_BLOCKS, (unsigned)J, (unsigned)nc), dim3(256), 0, c->stream, a));
+    CHECK(launch(c, "seg_select", "k_seg_select", k_seg_select, jobs, dim3(256), 0, c->stream, a));
     std::vector<SegMeta> meta(nJobs);
     {
         Scope sc(c, "seg_download");
@@ -253,11 +231,7 @@ static int seg_run(csr_ctx *c, const double *dRows, int64_t rowLen, int nRows, c
         a.oMean = (double *)(ob + 4 * slot);
         a.oMax = (double *)(ob + 5 * slot);
         HIPOK(hipMemcpyAsync(g.baseBuf.ptr, base.data(), 8 * nJobs, hipMemcpyHostToDevice, c->stream));
-        {
-            Scope sc(c, "seg_emit");
-            hipLaunchKernelGGL(k_seg_emit, jobs, dim3(256), 0, c->stream, a);
-        }
-        LAUNCH_CHECK("k_seg_emit");
+        CHECK(launch(c, "seg_emit", "k_seg_emit", k_seg_emit, jobs, dim3(256), 0, c->stream, a));
         {
             Scope sc(c, "seg_download");
             void *dst[6] = {g.oStart.data(), g.oEnd.data(), g.oScore.data(), g.oInteg.data(), g.oMean.data(), g.oMax.data()};

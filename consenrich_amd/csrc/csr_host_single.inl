@@ -81,8 +81,7 @@ static int import_nat(csr_ctx *c, const float *host, int ncomp, int64_t rows, in
         HIPOK(hipMemcpyAsync(scr + (c->chains[0].off + rowShift) * ncomp, host, sizeof(float) * ncomp * rows,
                              hipMemcpyHostToDevice, c->stream));
     for (int k = 0; k < ncomp; ++k) {
-        hipLaunchKernelGGL(k_import_f32, dim3(grid_slots(c)), dim3(256), 0, c->stream, c->p, scr, ncomp, k, dst, dstStride, k);
-        LAUNCH_CHECK("k_import_f32");
+        CHECK(launch(c, nullptr, "k_import_f32", k_import_f32, dim3(grid_slots(c)), dim3(256), 0, c->stream, c->p, scr, ncomp, k, dst, dstStride, k));
     }
     return 0;
 }
@@ -226,10 +225,10 @@ extern "C" int csr_expected_transition_residual_sums(int32_t state_dim, int64_t 
         cleanup();
         return fail("hipMemcpyAsync (transition sums inputs) failed");
     }
-    {
-        Scope sc(c, "transition_sums");
-        hipLaunchKernelGGL(k_tsums, dim3(grid), dim3(256), 0, c->stream, d, n, dxs, dPs, dlag, d == 2 ? F[0] : 1.0,
-                           d == 2 ? F[1] : 0.0, d == 2 ? F[2] : 0.0, d == 2 ? F[3] : 1.0, dpart, dpart + grid);
+    if (launch(c, "transition_sums", "k_tsums", k_tsums, dim3(grid), dim3(256), 0, c->stream, d, n, dxs, dPs, dlag, d == 2 ? F[0] : 1.0,
+               d == 2 ? F[1] : 0.0, d == 2 ? F[2] : 0.0, d == 2 ? F[3] : 1.0, dpart, dpart + grid) != 0) {
+        cleanup();
+        return -1;
     }
     std::vector<double> part(2 * grid);
     hipError_t e = hipMemcpyAsync(part.data(), dpart, sizeof(double) * 2 * grid, hipMemcpyDeviceToHost, c->stream);

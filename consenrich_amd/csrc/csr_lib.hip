@@ -31,6 +31,7 @@
 #include <sys/prctl.h>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 using namespace csr;
@@ -621,13 +622,14 @@ static hipEvent_t get_event(csr_ctx *c) {
     (void)hipEventCreate(&e);
     return e;
 }
+// (name == nullptr: no scope -- the caller holds one around several launches, or the launch is not counted)
 struct Scope {
     csr_ctx *c;
     ProfEntry *pe = nullptr;
     hipEvent_t a{}, b{};
     hipStream_t st;
     Scope(csr_ctx *c_, const char *name, hipStream_t st_ = nullptr) : c(c_), st(st_ ? st_ : c_->stream) {
-        if (c->profiling) {
+        if (name && c->profiling) {
             pe = &c->prof[name];
             a = get_event(c);
             b = get_event(c);
@@ -698,11 +700,20 @@ extern "C" int csr_get_run_stats(csr_ctx *c, csr_run_stats *out) {
     return 0;
 }
 
-#define LAUNCH_CHECK(name)                                                              \
-    do {                                                                                \
-        hipError_t e_ = hipGetLastError();                                              \
-        if (e_ != hipSuccess) return fail("launch %s failed: %s", name, hipGetErrorString(e_)); \
-    } while (0)
+// Every kernel launch of the host layer: profile scope `scope` on the launch's stream (nullptr: none), the launch, and its
+// own error check under the kernel's name `what`.  A site that chooses among template instances computes the pointer (and
+// the dynamic LDS that goes with it) first and launches once.
+template <class... P, class... A>
+static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds,
+                  hipStream_t st, A &&...args) {
+    {
+        Scope sc(c, scope, st);
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, std::forward<A>(args)...);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("launch %s failed: %s", what, hipGetErrorString(e));
+    return 0;
+}
 
 // The rest of the host library, split by concern (same translation unit, order matters: later parts use earlier ones)
 #include "csr_host_batch.inl"
