@@ -3247,7 +3247,7 @@ __global__ __launch_bounds__(64) void k_chain_fix(Prm p_, int which) {
 // NIS / NLL per bin (pyx:458-475) from the stored predicted covariance, the previous filtered state and the bin
 // statistics; per-block partial sums give deterministic sumD / sumNLL.
 template <bool NATD>
-__global__ __launch_bounds__(256) void k_fwd_dstat(Prm p) {
+__device__ __forceinline__ void fwd_dstat_blocked(const Prm &p) {
     __shared__ double redD[4][64], redN[4][64];
     // NATD: D leaves the kernel in the reference layout -- the workgroup's 64 blocks x B steps are staged in LDS
     // ([lane][B + 1] floats, dynamic) and written as one contiguous run of B floats per block; no tD, no export pass
@@ -3339,6 +3339,136 @@ __global__ __launch_bounds__(256) void k_fwd_dstat(Prm p) {
             if (st < dLen[L]) p.natD[(int64_t)dBase[L] + st] = dTile[L * (p.B + 1) + st];
         }
     }
+}
+
+// NATX: the previous filtered state comes from the reference layout, where the bit-exact state chain wrote it (p.natXfIn) -- no
+// blocked copy of xf has to exist.  Same lanes-are-blocks shape, same arithmetic per bin, same order of the sums (per quarter in
+// ascending bin order, then ((q0 + q1) + q2) + q3).  A quarter is walked in two chunks of B / 8 steps: the chunk's runs of
+// {x0, x1} (B / 8 consecutive bins per block and quarter) come in coalesced through the LDS tile that the blocked-input form
+// uses for D alone -- [64][B + 1] floats, the pair of step r of a lane at floats 2r, 2r + 1 -- and the slot that held the
+// previous state of (block, step) receives that step's D: the thread that reads the first writes the second.  D then leaves
+// the tile in runs of B / 8 floats per block and quarter.
+// dLen[]: the block's length, bit 30 = the block is not its chain's first (the bin in front of it is the previous state of step 0)
+__device__ __forceinline__ void fwd_dstat_natx(const Prm &p) {
+    __shared__ double redD[4][64], redN[4][64];
+    extern __shared__ float dTile[];
+    __shared__ int dBase[64], dLen[64];
+    constexpr int HAS_PREV = 1 << 30;
+    const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
+    const int64_t b = (int64_t)blockIdx.x * 64 + lane;
+    const bool live = b < p.NB && chain_on(p, b);
+    const int RS = p.B + 1;
+    const int q4 = p.B >> 2, CH = p.B >> 3, per = p.B >> 1;     // steps per quarter, per chunk of a quarter; pairs per lane and chunk
+    int4 bi = make_int4(0, 0, 0, 0);
+    if (live) bi = p.blk[b];
+    if (part == 0) { dBase[lane] = bi.x; dLen[lane] = bi.y | ((live && b > bi.z) ? HAS_PREV : 0); }
+    if (!__syncthreads_or(live)) return;        // (a launch under a chain mask: most workgroups of an early group have nothing to do)
+    double sumD = 0.0, sumN = 0.0;
+    const int sBeg = part * q4;
+    const int sEnd = (sBeg + q4 < bi.y) ? sBeg + q4 : bi.y;      // (bi.y = 0 for a lane without a live block)
+    const double mD = (double)p.m;
+    const double log2pi = 1.8378770664093454835606594728112;
+    const bool wantNLL = (p.flags & F_NLL) != 0;
+    const int slots = 64 * per;
+    for (int j = 0; j < 2; ++j) {
+        // ---- the chunk's previous states: four independent loads per thread in flight
+        for (int e0 = threadIdx.x; e0 < slots; e0 += 1024) {
+            float2 v[4];
+            int at[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int e = e0 + k * 256;
+                at[k] = -1;
+                v[k] = make_float2(0.f, 0.f);
+                if (e >= slots) continue;
+                const int L = e / per, r = e - L * per;
+                const int pt = r / CH, u = r - pt * CH;
+                const int s = pt * q4 + j * CH + u;
+                const int lw = dLen[L];
+                if (s < (lw & (HAS_PREV - 1)) && (s > 0 || (lw & HAS_PREV))) {
+                    v[k] = p.natXfIn[(int64_t)dBase[L] + s - 1];
+                    at[k] = L * RS + 2 * r;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (at[k] >= 0) { dTile[at[k]] = v[k].x; dTile[at[k] + 1] = v[k].y; }
+        }
+        __syncthreads();
+        // ---- the chunk's steps of this lane's quarter (k_fwd_dstat's arithmetic, DU steps of loads together)
+        const int cBeg = sBeg + j * CH;
+        const int cEnd = (cBeg + CH < sEnd) ? cBeg + CH : sEnd;
+        const int64_t base = tbase(b, p.B);
+        const int mine = lane * RS + 2 * (part * CH - cBeg);      // pair of step s: dTile[mine + 2 s], dTile[mine + 2 s + 1]
+        constexpr int DU = 4;
+        for (int s0 = cBeg; s0 < cEnd; s0 += DU) {
+            double lamv[DU], xp0v[DU], ppv[DU], s0u[DU], zb[DU], s2c[DU], slr[DU];
+#pragma unroll
+            for (int u = 0; u < DU; ++u) {
+                const int s = s0 + u;
+                lamv[u] = 1.0; xp0v[u] = 0.0; ppv[u] = 0.0; s0u[u] = 0.0; zb[u] = 0.0; s2c[u] = 0.0; slr[u] = 0.0;
+                if (s >= cEnd) continue;
+                const int64_t i = base + (int64_t)s * 64;
+                if (p.flags & F_LAMBDA) lamv[u] = clampd((double)p.tLam[i], p.wMin, p.wMax);
+                double x0, x1;
+                if (s > 0 || b > bi.z) { x0 = dTile[mine + 2 * s]; x1 = dTile[mine + 2 * s + 1]; }
+                else { x0 = (double)(float)p.init; x1 = 0.0; }
+                xp0v[u] = r32(fma(p.F01, x1, p.F00 * x0));
+                ppv[u] = p.predCompact ? (double)p.tPP[i] : (double)p.tXin[i].z;
+                { const double2 sz = p.tSZ[i]; s0u[u] = sz.x; zb[u] = sz.y; }
+                s2c[u] = load_s2c(p, i);
+                if (wantNLL) slr[u] = load_logr(p, i);
+            }
+#pragma unroll
+            for (int u = 0; u < DU; ++u) {
+                const int s = s0 + u;
+                if (s >= cEnd) continue;
+                const double lam = lamv[u], pp = ppv[u];
+                const double S0 = lam * s0u[u];
+                const double dz = zb[u] - xp0v[u];
+                const double S1 = S0 * dz;
+                const double S2 = fma(S0, dz * dz, lam * s2c[u]);
+                const double is = 1.0 + pp * S0;
+                const double gl = pp * rcp_nr(is);
+                double quad = S2 - gl * (S1 * S1);
+                if (quad < 0.0) quad = 0.0;
+                double nll = 0.0;
+                if (wantNLL) {
+                    double SL = slr[u];
+                    if (p.flags & F_LAMBDA) SL -= mD * log_pos(lam);
+                    nll = 0.5 * (SL + log_pos(is) + quad + mD * log2pi);
+                    sumN += nll;
+                }
+                const float D = (float)((wantNLL && (p.flags & F_NLL_IN_D)) ? nll : quad / mD);
+                dTile[mine + 2 * s] = D;
+                sumD += (double)D;
+            }
+        }
+        __syncthreads();
+        // ---- the chunk's D to the reference layout
+        for (int e = threadIdx.x; e < slots; e += 256) {
+            const int L = e / per, r = e - L * per;
+            const int pt = r / CH, u = r - pt * CH;
+            const int s = pt * q4 + j * CH + u;
+            if (s < (dLen[L] & (HAS_PREV - 1))) p.natD[(int64_t)dBase[L] + s] = dTile[L * RS + 2 * r];
+        }
+        __syncthreads();
+    }
+    redD[part][lane] = sumD;
+    redN[part][lane] = sumN;
+    __syncthreads();
+    if (part == 0 && live) {
+        p.blkSumD[b] = ((redD[0][lane] + redD[1][lane]) + redD[2][lane]) + redD[3][lane];
+        p.blkSumNLL[b] = ((redN[0][lane] + redN[1][lane]) + redN[2][lane]) + redN[3][lane];
+    }
+}
+// NATX = false: the previous filtered state is read from the blocked xf.  NATX = true (state_dim 2, D in the reference layout): from
+// the reference-layout xf (fwd_dstat_natx)
+template <bool NATD, bool NATX = false>
+__global__ __launch_bounds__(256) void k_fwd_dstat(Prm p) {
+    static_assert(NATD || !NATX, "the reference-layout input form writes D in the reference layout");
+    if constexpr (NATX) fwd_dstat_natx(p);
+    else fwd_dstat_blocked<NATD>(p);
 }
 
 // per-chain sums in block order (fixed partition and fixed-shape tree: deterministic).  The partition is that of 1024 threads
@@ -3705,10 +3835,10 @@ __device__ __forceinline__ void resid_prologue_check(const Prm &p) {
     const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (b < p.NB) check_previous_stage(p, b, p.blk[b]);
 }
-__global__ __launch_bounds__(256) void k_resid(Prm p, const float *xsNat, int xsStride, float *resid, int64_t nBins) {
+// (wg: the workgroup's index within the run of bins [0, nBins) that the pointers start at)
+__device__ __forceinline__ void resid_dev(const Prm &p, const float *xsNat, int xsStride, float *resid, int64_t nBins, int64_t wg) {
     extern __shared__ float tileR[];                 // [m][65]
-    resid_prologue_check(p);
-    const int64_t g0 = (int64_t)blockIdx.x * 64;
+    const int64_t g0 = wg * 64;
     const int t = threadIdx.x;
     const int gl = t & 63, r0 = t >> 6;
     const int64_t g = g0 + gl;
@@ -3726,16 +3856,19 @@ __global__ __launch_bounds__(256) void k_resid(Prm p, const float *xsNat, int xs
         if (g0 + bin < nBins) resid[(g0 + bin) * (int64_t)p.m + j] = tileR[j * 65 + bin];
     }
 }
+__global__ __launch_bounds__(256) void k_resid(Prm p, const float *xsNat, int xsStride, float *resid, int64_t nBins) {
+    resid_prologue_check(p);
+    resid_dev(p, xsNat, xsStride, resid, nBins, (int64_t)blockIdx.x);
+}
 
 // vectorised variant for m % 4 == 0: 16-byte loads of four consecutive bins per sample row, 16-byte stores of four
 // consecutive samples of one bin.  One workgroup = K * 64 bins x m samples: K independent 16-byte loads per thread and
 // sweep are in flight together (K = 1 leaves the kernel latency-bound: 2 loads per thread at m = 32).
 template <int K>
-__global__ __launch_bounds__(256) void k_resid_v4(Prm p, const float *xsNat, int xsStride, float *resid, int64_t nBins) {
+__device__ __forceinline__ void resid_v4_dev(const Prm &p, const float *xsNat, int xsStride, float *resid, int64_t nBins, int64_t wg) {
     extern __shared__ float tileR[];                 // [m][K*64+4]: the row stride keeps float4 rows 16-B aligned
     constexpr int RS = K * 64 + 4;
-    resid_prologue_check(p);
-    const int64_t g0 = (int64_t)blockIdx.x * (K * 64);
+    const int64_t g0 = wg * (K * 64);
     const int t = threadIdx.x;
     const int q = t & 15, r0 = t >> 4;               // q: group of 4 bins, r0: sample row within a sweep of 16
     float x[K][4];
@@ -3783,6 +3916,37 @@ __global__ __launch_bounds__(256) void k_resid_v4(Prm p, const float *xsNat, int
             *reinterpret_cast<float4 *>(resid + (g0 + bin) * (int64_t)p.m + j) = o;
         }
     }
+}
+template <int K>
+__global__ __launch_bounds__(256) void k_resid_v4(Prm p, const float *xsNat, int xsStride, float *resid, int64_t nBins) {
+    resid_prologue_check(p);
+    resid_v4_dev<K>(p, xsNat, xsStride, resid, nBins, (int64_t)blockIdx.x);
+}
+
+// The residuals of several runs of bins in ONE launch (a tail group of a pipelined step: its chains are a few runs of consecutive
+// chains).  runs[0 .. nRuns): ascending in their first workgroup; a workgroup finds its run by bisection and then does exactly
+// what a workgroup of a launch over that run alone does.  (No folded check: a group covers a part of the batch.)
+struct ResidRun { int64_t off, len, wg0; };      // bins [off, off + len) of the reference layout, from workgroup wg0 of the launch on
+__device__ __forceinline__ int resid_find_run(const ResidRun *runs, int nRuns) {
+    int lo = 0, hi = nRuns - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (runs[mid].wg0 <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void k_resid_runs(Prm p, const float *xsNat, int xsStride, float *resid, const ResidRun *runs, int nRuns) {
+    const ResidRun r = runs[resid_find_run(runs, nRuns)];
+    p.data += r.off;
+    if (p.bg) p.bg += r.off;
+    resid_dev(p, xsNat + r.off * xsStride, xsStride, resid + r.off * p.m, r.len, (int64_t)blockIdx.x - r.wg0);
+}
+template <int K>
+__global__ __launch_bounds__(256) void k_resid_v4_runs(Prm p, const float *xsNat, int xsStride, float *resid, const ResidRun *runs, int nRuns) {
+    const ResidRun r = runs[resid_find_run(runs, nRuns)];
+    p.data += r.off;
+    if (p.bg) p.bg += r.off;
+    resid_v4_dev<K>(p, xsNat + r.off * xsStride, xsStride, resid + r.off * p.m, r.len, (int64_t)blockIdx.x - r.wg0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -159,10 +159,17 @@ static int fork_side(csr_ctx *c, hipEvent_t ev) {
     return 0;
 }
 // NIS / NLL epilogue (D in the reference layout goes through one LDS tile per block)
-static int launch_dstat(csr_ctx *c, const Prm &p, hipStream_t st) {
-    void (*const kernel)(Prm) = p.natD ? &k_fwd_dstat<true> : &k_fwd_dstat<false>;
+// natXf: the previous filtered state is read in the reference layout, where the bit-exact state chain wrote it, instead of from the
+// blocked xf (p.natD is set; the same tile, the same sums)
+static int launch_dstat(csr_ctx *c, const Prm &p, hipStream_t st, const float *natXf = nullptr) {
+    void (*kernel)(Prm) = p.natD ? &k_fwd_dstat<true> : &k_fwd_dstat<false>;
     const size_t lds = p.natD ? sizeof(float) * 64 * (c->B + 1) : 0;
-    return launch(c, "fwd_dstat", "k_fwd_dstat", kernel, dim3((int)c->NG), dim3(256), lds, st, p);
+    if (natXf == nullptr) return launch(c, "fwd_dstat", "k_fwd_dstat", kernel, dim3((int)c->NG), dim3(256), lds, st, p);
+    if (p.natD == nullptr || c->mdl.state_dim != 2 || (c->B % 32) != 0) return fail("internal: NIS / NLL epilogue from the reference-layout xf");
+    Prm q = p;
+    q.natXfIn = reinterpret_cast<const float2 *>(natXf);
+    kernel = &k_fwd_dstat<true, true>;
+    return launch(c, "fwd_dstat", "k_fwd_dstat<natXf>", kernel, dim3((int)c->NG), dim3(256), lds, st, q);
 }
 // per-chain sums of the per-block sums the epilogue (or the chain itself) left
 static int launch_chain_sums(csr_ctx *c, const Prm &p, hipStream_t st) {
@@ -540,6 +547,9 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
                 HIPOK(hipFuncSetAttribute(reinterpret_cast<const void *>(asyncFns[mode]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_ASYNC_LDS));
                 c->sbAsyncLdsRaised[mode] = true;
             }
+            // (a pipelined step's NIS / NLL epilogue groups run on the side stream while this launch runs: the side stream continues
+            // from HERE, behind the statistics and the covariance chain the epilogue reads; a chain's done word is the rest)
+            if (phase == 1 && c->tailEpilogue) CHECK(fork_side(c, c->evEpiFork));
             CHECK(launch(c, "fwd_state_chain", "k_sb_async", asyncFns[mode], dim3(grid), dim3(256), SB_ASYNC_LDS, c->stream, q, c->sbNatGain,
                          c->sbNatSZ, xf, a));
         }
@@ -561,7 +571,9 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
             c->rs.sb_bailouts++;
             if (c->dbgLog) fprintf(stderr, "[csr] fwd_state_chain (barrier-free superblocks): bailed out, running the pass form\n");
             // (a pipelined step may have tails of finished chains in flight that read the track the pass form rewrites)
+            // (... and epilogue groups on the side stream that read it)
             if (resume && c->tail) HIPOK(hipStreamSynchronize(c->tail));
+            if (resume && c->side) HIPOK(hipStreamSynchronize(c->side));
         }
     }
     if (!done)
@@ -737,6 +749,8 @@ static int forward_impl(csr_ctx *c, const FwdPass &pass) {
             bool ok = true;
             if (tileBytes > 48 * 1024 && !c->dstatLdsRaised) {      // 256-bin blocks: 65.8 KB of dynamic LDS
                 ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fwd_dstat<true>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)tileBytes) == hipSuccess &&
+                     hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fwd_dstat<true, true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)tileBytes) == hipSuccess;
                 (void)hipGetLastError();
                 c->dstatLdsRaised = ok;
@@ -1298,6 +1312,19 @@ static int need_natural_mult(csr_ctx *c, ExpList &L, int id) {
     return need_natural(c, L, id, id == CSR_ARR_LAMBDA ? c->p.tLam : (id == CSR_ARR_KAPPA ? c->p.tKap : c->p.tQs), 1, 1, 0);
 }
 
+// The form of the residual kernels for this batch: K 64-bin sub-tiles per workgroup, rows of m floats padded by `padRows` rows in
+// LDS: the 16-byte form (m a multiple of 4) with K = 2 (measured best: 0.665 vs 0.684 ms with 1 or 4, round 3) while its tile
+// fits 64 KB, else with K = 1
+struct ResidForm { bool v4; int K; size_t lds; };
+static ResidForm resid_form(const csr_ctx *c) {
+    int K = 1, padRows = 1;
+    const bool v4 = (c->m & 3) == 0;
+    if (v4) {
+        padRows = 4;
+        K = sizeof(float) * (size_t)(2 * 64 + 4) * c->m <= 65536 ? 2 : 1;
+    }
+    return {v4, K, sizeof(float) * (size_t)(K * 64 + padRows) * c->m};
+}
 // residuals of the bins [off, off + nb) of the batch's natural layout (whole chains: off and nb are multiples of 64)
 static int launch_resid(csr_ctx *c, int64_t off, int64_t nb, bool foldCheck) {
     const int d = c->mdl.state_dim;
@@ -1313,19 +1340,30 @@ static int launch_resid(csr_ctx *c, int64_t off, int64_t nb, bool foldCheck) {
     if (pr.bg) pr.bg += off;
     xs += off * d;
     res += off * c->m;
-    // K 64-bin sub-tiles per workgroup, rows of m floats padded by `padRows` rows in LDS: the 16-byte form (m a multiple of 4)
-    // with K = 2 (measured best: 0.665 vs 0.684 ms with 1 or 4, round 3) while its tile fits 64 KB, else with K = 1
-    void (*kernel)(Prm, const float *, int, float *, int64_t) = &k_resid;
-    int K = 1, padRows = 1;
-    if ((c->m & 3) == 0) {
-        padRows = 4;
-        const bool two = sizeof(float) * (size_t)(2 * 64 + 4) * c->m <= 65536;
-        K = two ? 2 : 1;
-        kernel = two ? &k_resid_v4<2> : &k_resid_v4<1>;
-    }
-    const size_t lds = sizeof(float) * (size_t)(K * 64 + padRows) * c->m;
-    const dim3 grid((unsigned)((nb + K * 64 - 1) / (K * 64)));
-    return launch(c, "residuals", "k_resid", kernel, grid, dim3(256), lds, c->stream, pr, xs, d, res, nb);
+    const ResidForm f = resid_form(c);
+    void (*const kernel)(Prm, const float *, int, float *, int64_t) = f.v4 ? (f.K == 2 ? &k_resid_v4<2> : &k_resid_v4<1>) : &k_resid;
+    const dim3 grid((unsigned)((nb + f.K * 64 - 1) / (f.K * 64)));
+    return launch(c, "residuals", "k_resid", kernel, grid, dim3(256), f.lds, c->stream, pr, xs, d, res, nb);
+}
+// residuals of `n` runs of whole chains (host copy `runs`, wg0 filled in here; device copy `dRuns`, uploaded on c->stream from the
+// pinned `runs`) in ONE launch: each workgroup does what it does in a launch over its run alone
+static int launch_resid_runs(csr_ctx *c, ResidRun *runs, ResidRun *dRuns, int n) {
+    if (n == 0) return 0;
+    const int d = c->mdl.state_dim;
+    float *xs, *res;
+    CHECK(nat_array(c, CSR_ARR_XS, &xs));
+    CHECK(nat_array(c, CSR_ARR_RESID, &res));
+    Prm pr = c->p;
+    pr.xTolUlps = c->xTolUlps;
+    pr.prevKind = CK_NONE;
+    const ResidForm f = resid_form(c);
+    int64_t wgs = 0;
+    for (int i = 0; i < n; ++i) { runs[i].wg0 = wgs; wgs += (runs[i].len + f.K * 64 - 1) / (f.K * 64); }
+    HIPOK(hipMemcpyAsync(dRuns, runs, sizeof(ResidRun) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    void (*const kernel)(Prm, const float *, int, float *, const ResidRun *, int) =
+        f.v4 ? (f.K == 2 ? &k_resid_v4_runs<2> : &k_resid_v4_runs<1>) : &k_resid_runs;
+    return launch(c, "residuals", "k_resid_runs", kernel, dim3((unsigned)wgs), dim3(256), f.lds, c->stream, pr, (const float *)xs, d, res,
+                  (const ResidRun *)dRuns, n);
 }
 
 static int export_impl(csr_ctx *c, uint32_t what) {
@@ -1394,14 +1432,36 @@ static int export_impl(csr_ctx *c, uint32_t what) {
 // chains of `dmask` (device bytes, nullptr = all), on c->stream.  `runs`: the maximal runs of those chains as bin ranges of the
 // natural layout.
 struct ChainRun { int64_t off, len, b0, b1; };     // bins [off, off + len) of the natural layout = blocks [b0, b1) of the batch
-static int step_tail(csr_ctx *c, const Prm &pf, const unsigned char *dmask, const std::vector<ChainRun> &runs, uint32_t what) {
+// one constant process noise: the smoother of a tail group reads xf / Pf of its chains in the reference layout (k_smooth_natin)
+static bool tail_reads_nat(csr_ctx *c, const Prm &pf) {
+    return c->natInEnabled && c->where[CSR_ARR_PF].nat && const_q(c) && pf.chainQ == nullptr && (c->B % 8) == 0 &&
+           (stage_warm(c, ST_B) % 8) == 0 && unit_f(pf);
+}
+// epi: the NIS / NLL epilogue runs in groups of its own (step_pipelined) -- the tail is the smoother (behind a blocked copy of xf
+// only where it reads blocks) and ONE residual launch over the group's runs (table `hRuns` / `dRuns`, launch_resid_runs)
+static int step_tail(csr_ctx *c, const Prm &pf, const unsigned char *dmask, const std::vector<ChainRun> &runs, uint32_t what, bool epi = false,
+                     ResidRun *hRuns = nullptr, ResidRun *dRuns = nullptr) {
     Prm pt = pf;
     pt.chainActive = dmask;
     pt.prevKind = CK_NONE;
     // one constant process noise: the smoother reads xf / Pf of these chains in the reference layout (k_smooth_natin) and starts
     // at once; the blocked copy of xf only the NIS / NLL epilogue needs is made on the side stream in front of it
-    const bool natTail = c->natInEnabled && c->where[CSR_ARR_PF].nat && const_q(c) && pf.chainQ == nullptr && (c->B % 8) == 0 &&
-                         (stage_warm(c, ST_B) % 8) == 0 && unit_f(pf);
+    const bool natTail = tail_reads_nat(c, pf);
+    if (epi) {
+        if (!natTail && !runs.empty()) {
+            int64_t g0 = runs.front().b0 / 64, g1 = (runs.front().b1 + 63) / 64;
+            for (const ChainRun &r : runs) { g0 = std::min(g0, r.b0 / 64); g1 = std::max(g1, (r.b1 + 63) / 64); }
+            CHECK(import_xf_blocked(c, pt, c->stream, g0, g1 - g0));
+        }
+        CHECK(backward_impl(c, {.active = dmask, .defer = true, .natOut = true, .preferNatIn = natTail}));
+        CHECK(flush_pending_check(c));
+        if (what & CSR_EXPORT_RESID) {
+            int n = 0;
+            for (const ChainRun &r : runs) hRuns[n++] = ResidRun{r.off, r.len, 0};
+            CHECK(launch_resid_runs(c, hRuns, dRuns, n));
+        }
+        return 0;
+    }
     CHECK(fork_side(c, c->evFork));
     hipStream_t imp = natTail ? c->side : c->stream;
     // (the smoother is what the group's residuals wait for: when it reads the reference layout it is launched FIRST, the
@@ -1429,9 +1489,11 @@ static int step_tail(csr_ctx *c, const Prm &pf, const unsigned char *dmask, cons
 // A step of the bit-exact mode whose tail is PIPELINED PER CHAIN behind the barrier-free state chain.  That launch lasts as
 // long as the slowest chain needs (3.7 ms at genome scale) while most chains are final a millisecond earlier, and it leaves the
 // memory system idle.  The kernel sets a host-visible word per chain when the chain is final; the host watches those words and,
-// whenever the newly finished chains make up an eighth of the batch, launches their tail (blocked copy of xf, NIS / NLL
-// epilogue, smoother, residuals; every kernel under a chain mask) on a second stream; the remainder follows when the state
-// chain has ended.  Same kernels, same results; a chain's tail simply starts when ITS filtered state stands.
+// whenever the newly finished chains make up tailFirstPct / tailNextPct per cent of the batch, launches their tail (smoother,
+// residuals; every kernel under a chain mask) on a second stream; the remainder follows when the state chain has ended.  The
+// NIS / NLL epilogue goes out in groups of its own on the side stream (epiPct per cent of the batch each): it needs the final xf
+// alone.  Same arithmetic, same results; a chain's tail simply starts when ITS filtered state stands.
+// (CONSENRICH_AMD_TAIL_EPILOGUE=0: the tails carry the epilogue, behind a blocked copy of xf, as they did before.)
 static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handled) {
     *handled = false;
     // (round 4: per-bin multipliers and per-chain base matrices pipeline as well -- their process noise goes to the reference
@@ -1465,6 +1527,33 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     if (!c->dMask[0]) for (auto &m : c->dMask) CHECK(dalloc(c, &m, nc));
     if (!c->hMaskPin) CHECK(c->hMaskPin.alloc(8 * (size_t)nc, hipHostMallocDefault));
     std::vector<unsigned char> tailed((size_t)nc, 0);
+    // NIS / NLL epilogue in groups of its own on the side stream (k_fwd_dstat<natXf> reads the previous filtered state where the state
+    // chain wrote it): it needs a chain's final xf and nothing of the smoother, and memory is idle under the state chain -- a group
+    // goes out whenever the final chains without an epilogue make up epiPct % of the batch, the remainder when the launch has ended
+    const bool epi = c->tailEpilogue && (c->B % 32) == 0;
+    const bool natTail = tail_reads_nat(c, pf);
+    std::vector<unsigned char> epid((size_t)nc, 0);
+    int epiGroups = 0;
+    float *natXf = nullptr;
+    if (epi) {
+        CHECK(nat_array(c, CSR_ARR_XF, &natXf));
+        if (!c->dEpiMask[0]) for (auto &m : c->dEpiMask) CHECK(dalloc(c, &m, nc));
+        if (!c->hEpiMaskPin) CHECK(c->hEpiMaskPin.alloc(9 * (size_t)nc, hipHostMallocDefault));
+        if (!c->dRuns[0]) for (auto &r : c->dRuns) CHECK(dalloc(c, &r, nc));
+        if (!c->hRunsPin) CHECK(c->hRunsPin.alloc(8 * (size_t)nc, hipHostMallocDefault));
+    }
+    auto launch_epilogue = [&](const std::vector<unsigned char> &grp) -> int {
+        unsigned char *dm = c->dEpiMask[epiGroups];
+        unsigned char *hm = c->hEpiMaskPin + (size_t)epiGroups * (size_t)nc;
+        std::copy(grp.begin(), grp.end(), hm);
+        HIPOK(hipMemcpyAsync(dm, hm, (size_t)nc, hipMemcpyHostToDevice, c->side));
+        Prm pe = pf;
+        pe.chainActive = dm;
+        pe.prevKind = CK_NONE;
+        CHECK(launch_dstat(c, pe, c->side, natXf));
+        ++epiGroups;
+        return 0;
+    };
     int phase = 0;
     bool any = false;
     hipStream_t mainStream = c->stream;
@@ -1484,7 +1573,8 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
         unsigned char *hm = c->hMaskPin + (size_t)phase * (size_t)nc;
         std::copy(grp.begin(), grp.end(), hm);
         HIPOK(hipMemcpyAsync(dm, hm, (size_t)nc, hipMemcpyHostToDevice, c->stream));
-        CHECK(step_tail(c, pf, dm, runs, what));
+        if (epi) CHECK(step_tail(c, pf, dm, runs, what, true, c->hRunsPin + (size_t)phase * (size_t)nc, c->dRuns[phase]));
+        else CHECK(step_tail(c, pf, dm, runs, what));
         ++phase;
         any = true;
         return 0;
@@ -1502,7 +1592,20 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
         const double el = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tLoop).count();
         if (qs != hipErrorNotReady) { if (qs != hipSuccess) rc = fail("state chain: %s", hipGetErrorString(qs)); else c->lastSbLoopUs = el; break; }
         // (bounded sleep-poll: the launch lasts milliseconds and a tail group is worth launching 20-50 us late; round 3 spun here)
-        if (!(expectEnd > 0.0 && el > expectEnd - 100.0 && el < expectEnd + 200.0)) std::this_thread::sleep_for(std::chrono::microseconds(20));
+        const bool nearEnd = expectEnd > 0.0 && el > expectEnd - 100.0 && el < expectEnd + 200.0;
+        if (!nearEnd) std::this_thread::sleep_for(std::chrono::microseconds(20));
+        // (an epilogue group is an upload and a launch: never inside the interval in which the end of the state chain is expected)
+        if (epi && c->epiPct > 0 && epiGroups < 8 && !nearEnd) {
+            std::vector<unsigned char> eg((size_t)nc, 0);
+            int64_t ebins = 0;
+            for (int i = 0; i < nc; ++i)
+                if (!epid[(size_t)i] && __atomic_load_n(&c->hDone[i], __ATOMIC_ACQUIRE) != 0u) { eg[(size_t)i] = 1; ebins += c->chains[(size_t)i].n; }
+            if (ebins > 0 && ebins * 100 >= total * c->epiPct) {
+                rc = launch_epilogue(eg);
+                if (rc) break;
+                for (int i = 0; i < nc; ++i) if (eg[(size_t)i]) epid[(size_t)i] = 1;
+            }
+        }
         if (phase >= 6) continue;
         std::vector<unsigned char> grp((size_t)nc, 0);
         int64_t bins = 0;
@@ -1520,9 +1623,11 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     // pass form rewrites the whole track from the cold prior: the tails already launched are waited for and everything is redone)
     const int64_t bail0 = c->rs.sb_bailouts;
     CHECK(state_chain_systolic(c, pf, false, flags, 2));
-    if (c->rs.sb_bailouts != bail0 && any) {
+    if (c->rs.sb_bailouts != bail0 && (any || epiGroups > 0)) {
         HIPOK(hipStreamSynchronize(c->tail));
+        HIPOK(hipStreamSynchronize(c->side));
         std::fill(tailed.begin(), tailed.end(), (unsigned char)0);
+        std::fill(epid.begin(), epid.end(), (unsigned char)0);
     }
     // ---- the remaining chains: on the main stream, behind the state chain and beside whatever the tail stream still has to do
     // (groups are disjoint sets of chains, hence of blocks: their kernels share no data; every group leaves no folded check behind)
@@ -1530,8 +1635,21 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     bool anyRest = false;
     for (int i = 0; i < nc; ++i) if (!tailed[(size_t)i]) { rest[(size_t)i] = 1; anyRest = true; }
     if (anyRest) CHECK(launch_group(rest));
+    // ---- the epilogue of the chains that have none yet, on the side stream (the state chain has ended: nothing to wait for)
+    if (epi) {
+        std::vector<unsigned char> er((size_t)nc, 0);
+        bool anyEr = false;
+        for (int i = 0; i < nc; ++i) if (!epid[(size_t)i]) { er[(size_t)i] = 1; anyEr = true; }
+        if (anyEr) CHECK(launch_epilogue(er));
+        HIPOK(hipEventRecord(c->evEpiJoin, c->side));
+    }
     HIPOK(hipEventRecord(c->evTailJoin, c->tail));
     HIPOK(hipStreamWaitEvent(mainStream, c->evTailJoin, 0));
+    if (epi) {
+        HIPOK(hipStreamWaitEvent(mainStream, c->evEpiJoin, 0));
+        // (no blocked copy of xf was made where the smoother read the reference layout: later readers of blocks bring it back)
+        if (natTail) produced(c, {CSR_ARR_XF}, W_NAT);
+    }
     Prm ps = pf;
     ps.chainActive = nullptr;
     CHECK(launch_chain_sums(c, ps, c->stream));

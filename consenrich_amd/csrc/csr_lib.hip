@@ -282,6 +282,12 @@ struct BatchState {
     unsigned int *dDone = nullptr;      // ... and their device alias
     unsigned char *dMask[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     PinBuf<unsigned char> hMaskPin;     // pinned staging of the eight masks (an upload from pageable memory may hold the host)
+    // step_pipelined, NIS / NLL epilogue groups of their own (side stream): up to eight early masks and the remainder's, with their
+    // pinned staging; and the run tables of the tail groups' residual launches (k_resid_runs), one per tail mask
+    unsigned char *dEpiMask[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PinBuf<unsigned char> hEpiMaskPin;
+    ResidRun *dRuns[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PinBuf<ResidRun> hRunsPin;
     bool pfPending = false;
     // the reference-layout process-noise array holds the constant fill of THESE values in every row (k_fill_rows): a step with the
     // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)
@@ -331,7 +337,7 @@ struct csr_ctx : BatchState {
     int xTolUlps = 0;           // carry validation: 0 = bit-exact sequential semantics (DEFAULT of every context since round 3: the
                                 // only mode that holds the parity gate through the ECM loop on ill-conditioned data, tests/test_hard_data.py);
                                 // k > 0 = k-ulp acceptance, the opt-in throughput mode (csr_set_validation / CONSENRICH_AMD_XTOL_ULPS)
-    bool dstatLdsRaised = false;
+    bool dstatLdsRaised = false;        // (both reference-layout-output instances of k_fwd_dstat)
     bool natInEnabled = true;           // CONSENRICH_AMD_NATIN=0 (tests): the smoother never reads the reference layout -- blocked copies
                                         // a forward pass did not write are brought back first (need_blocked)
     double lastSbLoopUs = 0.0;          // how long the host watched the previous single launch of the state chain (step_pipelined)
@@ -370,6 +376,9 @@ struct csr_ctx : BatchState {
     // step_pipelined: tails of the chains whose filtered state stands, on a stream of their own while the state chain runs
     hipStream_t tail = nullptr;
     hipEvent_t evTailJoin = nullptr;
+    // ... and their NIS / NLL epilogue in groups of its own on the side stream, which continues from the point of the main stream
+    // right in front of the state chain (evEpiFork); the main stream waits for evEpiJoin before the per-chain sums
+    hipEvent_t evEpiFork = nullptr, evEpiJoin = nullptr;
     // first-use zeroing of a reference-layout array (nat_array) runs HERE and is waited for by the host before the array is
     // handed out: it is ordered against no other stream, so it does not matter which stream the caller is on at that moment
     hipStream_t zeroStream = nullptr;
@@ -378,6 +387,11 @@ struct csr_ctx : BatchState {
     // 50 / 15) -- tail kernels take issue slots from the walking wavefronts, so fewer, later groups win (profiles/r04_tail_sweep.txt)
     int tailFirstPct = 60, tailNextPct = 40;
     bool tailSplit = true;      // CONSENRICH_AMD_TAIL_SPLIT=0: a step's tail follows the state chain for all chains at once
+    // CONSENRICH_AMD_TAIL_EPILOGUE=0: the epilogue runs inside the tail groups again, behind a blocked copy of xf, and a group's
+    // residuals are one launch per run of chains (the A/B yardstick of the epilogue groups).  CONSENRICH_AMD_EPILOGUE_PCT: share of
+    // the batch's bins that final chains without an epilogue must reach for an early epilogue group (0: no early groups)
+    bool tailEpilogue = true;
+    int epiPct = 10;
     // ROCCO (csr_host_rocco.inl): tuning, counters and growable work space; the batch's tracks are BatchState::rocco
     struct RoccoWs {
         int depth = 0;          // speculation depth of the calibration (0 = default)
@@ -470,6 +484,7 @@ static int dalloc(csr_ctx *c, T **ptr, int64_t count) {
 // free what they own when they are assigned to).  The device must be selected.
 static void free_batch(csr_ctx *c) {
     if (c->tail) (void)hipStreamSynchronize(c->tail);
+    if (c->side) (void)hipStreamSynchronize(c->side);
     for (void *q : c->allocs) (void)hipFree(q);
     static_cast<BatchState &>(*c) = BatchState{};
 }
@@ -510,7 +525,9 @@ extern "C" csr_ctx *csr_create(int device_ordinal) {
         hipEventCreateWithFlags(&c->evPf, hipEventDisableTiming) != hipSuccess ||
         hipStreamCreateWithFlags(&c->tail, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->zeroStream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evTailJoin, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->evTailJoin, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->evEpiFork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->evEpiJoin, hipEventDisableTiming) != hipSuccess) {
         fail("cannot create the side stream of device %d", device_ordinal);
         delete c;
         return nullptr;
@@ -543,6 +560,8 @@ extern "C" csr_ctx *csr_create(int device_ordinal) {
         int a = 60, b = 40;
         if (sscanf(e, "%d,%d", &a, &b) >= 1) { c->tailFirstPct = std::min(100, std::max(1, a)); c->tailNextPct = std::min(100, std::max(1, b)); }
     }
+    if ((e = getenv("CONSENRICH_AMD_TAIL_EPILOGUE"))) c->tailEpilogue = atoi(e) != 0;
+    if ((e = getenv("CONSENRICH_AMD_EPILOGUE_PCT"))) c->epiPct = std::min(100, std::max(0, atoi(e)));
     if ((e = getenv("CONSENRICH_AMD_SB_SPIN_LIMIT"))) c->sbSpinLimit = std::max(1, atoi(e));
     c->dbgLog = getenv("CONSENRICH_AMD_DEBUG") != nullptr;
     mode_warm_defaults(c);
@@ -568,6 +587,8 @@ extern "C" void csr_destroy(csr_ctx *c) {
     if (c->evFork2) (void)hipEventDestroy(c->evFork2);
     if (c->evPf) (void)hipEventDestroy(c->evPf);
     if (c->evTailJoin) (void)hipEventDestroy(c->evTailJoin);
+    if (c->evEpiFork) (void)hipEventDestroy(c->evEpiFork);
+    if (c->evEpiJoin) (void)hipEventDestroy(c->evEpiJoin);
     if (c->tail) { (void)hipStreamSynchronize(c->tail); (void)hipStreamDestroy(c->tail); }
     if (c->zeroStream) (void)hipStreamDestroy(c->zeroStream);
     if (c->side) (void)hipStreamDestroy(c->side);

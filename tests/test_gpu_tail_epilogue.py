@@ -1,0 +1,199 @@
+"""GPU tests (run with -m gpu) of the default-mode step whose NIS / NLL epilogue runs in groups of its own on the side stream while
+the state chain is still running (step_pipelined, csr_host_pipeline.inl): `k_fwd_dstat<natXf>` reads the previous filtered state
+where the state chain wrote it (no blocked copy of xf), and a tail group's residuals are ONE launch over a table of runs
+(`k_resid_runs`, `k_resid_v4_runs`).  Same arithmetic in the same order: every output equals, bit for bit, the step in order
+(CONSENRICH_AMD_TAIL_SPLIT=0) and the step whose tails carry the epilogue (CONSENRICH_AMD_TAIL_EPILOGUE=0).
+
+Small shapes on purpose: chains shorter than, equal to and just past one block of every block length, a chain of one bin, chains of
+several superblocks (CONSENRICH_AMD_SB_BINS=4096); m = 4 takes the 16-byte residual kernel, m = 5 the plain one.
+
+The smoother's speculation window is pinned at 384 bins (CONSENRICH_AMD_WARM=-1,-1,384).  With one constant process noise the
+default 128 bins do not validate bit for bit on this data at any of the three block lengths -- the step in order of the commit
+before this one re-runs 2 to 72 smoother blocks in its first step, widens the window to 192 / 384 bins and replays the pipeline
+once (pipeline_redos = 1), after which the second step validates.  A replayed step's outputs come from the in-order kernels of
+settle(), so such a first step would compare nothing of the pipelined path; at 384 bins both steps validate and both are compared
+with `pipeline_redos == 0`."""
+import os
+
+import numpy as np
+import pytest
+
+import cases
+from conftest import gpu_available
+
+pytestmark = pytest.mark.gpu
+
+N_LIST = [1, 63, 64, 65, 127, 128, 129, 257, 4097, 8193, 20000]
+NAMES = ("D", "xf", "Pf", "pnoise", "xs", "Ps", "lag", "resid")
+OWN = ("CONSENRICH_AMD_TAIL_SPLIT", "CONSENRICH_AMD_TAIL_EPILOGUE", "CONSENRICH_AMD_TAIL_PCT", "CONSENRICH_AMD_SB_SPIN_LIMIT",
+       "CONSENRICH_AMD_EPILOGUE_PCT")
+
+
+@pytest.fixture(scope="module")
+def product():
+    if not gpu_available():
+        pytest.fail("GPU tests selected but no HIP device / library: the product has no CPU fallback")
+    from consenrich_amd import cconsenrich
+
+    return cconsenrich
+
+
+def _pipelines():
+    """False when the suite runs under a mode switch (scripts/suite_variants.sh) that keeps a bit-exact step from pipelining at all:
+    the comparisons still hold, the counts of groups and bail-outs do not apply."""
+    e = os.environ.get
+    return (e("CONSENRICH_AMD_SB_ASYNC", "1") != "0" and e("CONSENRICH_AMD_SEQ_STATE", "0") == "0" and e("CONSENRICH_AMD_DEFER", "1") != "0"
+            and e("CONSENRICH_AMD_XTOL_ULPS", "0") == "0")
+
+
+@pytest.fixture(scope="module")
+def inputs():
+    """The chains' data (computed once, never changed): per m, per chain (data, munc); multipliers per chain."""
+    sets = {m: [cases.synth(n, m, 9100 + 10 * m + c, mask_frac=0.01, outlier_frac=0.01) for c, n in enumerate(N_LIST)] for m in (4, 5)}
+    mult = [cases.multipliers(n, 9300 + c) for c, n in enumerate(N_LIST)]
+    return sets, mult
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+def _flags(variant):
+    from consenrich_amd import _lib as L
+
+    flags = L.RETURN_NLL
+    if variant == "multipliers":
+        flags |= L.USE_LAMBDA | L.USE_KAPPA | L.USE_QSCALE
+    if variant == "nll_in_d":
+        flags |= L.NLL_IN_D
+    return flags
+
+
+def _run(monkeypatch, inputs, env, m, block, variant, profile=False):
+    """Two steps of a fresh batch: every array of every chain after the first and after the second, both sums, the run counters."""
+    from consenrich_amd import _lib as L
+    from consenrich_amd.batch import DeviceBatch, ModelParams
+
+    sets, mult = inputs
+    for k in OWN:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("CONSENRICH_AMD_BLOCK", str(block))
+    monkeypatch.setenv("CONSENRICH_AMD_SB_BINS", "4096")
+    monkeypatch.setenv("CONSENRICH_AMD_WARM", "-1,-1,384")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    what = L.EXPORT_FORWARD | L.EXPORT_SMOOTH | L.EXPORT_RESID
+    flags = _flags(variant)
+    out = {}
+    with DeviceBatch(0) as b:
+        b.configure(ModelParams(state_dim=2), m, N_LIST)
+        for c, (d_, v_) in enumerate(sets[m]):
+            b.upload(c, d_, v_)
+            if variant == "multipliers":
+                lam, kap, qs = mult[c]
+                b.upload_multipliers(c, lam, np.clip(kap, 0.25, 4.0), qs)
+        if variant == "per_chain_q":
+            b.set_chain_q([np.diag([1e-3 * (1 + c), 1e-4 * (1 + 0.5 * c)]).astype(np.float32) for c in range(len(N_LIST))])
+        if profile:
+            b.profile(True)
+        for step in range(2):
+            sd, sn = b.step(flags, what)
+            out[("sumD", step)], out[("sumNLL", step)] = np.array(sd), np.array(sn)
+            for c in range(len(N_LIST)):
+                for name in NAMES:
+                    out[(c, name, step)] = b.download(c, name)
+        if profile:
+            out["launches"] = {k: v[0] for k, v in b.kernel_times().items()}
+            b.profile(False)
+        out["stats"] = b.run_stats()
+    return out
+
+
+def _assert_same(got, ref, msg):
+    for key, val in ref.items():
+        if key in ("stats", "launches"):
+            continue
+        assert np.array_equal(_bits(val), _bits(got[key])), (msg, key)
+
+
+@pytest.mark.parametrize("variant", ["plain", "multipliers", "nll_in_d", "per_chain_q"])
+@pytest.mark.parametrize("block", [64, 128, 256])
+@pytest.mark.parametrize("m", [4, 5])
+def test_epilogue_groups_and_table_residuals_equal_the_step_in_order_and_the_old_tails(product, monkeypatch, inputs, m, block, variant):
+    """D, xf, Pf, pNoise, xs, Ps, lag, resid, sumD and sumNLL of the first and of the second step of a fresh batch, bit for bit:
+    the default step (tail thresholds unset, and at 1 % so that nearly every finished chain is a group) against (i) the step in
+    order and (ii) the step whose tails carry the epilogue; no replay and no bail-out in any of them.  Then with a wait bound of
+    one poll (CONSENRICH_AMD_SB_SPIN_LIMIT=1): the single launch gives up under the groups in flight, everything is redone behind
+    the pass form, and the outputs equal (i)."""
+    in_order = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_SPLIT": "0"}, m, block, variant)
+    old_tails = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_EPILOGUE": "0"}, m, block, variant)
+    assert in_order["stats"]["tail_groups"] == 0
+    for ref in (in_order, old_tails):
+        assert ref["stats"]["pipeline_redos"] == 0 and ref["stats"]["sb_bailouts"] == 0, ref["stats"]
+    _assert_same(old_tails, in_order, "tails with the epilogue against the step in order")
+    for env in ({}, {"CONSENRICH_AMD_TAIL_PCT": "1,1"}, {"CONSENRICH_AMD_TAIL_PCT": "1,1", "CONSENRICH_AMD_EPILOGUE_PCT": "1"}):
+        got = _run(monkeypatch, inputs, env, m, block, variant)
+        print(m, block, variant, env, got["stats"])
+        assert got["stats"]["pipeline_redos"] == 0 and got["stats"]["sb_bailouts"] == 0, (env, got["stats"])
+        if _pipelines():
+            assert got["stats"]["tail_groups"] >= 2, (env, got["stats"])        # two steps, at least one group each
+        _assert_same(got, in_order, (env, "against the step in order"))
+        _assert_same(got, old_tails, (env, "against the tails with the epilogue"))
+    bail = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_PCT": "1,1", "CONSENRICH_AMD_EPILOGUE_PCT": "1", "CONSENRICH_AMD_SB_SPIN_LIMIT": "1"},
+                m, block, variant)
+    print(m, block, variant, "bail-out", bail["stats"])
+    if _pipelines():
+        assert bail["stats"]["sb_bailouts"] >= 1, bail["stats"]
+    _assert_same(bail, in_order, "forced bail-out against the step in order")
+
+
+@pytest.mark.parametrize("m", [4, 5])
+def test_a_pipelined_step_launches_no_blocked_copy_of_xf_and_one_residual_kernel_per_group(product, monkeypatch, inputs, m):
+    """One constant process noise: the smoother of every tail group reads the reference layout, so nothing of the step reads a
+    blocked xf -- no `state_reblock_out` launch; the residuals are one launch per tail group; the epilogue ran at least once per
+    step.  With CONSENRICH_AMD_TAIL_EPILOGUE=0 the tails import xf again (one launch per group)."""
+    if not _pipelines() or os.environ.get("CONSENRICH_AMD_NATIN", "1") == "0":
+        return      # (a mode switch of the whole suite: the step does not pipeline, or its smoother reads blocks)
+    new = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_PCT": "1,1", "CONSENRICH_AMD_EPILOGUE_PCT": "1"}, m, 128, "plain", profile=True)
+    print(new["launches"], new["stats"])
+    assert new["launches"].get("state_reblock_out", 0) == 0, new["launches"]
+    assert new["launches"]["residuals"] == new["stats"]["tail_groups"], (new["launches"], new["stats"])
+    assert new["launches"]["fwd_dstat"] >= 2, new["launches"]
+    old = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_PCT": "1,1", "CONSENRICH_AMD_TAIL_EPILOGUE": "0"}, m, 128, "plain", profile=True)
+    assert old["launches"]["state_reblock_out"] == old["stats"]["tail_groups"], (old["launches"], old["stats"])
+    assert old["launches"]["fwd_dstat"] == old["stats"]["tail_groups"], (old["launches"], old["stats"])
+
+
+@pytest.mark.parametrize("block", [64, 128, 256])
+def test_a_masked_forward_pass_after_such_a_step_leaves_the_other_chains_as_they_were(product, monkeypatch, inputs, block):
+    """After a pipelined step with one constant process noise the blocked xf is not resident (csr_ctx::where[] says so).  A masked
+    forward pass on one chain rewrites the blocked copies of ITS blocks: the other chains' blocks come back from the reference
+    layout first (need_blocked), so xf / D of another chain are unchanged -- as downloaded at once and, for xf / Pf and the
+    smoothed arrays, after a smoother pass and a new export of every chain."""
+    from consenrich_amd import _lib as L
+    from consenrich_amd.batch import DeviceBatch, ModelParams
+
+    sets, _ = inputs
+    for k in OWN:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("CONSENRICH_AMD_BLOCK", str(block))
+    monkeypatch.setenv("CONSENRICH_AMD_SB_BINS", "4096")
+    monkeypatch.setenv("CONSENRICH_AMD_WARM", "-1,-1,384")
+    m = 4
+    what = L.EXPORT_FORWARD | L.EXPORT_SMOOTH | L.EXPORT_RESID
+    mask = [c == 9 for c in range(len(N_LIST))]         # the chain of 8193 bins
+    with DeviceBatch(0) as b:
+        b.configure(ModelParams(state_dim=2), m, N_LIST)
+        for c, (d_, v_) in enumerate(sets[m]):
+            b.upload(c, d_, v_)
+        b.step(L.RETURN_NLL, what)
+        before = {(c, a): b.download(c, a) for c in range(len(N_LIST)) for a in ("D", "xf", "Pf", "xs", "Ps", "lag")}
+        b.forward_masked(L.RETURN_NLL, mask)
+        for c in (8, 10, 0):
+            for a in ("xf", "D"):
+                assert np.array_equal(_bits(before[(c, a)]), _bits(b.download(c, a))), (block, c, a)
+        b.backward()
+        b.export(L.EXPORT_FORWARD | L.EXPORT_SMOOTH)
+        for c in range(len(N_LIST)):
+            for a in ("xf", "Pf", "xs", "Ps", "lag"):
+                assert np.array_equal(_bits(before[(c, a)]), _bits(b.download(c, a))), (block, "after the smoother", c, a)
