@@ -43,14 +43,14 @@ __global__ __launch_bounds__(256) void k_obj_wave(Prm p, BgBatch a, ObjArgs o) {
         if (o.lamNat) {
             const double lam = (double)o.lamNat[g];
             if (o.useLambdaPenalty) {
-                const double v = lam > tiny ? lam : tiny;
+                const double v = lam < tiny ? tiny : lam;                        // np.maximum: NaN stays NaN
                 r[0] += v - log(v);
             }
             lamClip = lam < o.wMin ? o.wMin : (lam > o.wMax ? o.wMax : lam);
         }
         if (o.useKappaPenalty && o.kapNat && (k >= 1 || len == 1)) {
             const double kv = (double)o.kapNat[g];
-            const double v = kv > tiny ? kv : tiny;
+            const double v = kv < tiny ? tiny : kv;
             r[1] += v - log(v);
         }
         if (o.bg) {

@@ -170,3 +170,17 @@ def test_penalized_objective_known_answers():
     cfg["use_lambda"] = False
     o2 = odrv.penalized_objective(100.0, munc, bg, lam, None, cfg)
     assert o2["background_negative_penalty"] == 0.0 and o2["robust_observation_penalty"] == 0.0 and o2["robust_process_penalty"] == 0.0
+    # np.maximum(x, tiny) propagates NaN (core.py:3172, 3175): a NaN multiplier makes its penalty, and with it the objective, NaN
+    cfg["use_nonnegative"] = cfg["use_lambda"] = True
+    lam_nan, kap_nan = lam.copy(), kap.copy()
+    lam_nan[3] = kap_nan[5] = np.nan
+    with np.errstate(invalid="ignore"):
+        o3 = odrv.penalized_objective(100.0, munc, bg, lam_nan, kap, cfg)
+        o4 = odrv.penalized_objective(100.0, munc, bg, lam, kap_nan, cfg)
+    assert np.isnan(o3["robust_observation_penalty"]) and o3["robust_process_penalty"] == o["robust_process_penalty"]
+    assert np.isnan(o4["robust_process_penalty"]) and o4["robust_observation_penalty"] == o["robust_observation_penalty"]
+    assert np.isnan(o3["penalized_objective_per_cell"]) and np.isnan(o4["penalized_objective_per_cell"])
+    assert o4["background_negative_penalty"] == o["background_negative_penalty"]      # kappa does not enter the weights
+    kap_first = kap.copy()
+    kap_first[0] = np.nan                                   # the first kappa is skipped (n > 1): its NaN does not count
+    assert odrv.penalized_objective(100.0, munc, bg, lam, kap_first, cfg)["robust_process_penalty"] == o["robust_process_penalty"]
