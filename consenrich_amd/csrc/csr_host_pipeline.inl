@@ -473,20 +473,22 @@ static int need_blocked(csr_ctx *c, std::initializer_list<int> ids, const unsign
 // to the fixed point (= the sequential recursion, whatever the superblock length); one tiled launch brings the filtered state
 // back into the batch's blocked layout for the epilogue and the smoother.
 static int early_cov_exports(csr_ctx *c, const Prm &p, uint32_t flags, bool withPf);
-// phase 0: the whole chain.  phase 1 (a step that pipelines its tail per chain, step_pipelined): stop right after the launch of
-// the barrier-free kernel, with per-chain "done" words the host can watch -- c->sbp.active says that this happened (otherwise
-// the whole chain ran, as in phase 0).  phase 2: wait for that launch (or run the pass form if it bailed out); the filtered
-// state is NOT brought back into the blocked layout (the caller does that per group of chains).
-static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = false, uint32_t flags = 0, int phase = 0) {
-    const bool resume = phase == 2;
+// The three forms of the chain, each in the instance of a pass's `mode`
+static void (*const g_sbSys[3])(Prm, const float4 *, const float4 *, float2 *) = {&k_sb_sys<0>, &k_sb_sys<1>, &k_sb_sys<2>};
+static void (*const g_sbDelta[3])(Prm, const float4 *, const float4 *, float2 *, int, int) = {&k_sb_delta<0>, &k_sb_delta<1>, &k_sb_delta<2>};
+static void (*const g_sbAsync[3])(Prm, const float4 *, const float4 *, float2 *, SbAsync) = {&k_sb_async<0, false>, &k_sb_async<1, false>,
+                                                                                            &k_sb_async<2, false>};
+// The chain up to and including the launch of the barrier-free kernel (k_sb_async; CONSENRICH_AMD_SB_ASYNC=0: nothing is launched);
+// c->sbp holds what sb_finish needs.  watch (step_pipelined, a step that pipelines its tail per chain): the kernel sets a host-visible
+// "done" word per chain, the side stream continues from the point right in front of it, c->sbp.active says that the chain is in flight.
+static int sb_begin(csr_ctx *c, const Prm &p, bool earlyExports, uint32_t flags, bool watch) {
     CHECK(ensure_sb_view(c));
-    if (!resume) CHECK(flush_pending_check(c));
+    CHECK(flush_pending_check(c));
     csr_ctx::SbView &v = c->sb;
     CHECK(ensure_sb_nat(c));
     float *natXf;
     CHECK(nat_array(c, CSR_ARR_XF, &natXf));
-    c->sbp.active = false;
-    if (!resume && !(c->gainNat && c->natSZValid)) {
+    if (!(c->gainNat && c->natSZValid)) {
         ExpList L;
         memset(&L, 0, sizeof(L));
         // the gain records of this pass unless the covariance chain wrote them in the reference layout itself (forward_impl); the
@@ -501,65 +503,68 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
         }
         CHECK(launch(c, "state_records_natural", "k_export_tiled (state records)", k_export_tiled, tile_grid(c), dim3(256), 0, c->stream, pe, L));
     }
-    if (earlyExports && !resume) CHECK(early_cov_exports(c, p, flags, true));
-    Prm q = p;
+    if (earlyExports) CHECK(early_cov_exports(c, p, flags, true));
+    csr_ctx::SbPending &s = c->sbp;
+    s.active = s.launched = false;
+    s.watch = watch;
+    s.p = s.q = p;
+    Prm &q = s.q;
     q.B = v.B; q.NB = v.NB; q.NG = v.NG; q.blk = v.blk; q.blkChain = v.blkChain;
     q.carryIn = v.carryIn; q.carryOutA = v.carryOutA; q.carryOutB = v.carryOutB;
     unsigned int *const cnt = reinterpret_cast<unsigned int *>(c->dMail);
     q.rerunCount = cnt + ST_X;
     q.rerunCountPass = cnt + MAIL_DUMMY;
-    q.prevKind = CK_NONE;
-    const int mode = unit_f(p) ? (p.F01 == 1.0 ? 2 : 1) : 0;     // F01 == 1: the walker's predicted level is one float32 add
-    const int grid = (int)((v.NB + 3) / 4);
-    q.sbDbg = nullptr;
-    // the three forms of the chain, each in the instance of this pass's `mode`
-    using SysFn = void (*)(Prm, const float4 *, const float4 *, float2 *);
-    using DeltaFn = void (*)(Prm, const float4 *, const float4 *, float2 *, int, int);
-    using AsyncFn = void (*)(Prm, const float4 *, const float4 *, float2 *, SbAsync);
-    const SysFn sysFns[3] = {&k_sb_sys<0>, &k_sb_sys<1>, &k_sb_sys<2>};
-    const DeltaFn deltaFns[3] = {&k_sb_delta<0>, &k_sb_delta<1>, &k_sb_delta<2>};
-    const AsyncFn asyncFns[3] = {&k_sb_async<0, false>, &k_sb_async<1, false>, &k_sb_async<2, false>};
-    float2 *const xf = reinterpret_cast<float2 *>(natXf);
+    q.prevKind = CK_NONE; q.sbDbg = nullptr;
+    s.mode = unit_f(p) ? (p.F01 == 1.0 ? 2 : 1) : 0;     // F01 == 1: the walker's predicted level is one float32 add
+    s.grid = (int)((v.NB + 3) / 4);
+    s.xf = reinterpret_cast<float2 *>(natXf);
+    if (!c->sbAsync) return 0;
+    // the whole chain in one launch, no barrier between passes (k_sb_async); a bail-out (a bounded wait ran out) makes sb_finish run
+    // the pass form, which starts over from the cold prior
+    if (!v.pub) { CHECK(dalloc(c, &v.pub, 2 * v.NB + 2)); }
+    SbAsync a;
+    a.carry = v.pub; a.vf = v.pub + v.NB; a.ctl = reinterpret_cast<unsigned int *>(v.pub + 2 * v.NB);
+    a.spinLimit = c->sbSpinLimit;
+    a.hostDone = nullptr;
+    if (watch) {
+        // (nothing of this context is in flight that writes these words: the previous launch was waited for)
+        if (!c->hDone) {
+            // (coherent = fine-grained: a system-scope store of the running kernel is visible to the polling host at once,
+            // whatever HIP_HOST_COHERENT says)
+            CHECK(c->hDone.alloc(c->chains.size(), hipHostMallocCoherent | hipHostMallocMapped));
+            HIPOK(hipHostGetDevicePointer((void **)&c->dDone, c->hDone, 0));
+        }
+        for (size_t i = 0; i < c->chains.size(); ++i) c->hDone[i] = 0u;
+        a.hostDone = c->dDone;
+    }
+    HIPOK(hipMemsetAsync(v.pub, 0, sizeof(unsigned long long) * (size_t)(2 * v.NB + 2), c->stream));
+    // (the repair runs' LDS ring: > 64 KB of dynamic LDS has to be asked for once per kernel)
+    if (!c->sbAsyncLdsRaised[s.mode]) {
+        HIPOK(hipFuncSetAttribute(reinterpret_cast<const void *>(g_sbAsync[s.mode]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_ASYNC_LDS));
+        c->sbAsyncLdsRaised[s.mode] = true;
+    }
+    // (a pipelined step's NIS / NLL epilogue groups run on the side stream while this launch runs: the side stream continues
+    // from HERE, behind the statistics and the covariance chain the epilogue reads; a chain's done word is the rest)
+    if (watch) CHECK(fork_side(c, c->evEpiFork));
+    CHECK(launch(c, "fwd_state_chain", "k_sb_async", g_sbAsync[s.mode], dim3(s.grid), dim3(256), SB_ASYNC_LDS, c->stream, q, c->sbNatGain,
+                 c->sbNatSZ, s.xf, a));
+    s.ctl = a.ctl;
+    s.launched = true;
+    s.active = watch;
+    return 0;
+}
+
+// Everything behind sb_begin: the verdict of the single launch (or, when it bailed out or never went out, the pass form k_sb_sys),
+// the repair passes to the fixed point (= the sequential recursion, whatever the superblock length), and with `reblock` the blocked
+// copy of the filtered state for the whole batch (a pipelined step makes it per group of chains, where one is needed at all).
+static int sb_finish(csr_ctx *c, bool reblock) {
+    csr_ctx::SbPending &s = c->sbp;
+    const csr_ctx::SbView &v = c->sb;
+    s.active = false;
     bool done = false;
-    if (c->sbAsync) {
-        // the whole chain in one launch, no barrier between passes (k_sb_async); a bail-out (a bounded wait ran out) falls
-        // through to the pass form below, which starts over from the cold prior
-        if (!v.pub) { CHECK(dalloc(c, &v.pub, 2 * v.NB + 2)); }
-        SbAsync a;
-        a.carry = v.pub; a.vf = v.pub + v.NB; a.ctl = reinterpret_cast<unsigned int *>(v.pub + 2 * v.NB);
-        a.spinLimit = c->sbSpinLimit;
-        a.hostDone = nullptr;
-        if (phase == 1) {
-            // (nothing of this context is in flight that writes these words: the previous launch was waited for)
-            if (!c->hDone) {
-                // (coherent = fine-grained: a system-scope store of the running kernel is visible to the polling host at once,
-                // whatever HIP_HOST_COHERENT says)
-                CHECK(c->hDone.alloc(c->chains.size(), hipHostMallocCoherent | hipHostMallocMapped));
-                HIPOK(hipHostGetDevicePointer((void **)&c->dDone, c->hDone, 0));
-            }
-            for (size_t i = 0; i < c->chains.size(); ++i) c->hDone[i] = 0u;
-            a.hostDone = c->dDone;
-        }
-        if (!resume) {
-            HIPOK(hipMemsetAsync(v.pub, 0, sizeof(unsigned long long) * (size_t)(2 * v.NB + 2), c->stream));
-            // (the repair runs' LDS ring: > 64 KB of dynamic LDS has to be asked for once per kernel)
-            if (!c->sbAsyncLdsRaised[mode]) {
-                HIPOK(hipFuncSetAttribute(reinterpret_cast<const void *>(asyncFns[mode]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_ASYNC_LDS));
-                c->sbAsyncLdsRaised[mode] = true;
-            }
-            // (a pipelined step's NIS / NLL epilogue groups run on the side stream while this launch runs: the side stream continues
-            // from HERE, behind the statistics and the covariance chain the epilogue reads; a chain's done word is the rest)
-            if (phase == 1 && c->tailEpilogue) CHECK(fork_side(c, c->evEpiFork));
-            CHECK(launch(c, "fwd_state_chain", "k_sb_async", asyncFns[mode], dim3(grid), dim3(256), SB_ASYNC_LDS, c->stream, q, c->sbNatGain,
-                         c->sbNatSZ, xf, a));
-        }
-        if (phase == 1) {
-            c->sbp.active = true;
-            c->sbp.p = p;
-            return 0;
-        }
+    if (std::exchange(s.launched, false)) {
         unsigned int ctl[4];
-        HIPOK(hipMemcpyAsync(ctl, a.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipMemcpyAsync(ctl, s.ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
         HIPOK(wait_stream(c, 1));
         c->rs.fix_launches++;
         if (ctl[1] == 0) {
@@ -570,14 +575,14 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
         } else {
             c->rs.sb_bailouts++;
             if (c->dbgLog) fprintf(stderr, "[csr] fwd_state_chain (barrier-free superblocks): bailed out, running the pass form\n");
-            // (a pipelined step may have tails of finished chains in flight that read the track the pass form rewrites)
-            // (... and epilogue groups on the side stream that read it)
-            if (resume && c->tail) HIPOK(hipStreamSynchronize(c->tail));
-            if (resume && c->side) HIPOK(hipStreamSynchronize(c->side));
+            // (a pipelined step may have tails of finished chains in flight that read the track the pass form rewrites, and epilogue
+            // groups on the side stream that read it: this is the one place that waits for them)
+            if (s.watch) HIPOK(hipStreamSynchronize(c->tail));
+            if (s.watch) HIPOK(hipStreamSynchronize(c->side));
         }
     }
     if (!done)
-        CHECK(launch(c, "fwd_state_chain", "k_sb_sys", sysFns[mode], dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf));
+        CHECK(launch(c, "fwd_state_chain", "k_sb_sys", g_sbSys[s.mode], dim3(s.grid), dim3(256), 0, c->stream, s.q, c->sbNatGain, c->sbNatSZ, s.xf));
     int which = 0, burst = 2;
     const int adv = (c->sbAdvMin << 8) | (c->sbAdvFrom << 16);
     for (int64_t it = 0; it <= v.NB + 1 && !done; ++it) {
@@ -585,7 +590,7 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
             // repair passes in delta form (k_sb_delta): a burst of them under ONE profile scope
             Scope sc(c, "fwd_state_fix");
             for (int rep = 0; rep < burst; ++rep) {
-                CHECK(launch(c, nullptr, "k_sb_delta", deltaFns[mode], dim3(grid), dim3(256), 0, c->stream, q, c->sbNatGain, c->sbNatSZ, xf,
+                CHECK(launch(c, nullptr, "k_sb_delta", g_sbDelta[s.mode], dim3(s.grid), dim3(256), 0, c->stream, s.q, c->sbNatGain, c->sbNatSZ, s.xf,
                              which, adv));
                 which ^= 1;
                 c->rs.fix_launches++;
@@ -599,9 +604,13 @@ static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports = fa
         burst = c->dbgLog ? 1 : std::min(32, burst * 2);
     }
     if (!done) return fail("fwd_state_chain (systolic superblocks): fix-up did not reach a fixed point");
-    if (!resume) CHECK(import_xf_blocked(c, p, c->stream, 0, c->NG));
+    if (reblock) CHECK(import_xf_blocked(c, s.p, c->stream, 0, c->NG));
     produced(c, {CSR_ARR_XF}, W_BLOCKED | W_NAT);
     return 0;
+}
+static int state_chain_systolic(csr_ctx *c, const Prm &p, bool earlyExports, uint32_t flags) {
+    CHECK(sb_begin(c, p, earlyExports, flags, false));
+    return sb_finish(c, true);
 }
 
 // Join the side stream.  The per-chain sums (22 workgroups of 1024 threads, ~10 us) run on the main stream after the
@@ -847,7 +856,8 @@ static int forward_impl(csr_ctx *c, const FwdPass &pass) {
             } else {
                 // (the early covariance exports fork off behind the state chain's own record conversion)
                 const bool early = natOut && active == nullptr;
-                CHECK(state_chain_systolic(c, p, early, flags, split ? 1 : 0));
+                if (split && c->sbAsync) CHECK(sb_begin(c, p, early, flags, true));
+                else CHECK(state_chain_systolic(c, p, early, flags));
                 dX = false;
             }
         } else {
@@ -1428,61 +1438,54 @@ static int export_impl(csr_ctx *c, uint32_t what) {
 // Same launches as csr_batch_stats / csr_batch_forward_backward / csr_batch_export / csr_batch_sums in sequence -- a
 // convenience for callers; the four separate calls cost the same (0.411 vs 0.412 ms on a 1/8-genome shard: the host runs
 // ahead of the device, only the final read-back is a round trip).
-// Everything of a step behind the filtered state -- blocked copy of xf, NIS / NLL epilogue, smoother, residuals -- for the
-// chains of `dmask` (device bytes, nullptr = all), on c->stream.  `runs`: the maximal runs of those chains as bin ranges of the
-// natural layout.
-struct ChainRun { int64_t off, len, b0, b1; };     // bins [off, off + len) of the natural layout = blocks [b0, b1) of the batch
 // one constant process noise: the smoother of a tail group reads xf / Pf of its chains in the reference layout (k_smooth_natin)
 static bool tail_reads_nat(csr_ctx *c, const Prm &pf) {
     return c->natInEnabled && c->where[CSR_ARR_PF].nat && const_q(c) && pf.chainQ == nullptr && (c->B % 8) == 0 &&
            (stage_warm(c, ST_B) % 8) == 0 && unit_f(pf);
 }
-// epi: the NIS / NLL epilogue runs in groups of its own (step_pipelined) -- the tail is the smoother (behind a blocked copy of xf
-// only where it reads blocks) and ONE residual launch over the group's runs (table `hRuns` / `dRuns`, launch_resid_runs)
-static int step_tail(csr_ctx *c, const Prm &pf, const unsigned char *dmask, const std::vector<ChainRun> &runs, uint32_t what, bool epi = false,
-                     ResidRun *hRuns = nullptr, ResidRun *dRuns = nullptr) {
+// The tail of the chains of `dmask` (device bytes; `runs`: their maximal runs), on c->stream: the smoother (behind a blocked copy of
+// xf only where it reads blocks) and ONE residual launch over the runs (table `hRuns` / `dRuns`, launch_resid_runs).  The NIS / NLL
+// epilogue runs in groups of its own (step_pipelined).
+static int step_tail(csr_ctx *c, const Prm &pf, const unsigned char *dmask, const std::vector<ChainRun> &runs, uint32_t what,
+                     ResidRun *hRuns, ResidRun *dRuns) {
     Prm pt = pf;
     pt.chainActive = dmask;
     pt.prevKind = CK_NONE;
-    // one constant process noise: the smoother reads xf / Pf of these chains in the reference layout (k_smooth_natin) and starts
-    // at once; the blocked copy of xf only the NIS / NLL epilogue needs is made on the side stream in front of it
     const bool natTail = tail_reads_nat(c, pf);
-    if (epi) {
-        if (!natTail && !runs.empty()) {
-            int64_t g0 = runs.front().b0 / 64, g1 = (runs.front().b1 + 63) / 64;
-            for (const ChainRun &r : runs) { g0 = std::min(g0, r.b0 / 64); g1 = std::max(g1, (r.b1 + 63) / 64); }
-            CHECK(import_xf_blocked(c, pt, c->stream, g0, g1 - g0));
-        }
-        CHECK(backward_impl(c, {.active = dmask, .defer = true, .natOut = true, .preferNatIn = natTail}));
-        CHECK(flush_pending_check(c));
-        if (what & CSR_EXPORT_RESID) {
-            int n = 0;
-            for (const ChainRun &r : runs) hRuns[n++] = ResidRun{r.off, r.len, 0};
-            CHECK(launch_resid_runs(c, hRuns, dRuns, n));
-        }
-        return 0;
+    if (!natTail && !runs.empty()) {
+        const auto [g0, groups] = group_span(runs);
+        CHECK(import_xf_blocked(c, pt, c->stream, g0, groups));
     }
-    CHECK(fork_side(c, c->evFork));
-    hipStream_t imp = natTail ? c->side : c->stream;
-    // (the smoother is what the group's residuals wait for: when it reads the reference layout it is launched FIRST, the
-    // epilogue's kernels of the side stream after it -- they were forked above and do not wait for it)
-    if (natTail) CHECK(backward_impl(c, {.active = dmask, .defer = true, .natOut = true, .preferNatIn = true}));
-    if (!runs.empty()) {
-        // ONE launch over the wavefront-groups from the first to the last block of these chains: the mask trims what lies between
-        // (round 4: a launch per run of chains serialised four 60-us launches behind the state chain for a scattered last group)
-        int64_t g0 = runs.front().b0 / 64, g1 = (runs.front().b1 + 63) / 64;
-        for (const ChainRun &r : runs) { g0 = std::min(g0, r.b0 / 64); g1 = std::max(g1, (r.b1 + 63) / 64); }
-        CHECK(import_xf_blocked(c, pt, imp, g0, g1 - g0));
+    CHECK(backward_impl(c, {.active = dmask, .defer = true, .natOut = true, .preferNatIn = natTail}));
+    CHECK(flush_pending_check(c));
+    if (what & CSR_EXPORT_RESID) {
+        int n = 0;
+        for (const ChainRun &r : runs) hRuns[n++] = ResidRun{r.off, r.len, 0};
+        CHECK(launch_resid_runs(c, hRuns, dRuns, n));
     }
-    // the NIS / NLL epilogue beside the (latency-bound) smoother chain, on the side stream
-    if (!natTail) CHECK(fork_side(c, c->evFork));
-    CHECK(launch_dstat(c, pt, c->side));
-    HIPOK(hipEventRecord(c->evJoin, c->side));
-    if (!natTail) CHECK(backward_impl(c, {.active = dmask, .defer = true, .natOut = true}));
-    CHECK(flush_pending_check(c));              // (the residual launches below cover a part of the batch each: no folded check)
-    if (what & CSR_EXPORT_RESID)
-        for (const ChainRun &r : runs) CHECK(launch_resid(c, r.off, r.len, false));
-    HIPOK(hipStreamWaitEvent(c->stream, c->evJoin, 0));
+    return 0;
+}
+
+// c->stream is `st` while one of these lives: what a tail group launches goes to the tail stream through the same functions that
+// otherwise launch on the main stream (nat_array counts first uses in between, csr_run_stats.nat_first_use_off_main)
+struct StreamScope {
+    csr_ctx *c; hipStream_t old;
+    StreamScope(csr_ctx *c_, hipStream_t st) : c(c_), old(c_->stream) { c->stream = st; }
+    ~StreamScope() { c->stream = old; }
+};
+
+// Does this step pipeline its tail per chain?  Bit-exact levelTrend mode, barrier-free state chain, deferred validation, 2 to 4096 chains.
+// (round 4: per-bin multipliers and per-chain base matrices pipeline as well -- their process noise goes to the reference
+// layout underneath the state chain with Pf, early_cov_exports; the sequential APN pass has no state chain to hide behind)
+static bool step_pipelines(const csr_ctx *c, uint32_t flags, uint32_t what) {
+    return c->tailSplit && c->xTolUlps == 0 && c->mdl.state_dim == 2 && !c->seqState && c->sbAsync && c->deferEnabled &&
+           !((flags & F_APN) && !(flags & F_QSCALE)) && !(what & CSR_EXPORT_MULT) && c->chains.size() >= 2 && c->chains.size() <= 4096;
+}
+// the forward pass is complete: the rest of the step in order
+static int step_rest_in_order(csr_ctx *c, uint32_t what, bool *handled) {
+    CHECK(backward_impl(c, {.defer = true, .natOut = true}));
+    if (what) CHECK(csr_batch_export(c, what));
+    *handled = true;
     return 0;
 }
 
@@ -1491,171 +1494,93 @@ static int step_tail(csr_ctx *c, const Prm &pf, const unsigned char *dmask, cons
 // memory system idle.  The kernel sets a host-visible word per chain when the chain is final; the host watches those words and,
 // whenever the newly finished chains make up tailFirstPct / tailNextPct per cent of the batch, launches their tail (smoother,
 // residuals; every kernel under a chain mask) on a second stream; the remainder follows when the state chain has ended.  The
-// NIS / NLL epilogue goes out in groups of its own on the side stream (epiPct per cent of the batch each): it needs the final xf
-// alone.  Same arithmetic, same results; a chain's tail simply starts when ITS filtered state stands.
-// (CONSENRICH_AMD_TAIL_EPILOGUE=0: the tails carry the epilogue, behind a blocked copy of xf, as they did before.)
+// NIS / NLL epilogue goes out in groups of its own on the side stream (epiPct per cent of the batch each; k_fwd_dstat<natXf> reads
+// the previous filtered state where the state chain wrote it): it needs a chain's final xf and nothing of the smoother, and
+// memory is idle under the state chain.  Same arithmetic, same results; a chain's tail simply starts when ITS filtered state stands.
 static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handled) {
     *handled = false;
-    // (round 4: per-bin multipliers and per-chain base matrices pipeline as well -- their process noise goes to the reference
-    // layout underneath the state chain with Pf, early_cov_exports; the sequential APN pass has no state chain to hide behind)
-    if (!(c->tailSplit && c->xTolUlps == 0 && c->mdl.state_dim == 2 && !c->seqState && c->sbAsync &&
-          c->deferEnabled && !((flags & F_APN) && !(flags & F_QSCALE)) &&
-          !(what & CSR_EXPORT_MULT) && c->chains.size() >= 2 && c->chains.size() <= 4096))
-        return 0;
+    if (!step_pipelines(c, flags, what)) return 0;
     CHECK(settle(c));
     CHECK(forward_impl(c, {.flags = flags, .wantD = true, .defer = true, .natOut = true, .split = true}));
-    if (!c->sbp.active) {               // the state chain did not go out as one launch: the pass is complete, carry on as usual
-        CHECK(backward_impl(c, {.defer = true, .natOut = true}));
-        if (what) CHECK(csr_batch_export(c, what));
-        *handled = true;
-        return 0;
-    }
+    // the state chain did not go out as one launch: the pass is complete, carry on as usual
+    if (!c->sbp.active) return step_rest_in_order(c, what, handled);
     const Prm pf = c->sbp.p;
     if (!(c->where[CSR_ARR_D].nat && c->where[CSR_ARR_PF].nat && c->where[CSR_ARR_PNOISE].nat)) {
         // an output of this pass still needs a conversion launch of its own (export_impl): no pipelining, finish in order
-        CHECK(state_chain_systolic(c, pf, false, flags, 2));
+        CHECK(sb_finish(c, false));
         CHECK(import_xf_blocked(c, pf, c->stream, 0, c->NG, false));
         CHECK(forward_epilogue(c, pf, true));
-        CHECK(backward_impl(c, {.defer = true, .natOut = true}));
-        if (what) CHECK(csr_batch_export(c, what));
-        *handled = true;
-        return 0;
+        return step_rest_in_order(c, what, handled);
     }
     const int nc = (int)c->chains.size();
-    int64_t total = 0;
-    for (const ChainInfo &ci : c->chains) total += ci.n;
-    if (!c->dMask[0]) for (auto &m : c->dMask) CHECK(dalloc(c, &m, nc));
-    if (!c->hMaskPin) CHECK(c->hMaskPin.alloc(8 * (size_t)nc, hipHostMallocDefault));
-    std::vector<unsigned char> tailed((size_t)nc, 0);
-    // NIS / NLL epilogue in groups of its own on the side stream (k_fwd_dstat<natXf> reads the previous filtered state where the state
-    // chain wrote it): it needs a chain's final xf and nothing of the smoother, and memory is idle under the state chain -- a group
-    // goes out whenever the final chains without an epilogue make up epiPct % of the batch, the remainder when the launch has ended
-    const bool epi = c->tailEpilogue && (c->B % 32) == 0;
+    CHECK(c->tailMasks.ensure(c, nc));
     const bool natTail = tail_reads_nat(c, pf);
-    std::vector<unsigned char> epid((size_t)nc, 0);
-    int epiGroups = 0;
     float *natXf = nullptr;
-    if (epi) {
-        CHECK(nat_array(c, CSR_ARR_XF, &natXf));
-        if (!c->dEpiMask[0]) for (auto &m : c->dEpiMask) CHECK(dalloc(c, &m, nc));
-        if (!c->hEpiMaskPin) CHECK(c->hEpiMaskPin.alloc(9 * (size_t)nc, hipHostMallocDefault));
-        if (!c->dRuns[0]) for (auto &r : c->dRuns) CHECK(dalloc(c, &r, nc));
-        if (!c->hRunsPin) CHECK(c->hRunsPin.alloc(8 * (size_t)nc, hipHostMallocDefault));
-    }
-    auto launch_epilogue = [&](const std::vector<unsigned char> &grp) -> int {
-        unsigned char *dm = c->dEpiMask[epiGroups];
-        unsigned char *hm = c->hEpiMaskPin + (size_t)epiGroups * (size_t)nc;
-        std::copy(grp.begin(), grp.end(), hm);
-        HIPOK(hipMemcpyAsync(dm, hm, (size_t)nc, hipMemcpyHostToDevice, c->side));
+    CHECK(nat_array(c, CSR_ARR_XF, &natXf));
+    CHECK(c->epiMasks.ensure(c, nc));
+    CHECK(c->tailRuns.ensure(c, nc));
+    // (groups are disjoint sets of chains, hence of blocks: their kernels share no data; every group leaves no folded check behind.
+    // Each group uploads from the pinned slot it owns: no slot is written twice in a step)
+    ChainSet tails(c->chains, MAX_EARLY_TAILS), epis(c->chains, MAX_EARLY_EPILOGUES);
+    std::vector<unsigned char> grp((size_t)nc, 0), egrp((size_t)nc, 0);
+    // a group's epilogue (the chains of `egrp`, side stream) and a group's tail (the chains of `grp`, c->stream)
+    auto launch_epilogue = [&]() -> int {
+        const int slot = epis.handed() - 1;
+        CHECK(c->epiMasks.upload(slot, egrp.data(), c->side));
         Prm pe = pf;
-        pe.chainActive = dm;
+        pe.chainActive = c->epiMasks.dev(slot);
         pe.prevKind = CK_NONE;
-        CHECK(launch_dstat(c, pe, c->side, natXf));
-        ++epiGroups;
-        return 0;
+        return launch_dstat(c, pe, c->side, natXf);
     };
-    int phase = 0;
-    bool any = false;
-    hipStream_t mainStream = c->stream;
-    auto launch_group = [&](const std::vector<unsigned char> &grp) -> int {
-        // runs of consecutive chains -> bin ranges (a chain occupies [off, off + its length rounded up to 64))
-        std::vector<ChainRun> runs;
-        for (int i = 0; i < nc; ++i) {
-            if (!grp[(size_t)i]) continue;
-            const ChainInfo &ci = c->chains[(size_t)i];
-            const int64_t l = (ci.n + 63) / 64 * 64;
-            if (!runs.empty() && runs.back().off + runs.back().len == ci.off && runs.back().b1 == ci.b0) {
-                runs.back().len += l;
-                runs.back().b1 = ci.b0 + ci.nb;
-            } else runs.push_back(ChainRun{ci.off, l, ci.b0, ci.b0 + ci.nb});
-        }
-        unsigned char *dm = c->dMask[phase];
-        unsigned char *hm = c->hMaskPin + (size_t)phase * (size_t)nc;
-        std::copy(grp.begin(), grp.end(), hm);
-        HIPOK(hipMemcpyAsync(dm, hm, (size_t)nc, hipMemcpyHostToDevice, c->stream));
-        if (epi) CHECK(step_tail(c, pf, dm, runs, what, true, c->hRunsPin + (size_t)phase * (size_t)nc, c->dRuns[phase]));
-        else CHECK(step_tail(c, pf, dm, runs, what));
-        ++phase;
-        any = true;
-        return 0;
+    auto launch_tail = [&]() -> int {
+        const int slot = tails.handed() - 1;
+        CHECK(c->tailMasks.upload(slot, grp.data(), c->stream));
+        return step_tail(c, pf, c->tailMasks.dev(slot), chain_runs(c->chains, grp), what, c->tailRuns.host(slot), c->tailRuns.dev(slot));
     };
-    // ---- while the state chain runs: tails of the chains that are final, an eighth of the batch at a time, on the tail stream
-    c->stream = c->tail;
-    int rc = 0;
+    // ---- while the state chain runs: the chains that are final, a group at a time (tails: tail stream; epilogues: side stream)
     // (the end of the launch is on the step's critical path -- the last tail starts behind it: the loop's sleeps run with a lowered
     // timer slack and, around the moment the PREVIOUS launch of this context ended, it polls without sleeping)
     TimerSlack slack;
+    std::vector<unsigned> done((size_t)nc, 0u);
     const auto tLoop = std::chrono::steady_clock::now();
     const double expectEnd = c->lastSbLoopUs;
     for (;;) {
-        const hipError_t qs = hipStreamQuery(mainStream);
+        const hipError_t qs = hipStreamQuery(c->stream);
         const double el = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tLoop).count();
-        if (qs != hipErrorNotReady) { if (qs != hipSuccess) rc = fail("state chain: %s", hipGetErrorString(qs)); else c->lastSbLoopUs = el; break; }
+        if (qs == hipSuccess) { c->lastSbLoopUs = el; break; }
+        if (qs != hipErrorNotReady) return fail("state chain: %s", hipGetErrorString(qs));
         // (bounded sleep-poll: the launch lasts milliseconds and a tail group is worth launching 20-50 us late; round 3 spun here)
         const bool nearEnd = expectEnd > 0.0 && el > expectEnd - 100.0 && el < expectEnd + 200.0;
         if (!nearEnd) std::this_thread::sleep_for(std::chrono::microseconds(20));
+        for (int i = 0; i < nc; ++i) done[(size_t)i] = __atomic_load_n(&c->hDone[i], __ATOMIC_ACQUIRE);
         // (an epilogue group is an upload and a launch: never inside the interval in which the end of the state chain is expected)
-        if (epi && c->epiPct > 0 && epiGroups < 8 && !nearEnd) {
-            std::vector<unsigned char> eg((size_t)nc, 0);
-            int64_t ebins = 0;
-            for (int i = 0; i < nc; ++i)
-                if (!epid[(size_t)i] && __atomic_load_n(&c->hDone[i], __ATOMIC_ACQUIRE) != 0u) { eg[(size_t)i] = 1; ebins += c->chains[(size_t)i].n; }
-            if (ebins > 0 && ebins * 100 >= total * c->epiPct) {
-                rc = launch_epilogue(eg);
-                if (rc) break;
-                for (int i = 0; i < nc; ++i) if (eg[(size_t)i]) epid[(size_t)i] = 1;
-            }
-        }
-        if (phase >= 6) continue;
-        std::vector<unsigned char> grp((size_t)nc, 0);
-        int64_t bins = 0;
-        for (int i = 0; i < nc; ++i)
-            if (!tailed[(size_t)i] && __atomic_load_n(&c->hDone[i], __ATOMIC_ACQUIRE) != 0u) { grp[(size_t)i] = 1; bins += c->chains[(size_t)i].n; }
-        if (bins * 100 >= total * (phase == 0 ? c->tailFirstPct : c->tailNextPct)) {
-            rc = launch_group(grp);
-            if (rc) break;
-            for (int i = 0; i < nc; ++i) if (grp[(size_t)i]) tailed[(size_t)i] = 1;
+        if (c->epiPct > 0 && !nearEnd && epis.pick(done.data(), c->epiPct, egrp)) CHECK(launch_epilogue());
+        if (tails.pick(done.data(), tails.handed() == 0 ? c->tailFirstPct : c->tailNextPct, grp)) {
+            StreamScope onTail(c, c->tail);
+            CHECK(launch_tail());
         }
     }
-    c->stream = mainStream;
-    if (rc) return rc;
     // ---- the launch has ended: its verdict (a bail-out runs the pass form and invalidates nothing that was final, but the
-    // pass form rewrites the whole track from the cold prior: the tails already launched are waited for and everything is redone)
+    // pass form rewrites the whole track from the cold prior: sb_finish waits for the groups already launched and everything is redone)
     const int64_t bail0 = c->rs.sb_bailouts;
-    CHECK(state_chain_systolic(c, pf, false, flags, 2));
-    if (c->rs.sb_bailouts != bail0 && (any || epiGroups > 0)) {
-        HIPOK(hipStreamSynchronize(c->tail));
-        HIPOK(hipStreamSynchronize(c->side));
-        std::fill(tailed.begin(), tailed.end(), (unsigned char)0);
-        std::fill(epid.begin(), epid.end(), (unsigned char)0);
-    }
+    CHECK(sb_finish(c, false));
+    if (c->rs.sb_bailouts != bail0 && tails.handed() + epis.handed() > 0) { tails.clear(); epis.clear(); }
     // ---- the remaining chains: on the main stream, behind the state chain and beside whatever the tail stream still has to do
-    // (groups are disjoint sets of chains, hence of blocks: their kernels share no data; every group leaves no folded check behind)
-    std::vector<unsigned char> rest((size_t)nc, 0);
-    bool anyRest = false;
-    for (int i = 0; i < nc; ++i) if (!tailed[(size_t)i]) { rest[(size_t)i] = 1; anyRest = true; }
-    if (anyRest) CHECK(launch_group(rest));
+    if (tails.rest(grp)) CHECK(launch_tail());
     // ---- the epilogue of the chains that have none yet, on the side stream (the state chain has ended: nothing to wait for)
-    if (epi) {
-        std::vector<unsigned char> er((size_t)nc, 0);
-        bool anyEr = false;
-        for (int i = 0; i < nc; ++i) if (!epid[(size_t)i]) { er[(size_t)i] = 1; anyEr = true; }
-        if (anyEr) CHECK(launch_epilogue(er));
-        HIPOK(hipEventRecord(c->evEpiJoin, c->side));
-    }
+    if (epis.rest(egrp)) CHECK(launch_epilogue());
+    HIPOK(hipEventRecord(c->evEpiJoin, c->side));
     HIPOK(hipEventRecord(c->evTailJoin, c->tail));
-    HIPOK(hipStreamWaitEvent(mainStream, c->evTailJoin, 0));
-    if (epi) {
-        HIPOK(hipStreamWaitEvent(mainStream, c->evEpiJoin, 0));
-        // (no blocked copy of xf was made where the smoother read the reference layout: later readers of blocks bring it back)
-        if (natTail) produced(c, {CSR_ARR_XF}, W_NAT);
-    }
+    HIPOK(hipStreamWaitEvent(c->stream, c->evTailJoin, 0));
+    HIPOK(hipStreamWaitEvent(c->stream, c->evEpiJoin, 0));
+    // (no blocked copy of xf was made where the smoother read the reference layout: later readers of blocks bring it back)
+    if (natTail) produced(c, {CSR_ARR_XF}, W_NAT);
     Prm ps = pf;
     ps.chainActive = nullptr;
     CHECK(launch_chain_sums(c, ps, c->stream));
     replay_covers_every_chain(c);
     if (c->last.bwdPending) reexport_on_replay(c, what);
-    c->rs.tail_groups += phase;
+    c->rs.tail_groups += tails.handed();
     *handled = true;
     return 0;
 }

@@ -13,6 +13,7 @@
 #include "csr_rocco.h"
 #include "csr_dwb.h"
 #include "csr_segments.h"
+#include "csr_step_groups.h"
 
 #include <algorithm>
 #include <array>
@@ -83,13 +84,6 @@ extern "C" int csr_device_count(void) {
 constexpr size_t MAIL_HDR = 80;     // 20 x u32 counters
 constexpr int MAIL_PASS0 = 4, MAIL_DUMMY = 16, MAIL_LOCAL = 17, MAX_DEFER_PASSES = 4;    // MAIL_LOCAL: blocks repaired inside speculative kernels
 
-struct ChainInfo {
-    int64_t n;      // bins
-    int64_t off;    // natural offset (multiple of 64)
-    int64_t b0;     // first block
-    int64_t nb;     // number of blocks
-};
-
 struct ProfEntry {
     int64_t launches = 0;
     double total_ms = 0.0;
@@ -149,6 +143,24 @@ struct PinBuf {
         return 0;
     }
     operator T *() const { return ptr; }
+};
+// N device arrays of one element per chain (dalloc: they die with the batch) and the pinned staging of their uploads, one slot each
+// (an upload from pageable memory may hold the host): the masks and run tables of the groups of a pipelined step
+struct csr_ctx;
+template <class T, int N>
+struct GroupSlots {
+    T *d[N] = {};
+    PinBuf<T> pin;
+    size_t stride = 0;
+    int ensure(csr_ctx *c, int nc);
+    T *host(int i) const { return pin.ptr + (size_t)i * stride; }
+    T *dev(int i) const { return d[i]; }
+    // slot i := the stride elements at src, on stream st
+    int upload(int i, const T *src, hipStream_t st) {
+        std::copy(src, src + stride, host(i));
+        HIPOK(hipMemcpyAsync(d[i], host(i), sizeof(T) * stride, hipMemcpyHostToDevice, st));
+        return 0;
+    }
 };
 
 // One forward pass / one smoother pass as its caller describes it (forward_impl, backward_impl).  Everything a pass depends on
@@ -277,17 +289,23 @@ struct BatchState {
     } pendChk;
     void *carrySet[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [set][carryIn, carryOutA]
     int carryToggle = 0;
-    struct SbPending { bool active = false; Prm p{}; } sbp;     // a state chain launched and not yet waited for (step_pipelined)
+    // The state chain between sb_begin and sb_finish: `p` as the caller passed it, `q` / mode / grid / xf as the chain's kernels take
+    // them.  launched: k_sb_async went out (ctl = its verdict words); watch: with per-chain done words for step_pipelined, which
+    // finishes it -- `active` until then
+    struct SbPending {
+        bool active = false, launched = false, watch = false;
+        Prm p{}, q{};
+        int mode = 0, grid = 0;
+        float2 *xf = nullptr;
+        unsigned int *ctl = nullptr;
+    } sbp;
     PinBuf<unsigned int> hDone;         // host-visible "chain is final" words (coherent, mapped) ...
     unsigned int *dDone = nullptr;      // ... and their device alias
-    unsigned char *dMask[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    PinBuf<unsigned char> hMaskPin;     // pinned staging of the eight masks (an upload from pageable memory may hold the host)
-    // step_pipelined, NIS / NLL epilogue groups of their own (side stream): up to eight early masks and the remainder's, with their
-    // pinned staging; and the run tables of the tail groups' residual launches (k_resid_runs), one per tail mask
-    unsigned char *dEpiMask[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    PinBuf<unsigned char> hEpiMaskPin;
-    ResidRun *dRuns[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    PinBuf<ResidRun> hRunsPin;
+    // step_pipelined: the chain mask of every tail group and of every NIS / NLL epilogue group (the early ones and the remainder's),
+    // and the run table of every tail group's residual launch (k_resid_runs)
+    GroupSlots<unsigned char, MAX_EARLY_TAILS + 1> tailMasks;
+    GroupSlots<unsigned char, MAX_EARLY_EPILOGUES + 1> epiMasks;
+    GroupSlots<ResidRun, MAX_EARLY_TAILS + 1> tailRuns;
     bool pfPending = false;
     // the reference-layout process-noise array holds the constant fill of THESE values in every row (k_fill_rows): a step with the
     // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)
@@ -387,10 +405,8 @@ struct csr_ctx : BatchState {
     // 50 / 15) -- tail kernels take issue slots from the walking wavefronts, so fewer, later groups win (profiles/r04_tail_sweep.txt)
     int tailFirstPct = 60, tailNextPct = 40;
     bool tailSplit = true;      // CONSENRICH_AMD_TAIL_SPLIT=0: a step's tail follows the state chain for all chains at once
-    // CONSENRICH_AMD_TAIL_EPILOGUE=0: the epilogue runs inside the tail groups again, behind a blocked copy of xf, and a group's
-    // residuals are one launch per run of chains (the A/B yardstick of the epilogue groups).  CONSENRICH_AMD_EPILOGUE_PCT: share of
-    // the batch's bins that final chains without an epilogue must reach for an early epilogue group (0: no early groups)
-    bool tailEpilogue = true;
+    // CONSENRICH_AMD_EPILOGUE_PCT: share of the batch's bins that final chains without an epilogue must reach for an early epilogue
+    // group (0: no early groups)
     int epiPct = 10;
     // ROCCO (csr_host_rocco.inl): tuning, counters and growable work space; the batch's tracks are BatchState::rocco
     struct RoccoWs {
@@ -479,6 +495,13 @@ static int dalloc(csr_ctx *c, T **ptr, int64_t count) {
     *ptr = reinterpret_cast<T *>(q);
     return 0;
 }
+template <class T, int N>
+int GroupSlots<T, N>::ensure(csr_ctx *c, int nc) {
+    if (pin) return 0;
+    for (T *&x : d) CHECK(dalloc(c, &x, nc));
+    stride = (size_t)nc;
+    return pin.alloc((size_t)N * stride, hipHostMallocDefault);
+}
 
 // Ends the configured batch: its device memory is freed and every BatchState member is back at its default (DevBuf / PinBuf members
 // free what they own when they are assigned to).  The device must be selected.
@@ -560,7 +583,6 @@ extern "C" csr_ctx *csr_create(int device_ordinal) {
         int a = 60, b = 40;
         if (sscanf(e, "%d,%d", &a, &b) >= 1) { c->tailFirstPct = std::min(100, std::max(1, a)); c->tailNextPct = std::min(100, std::max(1, b)); }
     }
-    if ((e = getenv("CONSENRICH_AMD_TAIL_EPILOGUE"))) c->tailEpilogue = atoi(e) != 0;
     if ((e = getenv("CONSENRICH_AMD_EPILOGUE_PCT"))) c->epiPct = std::min(100, std::max(0, atoi(e)));
     if ((e = getenv("CONSENRICH_AMD_SB_SPIN_LIMIT"))) c->sbSpinLimit = std::max(1, atoi(e));
     c->dbgLog = getenv("CONSENRICH_AMD_DEBUG") != nullptr;

@@ -217,6 +217,23 @@ def test_header_is_plain_c_and_library_links_from_c(tmp_path):
                      C.sizeof(L.RunStats)]
 
 
+def test_step_groups_header_hands_out_chains_as_the_pipelined_step_expects(tmp_path):
+    """consenrich_amd/csrc/csr_step_groups.h is plain C++17: tests/step_groups_check.cpp (runs of chains, their span of
+    wavefront-groups, the thresholds / cap / remainder / bail-out of ChainSet) built stand-alone under the address and
+    undefined-behaviour sanitizers."""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "step_groups_check"
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "consenrich_amd", "csrc"), os.path.join(ROOT, "tests", "step_groups_check.cpp"),
+                           "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "step_groups_check ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+
+
 def test_qseed_posterior_fails_loudly_without_a_gpu():
     """The grid posterior of the Q0 seed (pyx:1905-2146) runs on the device since round 2 (csr_qseed_post.h; its golden
     vectors are checked under -m gpu, tests/test_gpu_qseed.py): without a GPU the call must raise, not compute on the host."""

@@ -2,7 +2,7 @@
 the state chain is still running (step_pipelined, csr_host_pipeline.inl): `k_fwd_dstat<natXf>` reads the previous filtered state
 where the state chain wrote it (no blocked copy of xf), and a tail group's residuals are ONE launch over a table of runs
 (`k_resid_runs`, `k_resid_v4_runs`).  Same arithmetic in the same order: every output equals, bit for bit, the step in order
-(CONSENRICH_AMD_TAIL_SPLIT=0) and the step whose tails carry the epilogue (CONSENRICH_AMD_TAIL_EPILOGUE=0).
+(CONSENRICH_AMD_TAIL_SPLIT=0).
 
 Small shapes on purpose: chains shorter than, equal to and just past one block of every block length, a chain of one bin, chains of
 several superblocks (CONSENRICH_AMD_SB_BINS=4096); m = 4 takes the 16-byte residual kernel, m = 5 the plain one.
@@ -25,8 +25,7 @@ pytestmark = pytest.mark.gpu
 
 N_LIST = [1, 63, 64, 65, 127, 128, 129, 257, 4097, 8193, 20000]
 NAMES = ("D", "xf", "Pf", "pnoise", "xs", "Ps", "lag", "resid")
-OWN = ("CONSENRICH_AMD_TAIL_SPLIT", "CONSENRICH_AMD_TAIL_EPILOGUE", "CONSENRICH_AMD_TAIL_PCT", "CONSENRICH_AMD_SB_SPIN_LIMIT",
-       "CONSENRICH_AMD_EPILOGUE_PCT")
+OWN = ("CONSENRICH_AMD_TAIL_SPLIT", "CONSENRICH_AMD_TAIL_PCT", "CONSENRICH_AMD_SB_SPIN_LIMIT", "CONSENRICH_AMD_EPILOGUE_PCT")
 
 
 @pytest.fixture(scope="module")
@@ -121,16 +120,13 @@ def _assert_same(got, ref, msg):
 @pytest.mark.parametrize("m", [4, 5])
 def test_epilogue_groups_and_table_residuals_equal_the_step_in_order_and_the_old_tails(product, monkeypatch, inputs, m, block, variant):
     """D, xf, Pf, pNoise, xs, Ps, lag, resid, sumD and sumNLL of the first and of the second step of a fresh batch, bit for bit:
-    the default step (tail thresholds unset, and at 1 % so that nearly every finished chain is a group) against (i) the step in
-    order and (ii) the step whose tails carry the epilogue; no replay and no bail-out in any of them.  Then with a wait bound of
-    one poll (CONSENRICH_AMD_SB_SPIN_LIMIT=1): the single launch gives up under the groups in flight, everything is redone behind
-    the pass form, and the outputs equal (i)."""
+    the default step (tail thresholds unset, and at 1 % so that nearly every finished chain is a group) against the step in
+    order; no replay and no bail-out in any of them.  Then with a wait bound of one poll (CONSENRICH_AMD_SB_SPIN_LIMIT=1): the
+    single launch gives up under the groups in flight, everything is redone behind the pass form, and the outputs equal the step
+    in order."""
     in_order = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_SPLIT": "0"}, m, block, variant)
-    old_tails = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_EPILOGUE": "0"}, m, block, variant)
     assert in_order["stats"]["tail_groups"] == 0
-    for ref in (in_order, old_tails):
-        assert ref["stats"]["pipeline_redos"] == 0 and ref["stats"]["sb_bailouts"] == 0, ref["stats"]
-    _assert_same(old_tails, in_order, "tails with the epilogue against the step in order")
+    assert in_order["stats"]["pipeline_redos"] == 0 and in_order["stats"]["sb_bailouts"] == 0, in_order["stats"]
     for env in ({}, {"CONSENRICH_AMD_TAIL_PCT": "1,1"}, {"CONSENRICH_AMD_TAIL_PCT": "1,1", "CONSENRICH_AMD_EPILOGUE_PCT": "1"}):
         got = _run(monkeypatch, inputs, env, m, block, variant)
         print(m, block, variant, env, got["stats"])
@@ -138,7 +134,6 @@ def test_epilogue_groups_and_table_residuals_equal_the_step_in_order_and_the_old
         if _pipelines():
             assert got["stats"]["tail_groups"] >= 2, (env, got["stats"])        # two steps, at least one group each
         _assert_same(got, in_order, (env, "against the step in order"))
-        _assert_same(got, old_tails, (env, "against the tails with the epilogue"))
     bail = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_PCT": "1,1", "CONSENRICH_AMD_EPILOGUE_PCT": "1", "CONSENRICH_AMD_SB_SPIN_LIMIT": "1"},
                 m, block, variant)
     print(m, block, variant, "bail-out", bail["stats"])
@@ -151,7 +146,7 @@ def test_epilogue_groups_and_table_residuals_equal_the_step_in_order_and_the_old
 def test_a_pipelined_step_launches_no_blocked_copy_of_xf_and_one_residual_kernel_per_group(product, monkeypatch, inputs, m):
     """One constant process noise: the smoother of every tail group reads the reference layout, so nothing of the step reads a
     blocked xf -- no `state_reblock_out` launch; the residuals are one launch per tail group; the epilogue ran at least once per
-    step.  With CONSENRICH_AMD_TAIL_EPILOGUE=0 the tails import xf again (one launch per group)."""
+    step."""
     if not _pipelines() or os.environ.get("CONSENRICH_AMD_NATIN", "1") == "0":
         return      # (a mode switch of the whole suite: the step does not pipeline, or its smoother reads blocks)
     new = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_PCT": "1,1", "CONSENRICH_AMD_EPILOGUE_PCT": "1"}, m, 128, "plain", profile=True)
@@ -159,9 +154,6 @@ def test_a_pipelined_step_launches_no_blocked_copy_of_xf_and_one_residual_kernel
     assert new["launches"].get("state_reblock_out", 0) == 0, new["launches"]
     assert new["launches"]["residuals"] == new["stats"]["tail_groups"], (new["launches"], new["stats"])
     assert new["launches"]["fwd_dstat"] >= 2, new["launches"]
-    old = _run(monkeypatch, inputs, {"CONSENRICH_AMD_TAIL_PCT": "1,1", "CONSENRICH_AMD_TAIL_EPILOGUE": "0"}, m, 128, "plain", profile=True)
-    assert old["launches"]["state_reblock_out"] == old["stats"]["tail_groups"], (old["launches"], old["stats"])
-    assert old["launches"]["fwd_dstat"] == old["stats"]["tail_groups"], (old["launches"], old["stats"])
 
 
 @pytest.mark.parametrize("block", [64, 128, 256])
