@@ -152,11 +152,20 @@ class RoccoStats(C.Structure):
                 ("d2h_bytes", C.c_int64), ("depth", C.c_int32), ("reserved", C.c_int32)]
 
 
+class NullOut(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("null_center", "null_scale", "bulk_quantile", "bulk_cutoff", "provisional_center",
+                                          "support_radius", "support_scale", "support_fraction", "clip_abs", "template_std",
+                                          "template_mean")] + \
+               [("support_size", C.c_int64), ("lower_bulk_size", C.c_int64), ("bulk_source", C.c_int32),
+                ("center_method", C.c_int32), ("null_method", C.c_int32), ("host_fallback", C.c_int32)]
+
+
 ROCCO_FIXED_PENALTY, ROCCO_TARGET_COUNT = 0, 1
 ROCCO_SCORE_STATE, ROCCO_SCORE_LOWER_CONFIDENCE = 0, 1
 ROCCO_ERR_VALUE = 2
 DWB_ERR_VALUE = 2
 SEG_ERR_VALUE = 2
+NULL_ERR_VALUE = 2
 
 
 class KernelTime(C.Structure):
@@ -283,6 +292,14 @@ SYMBOLS = {
     "csr_segments_flagged_fetch": (C.c_int, [C.c_void_p, C.c_int32, DP, I64P]),
     "csr_segments_flagged_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, I64P]),
     "csr_segments_fetch": (C.c_int, [C.c_void_p, I64P, I64P, I64P, I64P, DP, DP, DP, DP]),
+    "csr_null_prepare": (C.c_int, [DP, C.c_int64, C.c_double, DP, C.POINTER(NullOut), DP]),
+    "csr_null_scale": (C.c_int, [DP, C.c_int64, DP]),
+    "csr_null_sort": (C.c_int, [DP, C.c_int64, DP]),
+    "csr_batch_null_prepare": (C.c_int, [C.c_void_p, C.c_double, C.c_char_p, C.POINTER(NullOut)]),
+    "csr_batch_null_template_download": (C.c_int, [C.c_void_p, C.c_int32, DP]),
+    "csr_batch_null_template_upload": (C.c_int, [C.c_void_p, C.c_int32, DP]),
+    "csr_batch_null_pooled_scale": (C.c_int, [C.c_void_p, C.c_char_p, DP]),
+    "csr_batch_dwb_panel_begin": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, DP, C.c_int64, C.c_int32, C.c_int32]),
 }
 
 _lib = None

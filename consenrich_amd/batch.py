@@ -68,6 +68,7 @@ class DeviceBatch:
         self.d = 2
         self._comms = []
         self._rocco_count = {}      # selected bins per chain of the last rocco() (an upper bound of its runs)
+        self._null = {}             # chain -> (null centre, null scale) of the last rocco_null()
 
     def _attach_comm(self, comm):
         self._comms.append(comm)
@@ -107,6 +108,7 @@ class DeviceBatch:
         self.chain_lens = [int(v) for v in lens]
         self.m, self.d = int(m), int(model.state_dim)
         self.model = model
+        self._null = {}             # the templates died with the previous batch
 
     def set_model(self, model: ModelParams):
         mdl = model.to_c()
@@ -529,14 +531,83 @@ class DeviceBatch:
         return {k: getattr(rs, k) for k, _ in L.RoccoStats._fields_ if k != "reserved"}
 
     # -- stationary-null DWB panel behind the ROCCO budgets (consenrich_amd/dwb.py) -------------------------------------------
-    def dwb_panel(self, templates, null_centers, null_scales, *, threshold_z_grid, tail_quantiles=None, bandwidths,
+    # -- robust null of the resident scores: centre, scale and DWB template (consenrich_amd/null.py) --------------------------
+    def _chain_mask(self, chains):
+        nc = len(self.chain_lens)
+        take = [True] * nc if chains is None else [bool(t) for t in chains]
+        if len(take) != nc:
+            raise ValueError("one mask entry per chain")
+        return take, (None if chains is None else bytes(bytearray(int(t) for t in take)))
+
+    def rocco_null(self, bulk_quantile: float = 0.60, chains=None):
+        """`estimateROCCONull` and `_prepareNullResidualTemplate` (peaks.py:499-540, 1077-1122) of the chains' RESIDENT score
+        tracks in one call.  chains: optional per-chain booleans; chains with False keep what they had.  Returns one dict per
+        chain (None where not taken): null_center, null_scale, details (the reference's dict), template_meta (the reference's
+        template dict) and decided_on_host.  The templates stay on the device (download_template; dwb_panel / dwb_replay with
+        templates=None); neither the scores nor any array of the fit changes.  A chain whose central support falls short (see
+        consenrich_amd.null) is decided by NumPy from its downloaded track and its template uploaded."""
+        from . import null as N
+
+        take, mask = self._chain_mask(chains)
+        nc = len(take)
+        out = (L.NullOut * nc)()
+        N._call(self._lib.csr_batch_null_prepare(self._ctx, float(bulk_quantile), mask, out))
+        res = [None] * nc
+        for i in range(nc):
+            if not take[i]:
+                continue
+            if out[i].host_fallback:
+                res[i], template = N.host_result(self.download_scores(i), bulk_quantile)
+                self.upload_template(i, template)
+            else:
+                res[i] = N.chain_result(out[i], self.chain_lens[i])
+            self._null[i] = (res[i]["null_center"], res[i]["null_scale"])
+        return res
+
+    def download_template(self, chain: int) -> np.ndarray:
+        out = np.empty(self.chain_lens[chain], np.float64)
+        L.check(self._lib.csr_batch_null_template_download(self._ctx, int(chain), L.dp(out)))
+        return out
+
+    def upload_template(self, chain: int, template):
+        t = np.ascontiguousarray(np.asarray(template, dtype=np.float64).ravel())
+        if t.shape != (self.chain_lens[chain],):
+            raise ValueError("template must have shape (chain_len,)")
+        if not np.all(np.isfinite(t)):
+            raise ValueError("`template` contains non-finite values")
+        L.check(self._lib.csr_batch_null_template_upload(self._ctx, int(chain), L.dp(t)))
+
+    def null_pooled_scale(self, chains=None) -> float:
+        """`_estimateTemplateScale` (peaks.py:543-556) of the selected chains' resident templates concatenated in chain order
+        (the pooled null floor, peaks.py:950-951), on the device."""
+        from . import null as N
+
+        _, mask = self._chain_mask(chains)
+        out = np.empty(4, np.float64)
+        N._call(self._lib.csr_batch_null_pooled_scale(self._ctx, mask, L.dp(out)))
+        return float(out[0])
+
+    def _resident_null(self, null_centers, null_scales):
+        """None = what rocco_null left, for every chain."""
+        nc = len(self.chain_lens)
+        if (null_centers is None or null_scales is None) and any(i not in self._null for i in range(nc)):
+            raise ValueError("null_centers / null_scales of None need a rocco_null() of every chain first")
+        if null_centers is None:
+            null_centers = [self._null[i][0] for i in range(nc)]
+        if null_scales is None:
+            null_scales = [self._null[i][1] for i in range(nc)]
+        return null_centers, null_scales
+
+    def dwb_panel(self, templates=None, null_centers=None, null_scales=None, *, threshold_z_grid, tail_quantiles=None, bandwidths,
                   num_bootstrap=128, kernel="bartlett", random_seed=0, calibration_quantile=0.9, pooled_floors=None,
                   draws_per_group=0, noise=None):
         """`dwb.stationary_null_panel` for the batch's chains with the observed statistics taken from the RESIDENT score tracks
-        (rocco_scores / upload_scores): nothing of the fit is downloaded, and no resident array changes."""
+        (rocco_scores / upload_scores): nothing of the fit is downloaded, and no resident array changes.  templates /
+        null_centers / null_scales of None: what rocco_null left on the device (no template is uploaded)."""
         from . import dwb as W
 
         batch = self
+        null_centers, null_scales = self._resident_null(null_centers, null_scales)
 
         class _Resident:
             def length(self, c):
@@ -588,12 +659,16 @@ class DeviceBatch:
         total_cap, view_cap = S._caps(max_segments, max_segments_per_view)
         return self._segment_tracks(views, scales, max(int(min_run_bins), 1), max(int(max_gap_bins), 0), total_cap, view_cap)
 
-    def dwb_replay(self, templates, threshold_views, *, bandwidths, num_replay=64, kernel="bartlett", random_seed=0,
+    def dwb_replay(self, templates=None, threshold_views=None, *, bandwidths, num_replay=64, kernel="bartlett", random_seed=0,
                    scale_bins=None, min_run_bins=1, max_gap_bins=0, max_segments=20000, max_segments_per_view=1000,
                    draws_per_group=0, noise=None):
         """`dwb.null_replay_candidates` for the batch's chains with the observed candidates taken from the RESIDENT score
-        tracks; the replays use buffers of the panel's own.  No resident array changes."""
+        tracks; the replays use buffers of the panel's own.  No resident array changes.  templates=None: the resident
+        templates rocco_null left."""
         from . import dwb as W
+
+        if threshold_views is None:
+            raise TypeError("dwb_replay() needs threshold_views")
 
         return W._run_replays(self._ctx, self._segment_tracks, list(self.chain_lens), templates, threshold_views,
                               bandwidths=bandwidths, num_replay=num_replay, kernel=kernel, random_seed=random_seed,

@@ -13,8 +13,8 @@
 //   k_dwb_select  the exact order statistics of a row at up to DWB_MAX_RANKS ranks: a byte-wise radix select like csr_gain.h's,
 //                 on a plain double array, one workgroup per row, eight passes inside one launch;
 //   k_dwb_tail    count(x > offset) and the sum of clip((x - offset) / scale, 0, inf) in NumPy's summation order: one thread per
-//                 (chunk of 8192, z) evaluates NumPy's pairwise tree of that chunk; k_dwb_tail_fold folds the chunk sums in
-//                 ascending order and divides by n.
+//                 (chunk of 8192, z) evaluates NumPy's pairwise tree of that chunk (dwb_chunk_sum_f, over any element
+//                 expression: csr_null.h sums with it too); k_dwb_tail_fold folds the chunk sums in ascending order and divides by n.
 // Nothing here waits on another workgroup: every dependency is a kernel boundary, every loop bound is known at launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -270,40 +270,30 @@ __device__ __forceinline__ double dwb_excess(double x, double off, double s) {
     const double v = __ddiv_rn(x - off, s);
     return (v > 0.0 || v != v) ? v : 0.0;
 }
-// NumPy's pairwise sum of a block of 8 <= n <= 128 values (eight strided accumulators, then the remainder in order) or of
-// n < 8 values (in order)
-__device__ __forceinline__ double dwb_leaf(const double *x, int n, double off, double s, long long &cnt) {
+// NumPy's pairwise sum of f(x[i]) over a block of 8 <= n <= 128 values (eight strided accumulators, then the remainder in order)
+// or of n < 8 values (in order); f is evaluated once per element, in the order NumPy adds them
+template <class F>
+__device__ __forceinline__ double dwb_leaf_f(const double *x, int n, F &f) {
     if (n < 8) {
         double res = 0.0;
-        for (int i = 0; i < n; ++i) {
-            cnt += x[i] > off;
-            res = res + dwb_excess(x[i], off, s);
-        }
+        for (int i = 0; i < n; ++i) res = res + f(x[i]);
         return res;
     }
     double r[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        cnt += x[k] > off;
-        r[k] = dwb_excess(x[k], off, s);
-    }
+    for (int k = 0; k < 8; ++k) r[k] = f(x[k]);
     int i = 8;
     for (; i < n - (n % 8); i += 8) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            cnt += x[i + k] > off;
-            r[k] = r[k] + dwb_excess(x[i + k], off, s);
-        }
+        for (int k = 0; k < 8; ++k) r[k] = r[k] + f(x[i + k]);
     }
     double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) {
-        cnt += x[i] > off;
-        res = res + dwb_excess(x[i], off, s);
-    }
+    for (; i < n; ++i) res = res + f(x[i]);
     return res;
 }
 // the pairwise tree of one chunk (n <= DWB_CHUNK): blocks above 128 values split at n/2 - (n/2) % 8
-__device__ double dwb_chunk_sum(const double *x, int n, double off, double s, long long &cnt) {
+template <class F>
+__device__ double dwb_chunk_sum_f(const double *x, int n, F &f) {
     int lo[12], len[12], stage[12];
     double left[12];
     int sp = 0;
@@ -312,7 +302,7 @@ __device__ double dwb_chunk_sum(const double *x, int n, double off, double s, lo
     while (sp >= 0) {
         if (stage[sp] == 0) {
             if (len[sp] <= 128) {
-                ret = dwb_leaf(x + lo[sp], len[sp], off, s, cnt);
+                ret = dwb_leaf_f(x + lo[sp], len[sp], f);
                 --sp;
                 continue;
             }
@@ -334,6 +324,19 @@ __device__ double dwb_chunk_sum(const double *x, int n, double off, double s, lo
         }
     }
     return ret;
+}
+// the element of the tail statistics: counts x > off on the way
+struct DwbExcess {
+    double off, s;
+    long long &cnt;
+    __device__ __forceinline__ double operator()(double x) {
+        cnt += x > off;
+        return dwb_excess(x, off, s);
+    }
+};
+__device__ __forceinline__ double dwb_chunk_sum(const double *x, int n, double off, double s, long long &cnt) {
+    DwbExcess f{off, s, cnt};
+    return dwb_chunk_sum_f(x, n, f);
 }
 struct DwbTailArgs {
     const DwbChain *chains;

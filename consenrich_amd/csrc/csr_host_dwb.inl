@@ -243,9 +243,10 @@ static int dwb_ctx(csr_ctx *&c) {
     return ctx_select(c);
 }
 
-extern "C" int csr_dwb_panel_begin(csr_ctx *c, int32_t n_chains, const int64_t *chain_len, const int32_t *bandwidth,
-                                   const char *kernel, const double *templates, const double *noise, int64_t noise_len,
-                                   int32_t n_draws, int32_t draws_per_group) {
+// templates[i]: chain i's template, on the host or on the device as `kind` says
+static int dwb_panel_begin(csr_ctx *c, int32_t n_chains, const int64_t *chain_len, const int32_t *bandwidth, const char *kernel,
+                           const double *const *templates, hipMemcpyKind kind, const double *noise, int64_t noise_len, int32_t n_draws,
+                           int32_t draws_per_group) {
     DEFAULT_CTX_GUARD;
     int code = 0;
     CHECK(dwb_kernel_code(kernel, &code));
@@ -268,16 +269,30 @@ extern "C" int csr_dwb_panel_begin(csr_ctx *c, int32_t n_chains, const int64_t *
     CHECK(d.rowBuf.reserve(8 * (size_t)d.rowLen * (size_t)d.group));
     CHECK(d.tmplBuf.reserve(8 * (size_t)d.rowLen));
     CHECK(d.noiseBuf.reserve(8 * (size_t)n_draws * (size_t)d.strideMax));
-    int64_t so = 0;
-    for (int i = 0; i < n_chains; ++i) {
-        HIPOK(hipMemcpyAsync((double *)d.tmplBuf.ptr + d.chains[i].off, templates + so, 8 * (size_t)chain_len[i], hipMemcpyHostToDevice,
-                             c->stream));
-        so += chain_len[i];
-    }
+    for (int i = 0; i < n_chains; ++i)
+        HIPOK(hipMemcpyAsync((double *)d.tmplBuf.ptr + d.chains[i].off, templates[i], 8 * (size_t)chain_len[i], kind, c->stream));
     HIPOK(hipMemcpyAsync(d.noiseBuf.ptr, noise, 8 * (size_t)n_draws * (size_t)d.strideMax, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
     d.ready = true;
     return 0;
+}
+
+extern "C" int csr_dwb_panel_begin(csr_ctx *c, int32_t n_chains, const int64_t *chain_len, const int32_t *bandwidth,
+                                   const char *kernel, const double *templates, const double *noise, int64_t noise_len,
+                                   int32_t n_draws, int32_t draws_per_group) {
+    if (n_chains <= 0 || !chain_len || !templates) {
+        int code = 0;
+        CHECK(dwb_kernel_code(kernel, &code));
+        return fail("null or empty argument");
+    }
+    std::vector<const double *> tp((size_t)n_chains);
+    int64_t so = 0;
+    for (int i = 0; i < n_chains; ++i) {
+        tp[i] = templates + so;
+        so += chain_len[i];
+    }
+    return dwb_panel_begin(c, n_chains, chain_len, bandwidth, kernel, tp.data(), hipMemcpyHostToDevice, noise, noise_len, n_draws,
+                           draws_per_group);
 }
 
 // ranks[chain][n_ranks] (-1 = unused: NaN comes back); out[chain][draw][rank]

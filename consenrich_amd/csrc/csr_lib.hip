@@ -12,6 +12,7 @@
 #include "csr_gain.h"
 #include "csr_rocco.h"
 #include "csr_dwb.h"
+#include "csr_null.h"
 #include "csr_segments.h"
 #include "csr_step_groups.h"
 
@@ -320,6 +321,12 @@ struct BatchState {
         int *bad = nullptr;
         std::vector<char> haveScores, haveSol;
     } rocco;
+    // robust null (csr_host_null.inl): one DWB residual template per chain, laid out like the score tracks (allocated at first use);
+    // have[chain]: csr_batch_null_prepare or csr_batch_null_template_upload left one
+    struct NullRes {
+        double *tmpl = nullptr;
+        std::vector<char> have;
+    } nullRes;
     // stats
     csr_run_stats rs{};
 };
@@ -423,6 +430,11 @@ struct csr_ctx : BatchState {
         int nDraws = 0, group = 0;
         DevBuf chainBuf, wtsBuf, tmplBuf, noiseBuf, rowBuf, partBuf, outBuf, vecBuf, xBuf, meanBuf;
     } dwb;
+    // robust null (csr_host_null.inl): growable work space of a call -- track table, the two key buffers of the sort, the compacted
+    // supports and their tile counts, chunk sums, job tables, small results, uploaded host vectors
+    struct NullWs {
+        DevBuf trackBuf, keysA, keysB, comp, cnt, part, jobBuf, outBuf, xBuf;
+    } nullWs;
     // multiscale candidate segments (csr_host_segments.inl): growable work space and the result of the last run, which stays
     // until the next run so that the caller can resolve flagged views and fetch the rows
     struct Seg {
@@ -767,4 +779,5 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_comm.inl"
 #include "csr_host_rocco.inl"
 #include "csr_host_dwb.inl"
+#include "csr_host_null.inl"
 #include "csr_host_segments.inl"

@@ -7,8 +7,9 @@ order statistics and their tail statistics come from the C ABI (`csr_dwb_*`, csr
 bit for bit; what is left on the host is the noise stream (NumPy's generator, one stream per seed), the lerp between two order
 statistics, and the reductions over the B draws.  No CPU fallback.
 
-What stays with the caller: the dependence span (bandwidth), the null centre / scale / template, and the policy that turns the
-returned metrics into a budget.
+What stays with the caller: the dependence span (bandwidth) and the policy that turns the returned metrics into a budget.  The
+null centre / scale / template come from `consenrich_amd.null` (host arrays) or `DeviceBatch.rocco_null` (resident: a batch's panel
+and replays then take `templates=None`).
 """
 from __future__ import annotations
 
@@ -148,6 +149,29 @@ def _tail_of_vector(x, thresholds, scales):
     return cnt, soft
 
 
+def _checked_templates(templates, lens):
+    """The chains' templates as float64 vectors; None = the batch's resident ones (DeviceBatch.rocco_null), checked by the library."""
+    if templates is None:
+        return None
+    tmpl = [_f64(t) for t in templates]
+    for c in range(len(lens)):
+        if tmpl[c].shape[0] != lens[c] or lens[c] <= 0:
+            raise ValueError("a template must be as long as its chain's score track and not empty")
+        if not np.all(np.isfinite(tmpl[c])):
+            raise ValueError("`template` contains non-finite values")
+    return tmpl
+
+
+def _begin_panel(lib, ctx, n_arr, bw_arr, kernel, tmpl, z_stream, n_draws, draws_per_group):
+    bw_p = bw_arr.ctypes.data_as(C.POINTER(C.c_int32))
+    if tmpl is None:        # the resident templates of the batch context: nothing is uploaded but the noise
+        _call(lib.csr_batch_dwb_panel_begin(ctx, bw_p, _kname(kernel), L.dp(z_stream), z_stream.shape[0], n_draws, draws_per_group))
+        return
+    t_all = np.ascontiguousarray(np.concatenate(tmpl))
+    _call(lib.csr_dwb_panel_begin(ctx, len(n_arr), n_arr.ctypes.data_as(L.I64P), bw_p, _kname(kernel), L.dp(t_all), L.dp(z_stream),
+                                  z_stream.shape[0], n_draws, draws_per_group))
+
+
 def _run_panel(ctx, observed, lens, templates, null_centers, null_scales, *, threshold_z_grid, tail_quantiles, bandwidths,
                num_bootstrap, kernel, random_seed, calibration_quantile, pooled_floors, draws_per_group, noise):
     nc = len(lens)
@@ -164,14 +188,9 @@ def _run_panel(ctx, observed, lens, templates, null_centers, null_scales, *, thr
     bws = [_c_int(b) for b in (bandwidths if np.ndim(bandwidths) else [bandwidths] * nc)]
     centers = [float(v) for v in (null_centers if np.ndim(null_centers) else [null_centers] * nc)]
     scales0 = [float(v) for v in (null_scales if np.ndim(null_scales) else [null_scales] * nc)]
-    if not (len(bws) == len(centers) == len(scales0) == len(templates) == nc):
+    if not (len(bws) == len(centers) == len(scales0) == nc) or (templates is not None and len(templates) != nc):
         raise ValueError("one bandwidth, null centre, null scale and template per chain")
-    tmpl = [_f64(t) for t in templates]
-    for c in range(nc):
-        if tmpl[c].shape[0] != lens[c] or lens[c] <= 0:
-            raise ValueError("a template must be as long as its chain's score track and not empty")
-        if not np.all(np.isfinite(tmpl[c])):
-            raise ValueError("`template` contains non-finite values")
+    tmpl = _checked_templates(templates, lens)
     floors = None
     if pooled_floors is not None:
         floors = np.asarray(pooled_floors, np.float64)
@@ -191,9 +210,7 @@ def _run_panel(ctx, observed, lens, templates, null_centers, null_scales, *, thr
             ranks[c, 2 * k], ranks[c, 2 * k + 1], gam[c, k] = quantile_ranks(lens[c], tq[k])
     n_arr = np.asarray(lens, np.int64)
     bw_arr = np.asarray(bws, np.int32)
-    t_all = np.ascontiguousarray(np.concatenate(tmpl))
-    _call(lib.csr_dwb_panel_begin(ctx, nc, n_arr.ctypes.data_as(L.I64P), bw_arr.ctypes.data_as(C.POINTER(C.c_int32)), _kname(kernel),
-                                  L.dp(t_all), L.dp(z_stream), z_stream.shape[0], B, int(draws_per_group)))
+    _begin_panel(lib, ctx, n_arr, bw_arr, kernel, tmpl, z_stream, B, int(draws_per_group))
     try:
         # phase A: two order statistics per (draw, z); the lerp and the reductions over the draws on the host
         os_ = np.empty((nc, B, 2 * nz), np.float64)
@@ -321,14 +338,9 @@ def _run_replays(ctx, observed, lens, templates, threshold_views, *, bandwidths,
     if view_cap is None:
         raise ValueError("null replays on the device need max_segments_per_view > 0")
     bws = [_c_int(b) for b in (bandwidths if np.ndim(bandwidths) else [bandwidths] * nc)]
-    if not (len(bws) == len(templates) == len(threshold_views) == nc):
+    if not (len(bws) == len(threshold_views) == nc) or (templates is not None and len(templates) != nc):
         raise ValueError("one bandwidth, template and set of threshold views per chain")
-    tmpl = [_f64(t) for t in templates]
-    for c in range(nc):
-        if tmpl[c].shape[0] != lens[c] or lens[c] <= 0:
-            raise ValueError("a template must be as long as its chain's score track and not empty")
-        if not np.all(np.isfinite(tmpl[c])):
-            raise ValueError("`template` contains non-finite values")
+    tmpl = _checked_templates(templates, lens)
     views = [S.Views(v) for v in threshold_views]
     replay_views = [v.for_replay() for v in views]
     per_chain_bins = scale_bins is not None and len(scale_bins) > 0 and np.ndim(scale_bins[0]) > 0
@@ -343,12 +355,10 @@ def _run_replays(ctx, observed, lens, templates, threshold_views, *, bandwidths,
     lib = L.lib()
     group = _replay_group(lens, [len(s) for s in scales], [len(v.keys) for v in views], R, draws_per_group)
     n_arr, bw_arr = np.asarray(lens, np.int64), np.asarray(bws, np.int32)
-    t_all = np.ascontiguousarray(np.concatenate(tmpl))
     n_s, sc_all, n_v, thr_all, ns_all = S.pack(scales, [v.threshold for v in replay_views], [v.null_scale for v in replay_views])
     replays = [[None] * R for _ in range(nc)]
     capped = fallback = 0
-    _call(lib.csr_dwb_panel_begin(ctx, nc, n_arr.ctypes.data_as(L.I64P), bw_arr.ctypes.data_as(C.POINTER(C.c_int32)), _kname(kernel),
-                                  L.dp(t_all), L.dp(z_stream), z_stream.shape[0], R, group))
+    _begin_panel(lib, ctx, n_arr, bw_arr, kernel, tmpl, z_stream, R, group)
     try:
         for d0 in range(0, R, group):
             g = min(group, R - d0)

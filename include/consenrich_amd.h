@@ -634,6 +634,47 @@ int csr_segments_flagged_select(csr_ctx *ctx, int32_t k, int64_t n_selected, con
 int csr_segments_fetch(csr_ctx *ctx, int64_t *start, int64_t *end, int64_t *scale, int64_t *view, double *score,
                        double *integrated, double *mean, double *max_excess);
 
+/* ---- the robust null of a ROCCO score track: peaks.py:312-339 `_halfSampleMode`, 418-496 `_selectRobustNullSupport`, 499-540
+ * `estimateROCCONull`, 543-556 `_estimateTemplateScale`, 1077-1122 `_prepareNullResidualTemplate` ------------------------------
+ * Every value equals the reference's bit for bit (a zero may differ in sign when the track holds -0.0: the device orders -0.0
+ * before +0.0, np.sort does not).  The track is sorted on the device; order statistics, the half-sample mode, the stable
+ * compaction of the support and NumPy-order sums come from kernels, the scalars between them are composed on the host.
+ * host_fallback = 1: the central support holds fewer than max(16, ceil(0.05 n)) values (always so below 16 values).  The reference
+ * then takes an UNSTABLE argsort of the track, whose tie order the values do not determine: the caller decides such a track with
+ * NumPy; the fields up to support_size are filled as far as they were reached, no template is left.
+ * A non-finite or empty vector returns CSR_NULL_ERR_VALUE with the reference's ValueError text, before any launch. */
+enum { CSR_NULL_ERR_VALUE = 2 };
+enum { CSR_NULL_LOWER_BULK = 0, CSR_NULL_FULL_TRACK = 1 };                  /* bulk_source */
+enum { CSR_NULL_HALF_SAMPLE_MODE = 0, CSR_NULL_MEDIAN = 1 };                /* center_method (after the bulk source) */
+enum { CSR_NULL_CENTRAL_SUPPORT = 0, CSR_NULL_NEAREST_SUPPORT = 1 };        /* null_method */
+typedef struct csr_null_out {
+    double null_center, null_scale;
+    double bulk_quantile, bulk_cutoff, provisional_center, support_radius, support_scale, support_fraction;
+    double clip_abs, template_std, template_mean;
+    int64_t support_size, lower_bulk_size;
+    int32_t bulk_source, center_method, null_method, host_fallback;
+} csr_null_out;
+/* Host arrays (default context).  given: NULL, or {null centre, null scale} around which the template is built instead of the
+ * track's own (the arguments of `_prepareNullResidualTemplate`).  template_out: n values or NULL.
+ * csr_null_scale: out[4] = `_estimateTemplateScale`, then its MAD-, IQR- and std-based parts. */
+int csr_null_prepare(const double *scores, int64_t n, double bulk_quantile, const double *given, csr_null_out *out,
+                     double *template_out);
+int csr_null_scale(const double *x, int64_t n, double *out);
+/* The device's ascending sort of a finite vector (keys only: a function of the values alone), n values out. */
+int csr_null_sort(const double *x, int64_t n, double *out);
+/* The RESIDENT score tracks of a batch (csr_batch_rocco_scores / csr_batch_upload_scores) for the chains of chain_mask (n_chains
+ * bytes or NULL = all); out: n_chains records, those of the other chains untouched.  The templates stay on the device in a buffer
+ * of the batch's own; no array of the fit or of the scores changes.  template_upload plants a chain's template (a host-decided
+ * chain's, a test's).  pooled_scale: csr_null_scale of the selected chains' templates concatenated in chain order. */
+int csr_batch_null_prepare(csr_ctx *ctx, double bulk_quantile, const unsigned char *chain_mask, csr_null_out *out);
+int csr_batch_null_template_download(csr_ctx *ctx, int32_t chain, double *host_dst);
+int csr_batch_null_template_upload(csr_ctx *ctx, int32_t chain, const double *tmpl);
+int csr_batch_null_pooled_scale(csr_ctx *ctx, const unsigned char *chain_mask, double *out);
+/* csr_dwb_panel_begin over ALL chains of the batch with their resident templates (every chain needs one); the other panel calls
+ * follow as usual. */
+int csr_batch_dwb_panel_begin(csr_ctx *ctx, const int32_t *bandwidth, const char *kernel, const double *noise, int64_t noise_len,
+                              int32_t n_draws, int32_t draws_per_group);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
