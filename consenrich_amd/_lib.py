@@ -160,12 +160,18 @@ class NullOut(C.Structure):
                 ("center_method", C.c_int32), ("null_method", C.c_int32), ("host_fallback", C.c_int32)]
 
 
+class EssOut(C.Structure):
+    _fields_ = [("n_eff", C.c_double), ("tau", C.c_double), ("lags_used", C.c_int64)]
+
+
 ROCCO_FIXED_PENALTY, ROCCO_TARGET_COUNT = 0, 1
 ROCCO_SCORE_STATE, ROCCO_SCORE_LOWER_CONFIDENCE = 0, 1
 ROCCO_ERR_VALUE = 2
 DWB_ERR_VALUE = 2
 SEG_ERR_VALUE = 2
 NULL_ERR_VALUE = 2
+ESS_ERR_VALUE = 2
+ESS_OCCUPANCY, ESS_SOFT, ESS_INTEGRATED = 1, 2, 3
 
 
 class KernelTime(C.Structure):
@@ -300,6 +306,10 @@ SYMBOLS = {
     "csr_batch_null_template_upload": (C.c_int, [C.c_void_p, C.c_int32, DP]),
     "csr_batch_null_pooled_scale": (C.c_int, [C.c_void_p, C.c_char_p, DP]),
     "csr_batch_dwb_panel_begin": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, DP, C.c_int64, C.c_int32, C.c_int32]),
+    "csr_ess_scan": (C.c_int, [DP, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.c_int32, C.c_int64, C.POINTER(EssOut)]),
+    "csr_batch_ess": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, DP, DP, I64P, C.c_char_p, C.POINTER(EssOut)]),
+    "csr_batch_rocco_excess_ranks": (C.c_int, [C.c_void_p, DP, C.c_char_p, I64P, DP]),
+    "csr_batch_rocco_upload": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8)]),
 }
 
 _lib = None

@@ -31,6 +31,7 @@ __all__ = [
     "cfixedBackgroundECMLevel", "cExpectedTransitionResidualSums", "cExpectedTransitionResidualSumsLevel",
     "csolvePenalizedChainROCCO", "ccalibrateSelectionPenaltyROCCO", "csolveChromROCCOExact",
     "cGenerateDWBMultipliersFromNoise", "cApplyStationaryNullDWB", "cStationaryNullDWBDraw",
+    "cEstimateEffectiveSampleSize",
 ]
 
 
@@ -633,3 +634,6 @@ from .dwb import (  # noqa: E402,F401
 
 # multiscale candidate segments of a score track or a null replay (pyx:9460-9669), implemented in consenrich_amd/segments.py
 from .segments import cMultiscaleCandidateSegmentStats  # noqa: E402,F401
+
+# effective sample size scan behind the ROCCO budget (pyx:9160-9279), implemented in consenrich_amd/ess.py
+from .ess import cEstimateEffectiveSampleSize  # noqa: E402,F401

@@ -14,6 +14,7 @@
 #include "csr_dwb.h"
 #include "csr_null.h"
 #include "csr_segments.h"
+#include "csr_ess.h"
 #include "csr_step_groups.h"
 
 #include <algorithm>
@@ -435,6 +436,11 @@ struct csr_ctx : BatchState {
     struct NullWs {
         DevBuf trackBuf, keysA, keysB, comp, cnt, part, jobBuf, outBuf, xBuf;
     } nullWs;
+    // effective sample size scan (csr_host_ess.inl): growable work space of a call -- track table, the centred series, the sums and
+    // pair counts of a round of lags, the means, an uploaded host vector and its mask
+    struct EssWs {
+        DevBuf trackBuf, cenBuf, sumBuf, pairBuf, outBuf, xBuf, maskBuf;
+    } essWs;
     // multiscale candidate segments (csr_host_segments.inl): growable work space and the result of the last run, which stays
     // until the next run so that the caller can resolve flagged views and fetch the rows
     struct Seg {
@@ -781,3 +787,4 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_dwb.inl"
 #include "csr_host_null.inl"
 #include "csr_host_segments.inl"
+#include "csr_host_ess.inl"

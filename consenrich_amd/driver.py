@@ -571,12 +571,67 @@ def call_peaks_batch(batch: DeviceBatch, *, budget=None, gamma=0.5, selection_pe
     """The last native stage of the reference's per-chromosome loop (`solveChromROCCO`, peaks.py:1783) for every chain of a
     fitted batch, on the device: score track from the resident smoothed fit -> budgeted chain selection
     (`csolveChromROCCOExact`) -> run bounds of the mask (`cBooleanRunBounds`).  Thin composition of DeviceBatch.rocco_scores /
-    rocco / rocco_runs; the rest of peaks.py (null model, gamma from the dependence span, budget estimation, fallbacks,
-    merging) stays with the caller, who passes their results as budget / gamma.  Returns one dict per chain (None for a
+    rocco / rocco_runs with the caller's budget / gamma; `first_pass_peaks_batch` below derives both on the device (null model,
+    budget estimation, gamma from the dependence span, the fallback window) and needs neither.  Returns one dict per chain (None for a
     chain masked out): the values of the reference's tuple plus `starts` / `ends` (inclusive bin indices)."""
     batch.rocco_scores(score_mode, z)
     res = batch.rocco(budget=budget, gamma=gamma, selection_penalty=selection_penalty, max_iter=max_iter, chains=chains)
     for ch, r in enumerate(res):
         if r is not None:
             r["starts"], r["ends"] = batch.rocco_runs(ch, max_gap_bins)
+    return res
+
+
+def first_pass_peaks_batch(batch: DeviceBatch, *, dependence_spans, threshold_z, threshold_z_grid, num_bootstrap, random_seed,
+                           gamma, gamma_scale, selection_penalty=None, score_mode, z, max_gap_bins,
+                           pooled_floors=None) -> List[dict]:
+    """The reference's per-chromosome path from a fit to the first-pass solution (`solveRocco`, peaks.py:6700-6833) for every
+    chain of a fitted batch, without a track leaving the device and without a score-derived number from the caller:
+    rocco_scores -> rocco_null -> dwb_panel -> rocco_budget -> rocco_gamma -> rocco -> rocco_runs.  The dependence span stays an
+    input (one per chain or one for all; below 2 it counts as 2 and is the DWB bandwidth, as in the reference); the budget is
+    the reference's "occupancy" statistic, not shrunk across chromosomes (`solveRocco` does not apply `shrinkROCCOBudgets`);
+    random_seed is the seed of every chain's panel (the reference passes its seed plus the chromosome's index: call once per
+    seed to reproduce that).
+
+    Includes the wrapper of `solveChromROCCO` (peaks.py:1804-1835): a chain that selects nothing although floor(n * budget) is
+    positive is given the best contiguous window of that many bins if it passes the reference's 5 % range test.  That chain
+    alone is decided on the host from its downloaded track with the reference's NumPy steps (rare; its cumulative sum is
+    sequential), its mask uploaded, its objectives recomputed.
+
+    Returns one dict per chain: objective, penalized_objective, selected_count, selection_penalty, gamma, budget,
+    budget_target_count, budget_fallback_window, budget_details, gamma_details, null, starts / ends (inclusive bin indices)."""
+    from . import ess as E
+    from . import rocco as R
+
+    nc = len(batch.chain_lens)
+    spans = [max(int(s), 2) for s in (dependence_spans if np.ndim(dependence_spans) else [dependence_spans] * nc)]
+    if len(spans) != nc:
+        raise ValueError("one dependence span per chain")
+    grid = E.resolve_z_grid(threshold_z, threshold_z_grid)
+    batch.rocco_scores(score_mode, z)
+    null = batch.rocco_null()
+    panel = batch.dwb_panel(threshold_z_grid=grid, bandwidths=spans, num_bootstrap=num_bootstrap, random_seed=random_seed,
+                            calibration_quantile=0.9, pooled_floors=pooled_floors)
+    budgets = batch.rocco_budget(panel, statistic="occupancy", threshold_z=threshold_z, threshold_z_grid=grid,
+                                 dependence_spans=spans)
+    gammas = batch.rocco_gamma(gamma, dependence_spans=spans, gamma_spans=spans, gamma_scale=gamma_scale,
+                               null_centers=[b["null_center"] for b in budgets], thresholds=[b["threshold"] for b in budgets])
+    res = batch.rocco(budget=[b["budget"] for b in budgets], gamma=[g for g, _ in gammas], selection_penalty=selection_penalty)
+    for ch, r in enumerate(res):
+        n, g = batch.chain_lens[ch], gammas[ch][0]
+        r.update(gamma=g, budget=budgets[ch]["budget"], budget_details=budgets[ch], gamma_details=gammas[ch][1], null=null[ch],
+                 budget_target_count=None, budget_fallback_window=False)
+        if selection_penalty is None:
+            r["budget_target_count"] = target = R.budget_target_count(n, r["budget"])
+            if r["selected_count"] == 0 and target is not None and target > 0:
+                scores = batch.download_scores(ch)
+                mask, used = R.best_contiguous_budget_fallback_mask(scores, target, 0.0, g, maxRelativeRange=0.05)
+                if used:
+                    solution = mask.astype(np.uint8)
+                    batch.upload_solution(ch, solution)
+                    r["selected_count"] = int(np.sum(solution))
+                    r["objective"] = R.objective_for_solution(scores, solution, g)
+                    r["penalized_objective"] = float(r["objective"]) - float(r["selection_penalty"]) * float(r["selected_count"])
+                    r["budget_fallback_window"] = True
+        r["starts"], r["ends"] = batch.rocco_runs(ch, max_gap_bins)
     return res

@@ -126,3 +126,57 @@ def csolveChromROCCOExact(scores, budget=None, gamma=0.5, selectionPenalty=None,
     sol, out = _solve_one(scoresArr, None, cfg)
     return (sol, float(out.objective), float(out.penalized_objective), int(out.selected_count),
             float(out.selection_penalty))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the wrapper `solveChromROCCO` puts around the native (peaks.py:1804-1835): host steps of the rare chain that selected nothing
+# ------------------------------------------------------------------------------------------------------------------
+def budget_target_count(n: int, budget) -> int | None:
+    """peaks.py:1806-1811: None when the budget is not finite."""
+    b = float(budget)
+    if not np.isfinite(b):
+        return None
+    return int(min(max(math.floor(int(n) * b), 0), int(n)))
+
+
+def best_contiguous_budget_fallback_mask(scores, targetCount, selectionPenalty, gamma, maxRelativeRange=None):
+    """peaks.py:3723-3760 `_bestContiguousBudgetFallbackMask` with the reference's NumPy steps: (mask, used)."""
+    scores_ = np.asarray(scores, dtype=np.float64)
+    n = int(scores_.size)
+    target = int(min(max(int(targetCount), 1), n))
+    out = np.zeros(n, dtype=bool)
+    if n == 0 or target <= 0:
+        return out, False
+    adjusted = scores_ - float(selectionPenalty)
+    cumsum = np.concatenate(([0.0], np.cumsum(adjusted, dtype=np.float64)))
+    # the reference's loop keeps the FIRST start of the largest objective (strict '>'): np.argmax of the same floats
+    window = cumsum[target:] - cumsum[: n - target + 1]
+    starts = np.arange(n - target + 1)
+    switches = (starts > 0).astype(np.float64) + (starts + target - 1 < n - 1).astype(np.float64)
+    objective = window - float(max(float(gamma), 0.0)) * switches
+    if np.any(np.isnan(objective)):
+        finite = np.where(np.isnan(objective), -np.inf, objective)       # (a NaN never wins a '>' comparison)
+    else:
+        finite = objective
+    bestStart = int(np.argmax(finite))
+    bestObjective = float(finite[bestStart])
+    if not np.isfinite(bestObjective) or bestObjective <= 0.0:
+        return out, False
+    if maxRelativeRange is not None:
+        bestWindow = scores_[bestStart: bestStart + target]
+        windowRange = float(np.max(bestWindow) - np.min(bestWindow))
+        windowScale = float(max(np.max(np.abs(bestWindow)), 1.0e-6))
+        if windowRange > float(max(float(maxRelativeRange), 0.0)) * windowScale:
+            return out, False
+    out[bestStart: bestStart + target] = True
+    return out, True
+
+
+def objective_for_solution(scores, solution, gamma) -> float:
+    """peaks.py:2017-2031 `_roccoObjectiveForSolution`."""
+    scores_ = np.asarray(scores, dtype=np.float64)
+    solution_ = np.asarray(solution, dtype=np.uint8)
+    objective = float(np.sum(scores_[solution_ > 0]))
+    if solution_.size > 1:
+        objective -= float(max(float(gamma), 0.0)) * float(np.sum(np.diff(solution_) != 0))
+    return objective

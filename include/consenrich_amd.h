@@ -675,6 +675,40 @@ int csr_batch_null_pooled_scale(csr_ctx *ctx, const unsigned char *chain_mask, d
 int csr_batch_dwb_panel_begin(csr_ctx *ctx, const int32_t *bandwidth, const char *kernel, const double *noise, int64_t noise_len,
                               int32_t n_draws, int32_t draws_per_group);
 
+/* ---- the effective sample size scan behind the ROCCO budget: pyx:9160-9279 `cEstimateEffectiveSampleSize` ----------------------
+ * (n_eff, tau, lags_used) equal the reference's bit for bit: the mean, the variance sum and the covariance sum of every lag are
+ * walked in index order on the device (separate multiply and add), the host composes rho, the break / taper rule and the clamps.
+ * Lags are scanned in rounds; a scan that broke asks for no further round.
+ * csr_ess_scan (default context): values = the series, already log-transformed by the caller when the reference's logPositive is
+ * set; general != 0, a mask or a window selects the reference's second path (finiteness check of the active values, pair counts,
+ * taper).  The reference's ValueErrors return CSR_ESS_ERR_VALUE with its text: "windowIntervals must be nonnegative" and "active
+ * values must be finite" before any launch; "variance estimate must be finite" and "autocorrelation estimate must be finite"
+ * depend on the sums.
+ * csr_batch_ess: the series of peaks.py:1414-1434 built on the device from the RESIDENT score tracks (kind 1: score > threshold
+ * as 0 / 1; 2: max((score - threshold) / max(scale, DBL_MIN), 0); 3: those of n_z (threshold, scale) pairs added in order, / n_z),
+ * scanned on the reference's fast path.  thresholds / scales: [chain][n_z] (n_z <= 16; kinds 1 and 2 read the first pair);
+ * max_lags[chain]; chain_mask: n_chains bytes or NULL = all; out: n_chains records, those of the other chains untouched.  No
+ * resident array changes. */
+enum { CSR_ESS_ERR_VALUE = 2 };
+enum { CSR_ESS_OCCUPANCY = 1, CSR_ESS_SOFT = 2, CSR_ESS_INTEGRATED = 3 };
+typedef struct csr_ess_out {
+    double n_eff, tau;
+    int64_t lags_used;
+} csr_ess_out;
+int csr_ess_scan(const double *values, int64_t n, int64_t max_lag, const unsigned char *active_mask, int32_t general,
+                 int64_t window_intervals, csr_ess_out *out);
+int csr_batch_ess(csr_ctx *ctx, int32_t kind, int32_t n_z, const double *thresholds, const double *scales, const int64_t *max_lags,
+                  const unsigned char *chain_mask, csr_ess_out *out);
+/* What `estimateROCCOGamma` (peaks.py:1741-1751) reads of a resident score track: count[chain] = how many scores have
+ * score - levels[chain] > 0, and mid[2 chain], mid[2 chain + 1] = the lower and upper middle SCORES of those (equal for an odd
+ * count, untouched for none) -- the caller subtracts the level and averages, as np.median does.  The tracks are sorted with the
+ * null's sort in work space; no resident array changes. */
+int csr_batch_rocco_excess_ranks(csr_ctx *ctx, const double *levels, const unsigned char *chain_mask, int64_t *count, double *mid);
+/* Plants the selection mask (bytes 0 / 1) of one chain, decided by the caller (the contiguous-window fallback of
+ * `solveChromROCCO`, peaks.py:1812-1835); csr_batch_rocco_download / csr_batch_rocco_runs then serve it.  Needs an earlier
+ * csr_batch_rocco of the batch. */
+int csr_batch_rocco_upload(csr_ctx *ctx, int32_t chain, const unsigned char *solution);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
