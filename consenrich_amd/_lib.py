@@ -166,11 +166,8 @@ class EssOut(C.Structure):
 
 ROCCO_FIXED_PENALTY, ROCCO_TARGET_COUNT = 0, 1
 ROCCO_SCORE_STATE, ROCCO_SCORE_LOWER_CONFIDENCE = 0, 1
-ROCCO_ERR_VALUE = 2
-DWB_ERR_VALUE = 2
-SEG_ERR_VALUE = 2
-NULL_ERR_VALUE = 2
-ESS_ERR_VALUE = 2
+ERR_VALUE = 2       # CSR_ERR_VALUE: what the reference answers with ValueError (check_value); the stages' own names are aliases
+ROCCO_ERR_VALUE = DWB_ERR_VALUE = SEG_ERR_VALUE = NULL_ERR_VALUE = ESS_ERR_VALUE = ERR_VALUE
 ESS_OCCUPANCY, ESS_SOFT, ESS_INTEGRATED = 1, 2, 3
 
 
@@ -350,6 +347,13 @@ def last_error() -> str:
 def check(rc: int) -> None:
     if rc != 0:
         raise ConsenrichAMDError(last_error() or f"consenrich_amd call failed (rc={rc})")
+
+
+def check_value(rc: int) -> None:
+    """check() of a peak-stage call: the reference's ValueErrors come back as ValueError with its text"""
+    if rc == ERR_VALUE:
+        raise ValueError(last_error())
+    check(rc)
 
 
 def device_count() -> int:

@@ -443,10 +443,8 @@ class DeviceBatch:
         modes = {"state": L.ROCCO_SCORE_STATE, "lower_confidence": L.ROCCO_SCORE_LOWER_CONFIDENCE}
         if mode not in modes:
             raise ValueError("`uncertaintyScoreMode` must be 'state' or 'lower_confidence'")
-        rc = self._lib.csr_batch_rocco_scores(self._ctx, modes[mode], float(z))
-        if rc == L.ROCCO_ERR_VALUE:        # what the reference answers with ValueError (negative variance, bad z)
-            raise ValueError(L.last_error())
-        L.check(rc)
+        # (a negative variance or a bad z comes back as the reference's ValueError)
+        L.check_value(self._lib.csr_batch_rocco_scores(self._ctx, modes[mode], float(z)))
 
     def upload_scores(self, chain: int, scores):
         s = np.ascontiguousarray(np.asarray(scores, dtype=np.float64).ravel())
@@ -551,7 +549,7 @@ class DeviceBatch:
         take, mask = self._chain_mask(chains)
         nc = len(take)
         out = (L.NullOut * nc)()
-        N._call(self._lib.csr_batch_null_prepare(self._ctx, float(bulk_quantile), mask, out))
+        L.check_value(self._lib.csr_batch_null_prepare(self._ctx, float(bulk_quantile), mask, out))
         res = [None] * nc
         for i in range(nc):
             if not take[i]:
@@ -580,11 +578,9 @@ class DeviceBatch:
     def null_pooled_scale(self, chains=None) -> float:
         """`_estimateTemplateScale` (peaks.py:543-556) of the selected chains' resident templates concatenated in chain order
         (the pooled null floor, peaks.py:950-951), on the device."""
-        from . import null as N
-
         _, mask = self._chain_mask(chains)
         out = np.empty(4, np.float64)
-        N._call(self._lib.csr_batch_null_pooled_scale(self._ctx, mask, L.dp(out)))
+        L.check_value(self._lib.csr_batch_null_pooled_scale(self._ctx, mask, L.dp(out)))
         return float(out[0])
 
     def _resident_null(self, null_centers, null_scales):
@@ -617,8 +613,8 @@ class DeviceBatch:
                 nz = len(thresholds)
                 off, sc = np.asarray(thresholds, np.float64), np.asarray(scales, np.float64)
                 cnt, soft = np.zeros(nz, np.int64), np.zeros(nz, np.float64)
-                W._call(batch._lib.csr_batch_dwb_observed(batch._ctx, int(c), nz, L.dp(off), L.dp(sc),
-                                                          cnt.ctypes.data_as(L.I64P), L.dp(soft)))
+                L.check_value(batch._lib.csr_batch_dwb_observed(batch._ctx, int(c), nz, L.dp(off), L.dp(sc),
+                                                                cnt.ctypes.data_as(L.I64P), L.dp(soft)))
                 return cnt, soft
 
         return W._run_panel(self._ctx, _Resident(), list(self.chain_lens), templates, null_centers, null_scales,
@@ -655,8 +651,8 @@ class DeviceBatch:
             raise ValueError("one maxLag per chain")
         t_all, s_all = np.ascontiguousarray(np.stack(thr)), np.ascontiguousarray(np.stack(sc))
         out = (L.EssOut * nc)()
-        E._call(self._lib.csr_batch_ess(self._ctx, E.KINDS[kind], nz, L.dp(t_all), L.dp(s_all), lags.ctypes.data_as(L.I64P), mask,
-                                        out))
+        L.check_value(self._lib.csr_batch_ess(self._ctx, E.KINDS[kind], nz, L.dp(t_all), L.dp(s_all), lags.ctypes.data_as(L.I64P), mask,
+                                              out))
         return [(float(out[i].n_eff), float(out[i].tau), int(out[i].lags_used)) if take[i] else None for i in range(nc)]
 
     def rocco_budget(self, panel, *, statistic="occupancy", threshold_z, threshold_z_grid, dependence_spans, budget_min=None,
@@ -744,9 +740,9 @@ class DeviceBatch:
         nc = len(self.chain_lens)
         rows, counters, flagged = np.zeros(nc, np.int64), np.zeros(3 * nc, np.int64), C.c_int32(0)
         cap = 0 if view_cap is None else view_cap
-        S._call(self._lib.csr_batch_segments_run(self._ctx, n_s.ctypes.data_as(L.I32P), sc_all.ctypes.data_as(L.I64P),
-                                                 n_v.ctypes.data_as(L.I32P), L.dp(thr_all), L.dp(ns_all), min_run, gap, cap,
-                                                 rows.ctypes.data_as(L.I64P), counters.ctypes.data_as(L.I64P), C.byref(flagged)))
+        L.check_value(self._lib.csr_batch_segments_run(self._ctx, n_s.ctypes.data_as(L.I32P), sc_all.ctypes.data_as(L.I64P),
+                                                       n_v.ctypes.data_as(L.I32P), L.dp(thr_all), L.dp(ns_all), min_run, gap, cap,
+                                                       rows.ctypes.data_as(L.I64P), counters.ctypes.data_as(L.I64P), C.byref(flagged)))
         tracks = S.collect(self._ctx, rows, counters, flagged.value, cap)
         return [S.compose(tracks[c], views[c], total_cap, view_cap) for c in range(nc)]
 

@@ -8,15 +8,7 @@
 
 static void seg_release(csr_ctx *c);     // csr_host_segments.inl
 
-static int dwb_value_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return CSR_DWB_ERR_VALUE;
-}
-
-// pyx:9283-9291: 0 bartlett, 1 parzen, 2 quadratic spectral; CSR_DWB_ERR_VALUE for anything else
+// pyx:9283-9291: 0 bartlett, 1 parzen, 2 quadratic spectral; CSR_ERR_VALUE for anything else
 static int dwb_kernel_code(const char *kernel, int *code) {
     std::string s(kernel ? kernel : "");
     const char *ws = " \t\n\r\f\v";
@@ -26,7 +18,7 @@ static int dwb_kernel_code(const char *kernel, int *code) {
     if (name == "bartlett" || name == "triangle" || name == "triangular") *code = 0;
     else if (name == "parzen") *code = 1;
     else if (name == "qs" || name == "quadratic_spectral" || name == "quadraticspectral") *code = 2;
-    else return dwb_value_error("Unknown DWB kernel: %s", kernel ? kernel : "");
+    else return value_error("Unknown DWB kernel: %s", kernel ? kernel : "");
     return 0;
 }
 static int dwb_max_lag(int bandwidth, int code) {       // pyx:9294-9302
@@ -181,9 +173,8 @@ extern "C" int csr_dwb_max_lag(int32_t bandwidth, const char *kernel, int32_t *m
 static int dwb_native(const double *noise, int64_t noise_len, const double *mult, const double *tmpl, int64_t n, int32_t bandwidth,
                       int code, double *out) {
     DEFAULT_CTX_GUARD;
-    csr_ctx *c = default_ctx();
-    if (!c) return -1;
-    CHECK(ctx_select(c));
+    csr_ctx *c = nullptr;
+    CHECK(ctx_or_default(c));
     csr_ctx::Dwb &d = c->dwb;
     CHECK(dwb_setup(c, 1, &n, &bandwidth, code));
     CHECK(d.rowBuf.reserve(8 * (size_t)d.rowLen));
@@ -208,13 +199,13 @@ extern "C" int csr_dwb_multipliers(const double *noise, int64_t noise_len, int32
     CHECK(dwb_kernel_code(kernel, &code));
     const int bw = bandwidth >= 2 ? bandwidth : 2;
     const int64_t n = noise_len - 2 * (int64_t)dwb_max_lag(bw, code);
-    if (n <= 0) return dwb_value_error("noise length is too short for the requested DWB bandwidth");
+    if (n <= 0) return value_error("noise length is too short for the requested DWB bandwidth");
     if (!noise || !out) return fail("null argument");
     return dwb_native(noise, noise_len, nullptr, nullptr, n, bw, code, out);
 }
 
 extern "C" int csr_dwb_apply(const double *tmpl, int64_t n, const double *multipliers, int64_t n_multipliers, double *out) {
-    if (n_multipliers != n) return dwb_value_error("template and multipliers must have the same length");
+    if (n_multipliers != n) return value_error("template and multipliers must have the same length");
     if (n < 0) return fail("negative length");
     if (n == 0) return 0;
     if (!tmpl || !multipliers || !out) return fail("null argument");
@@ -228,8 +219,8 @@ extern "C" int csr_dwb_draw(const double *tmpl, int64_t n, int32_t bandwidth, co
     const int bw = bandwidth >= 2 ? bandwidth : 2;
     if (n < 0) return fail("negative length");
     if (n <= 0 || noise_len < n + 2 * (int64_t)dwb_max_lag(bw, code))
-        return dwb_value_error("noise length is too short for the requested DWB bandwidth");
-    if (noise_len != n + 2 * (int64_t)dwb_max_lag(bw, code)) return dwb_value_error("template and multipliers must have the same length");
+        return value_error("noise length is too short for the requested DWB bandwidth");
+    if (noise_len != n + 2 * (int64_t)dwb_max_lag(bw, code)) return value_error("template and multipliers must have the same length");
     if (!tmpl || !noise || !out) return fail("null argument");
     return dwb_native(noise, noise_len, nullptr, tmpl, n, bw, code, out);
 }
@@ -237,12 +228,6 @@ extern "C" int csr_dwb_draw(const double *tmpl, int64_t n, int32_t bandwidth, co
 // ---------------------------------------------------------------------------------------------------------------
 // the panel: begin (upload once per seed) -> order statistics (phase A) -> tail statistics (phase B) -> end
 // ---------------------------------------------------------------------------------------------------------------
-static int dwb_ctx(csr_ctx *&c) {
-    if (!c) c = default_ctx();
-    if (!c) return -1;
-    return ctx_select(c);
-}
-
 // templates[i]: chain i's template, on the host or on the device as `kind` says
 static int dwb_panel_begin(csr_ctx *c, int32_t n_chains, const int64_t *chain_len, const int32_t *bandwidth, const char *kernel,
                            const double *const *templates, hipMemcpyKind kind, const double *noise, int64_t noise_len, int32_t n_draws,
@@ -258,8 +243,8 @@ static int dwb_panel_begin(csr_ctx *c, int32_t n_chains, const int64_t *chain_le
         if (chain_len[i] <= 0) return fail("chain %d is empty", i);
         strideMax = std::max(strideMax, chain_len[i] + 2 * (int64_t)dwb_max_lag(bandwidth[i], code));
     }
-    if (noise_len < (int64_t)n_draws * strideMax) return dwb_value_error("noise length is too short for the requested DWB bandwidth");
-    CHECK(dwb_ctx(c));
+    if (noise_len < (int64_t)n_draws * strideMax) return value_error("noise length is too short for the requested DWB bandwidth");
+    CHECK(ctx_or_default(c));
     csr_ctx::Dwb &d = c->dwb;
     CHECK(dwb_setup(c, n_chains, chain_len, bandwidth, code));
     // default group: as many draws as fit 16 GiB of rows (chr1 x 128 draws: 1.3 GB; the 22 autosomes x 128: 14.7 GB, one group each)
@@ -300,7 +285,7 @@ extern "C" int csr_dwb_panel_order_stats(csr_ctx *c, int32_t n_ranks, const int6
     DEFAULT_CTX_GUARD;
     if (n_ranks <= 0 || n_ranks > DWB_MAX_RANKS) return fail("n_ranks must be in 1..%d", DWB_MAX_RANKS);
     if (!ranks || !out) return fail("null argument");
-    CHECK(dwb_ctx(c));
+    CHECK(ctx_or_default(c));
     csr_ctx::Dwb &d = c->dwb;
     if (!d.ready) return fail("no DWB panel: call csr_dwb_panel_begin first");
     const int nc = (int)d.chains.size();
@@ -329,7 +314,7 @@ extern "C" int csr_dwb_panel_tail_stats(csr_ctx *c, int32_t n_z, const double *o
                                         double *soft) {
     DEFAULT_CTX_GUARD;
     CHECK(dwb_check_z(n_z, offsets, scales, counts, soft));
-    CHECK(dwb_ctx(c));
+    CHECK(ctx_or_default(c));
     csr_ctx::Dwb &d = c->dwb;
     if (!d.ready) return fail("no DWB panel: call csr_dwb_panel_begin first");
     const int nc = (int)d.chains.size();
@@ -356,7 +341,7 @@ extern "C" int csr_dwb_panel_tail_stats(csr_ctx *c, int32_t n_z, const double *o
 
 extern "C" int csr_dwb_panel_end(csr_ctx *c) {
     DEFAULT_CTX_GUARD;
-    CHECK(dwb_ctx(c));
+    CHECK(ctx_or_default(c));
     csr_ctx::Dwb &d = c->dwb;
     d.ready = false;
     HIPOK(hipStreamSynchronize(c->stream));
@@ -397,11 +382,10 @@ extern "C" int csr_dwb_tail_stats(csr_ctx *c, const double *x, int64_t n, int32_
     DEFAULT_CTX_GUARD;
     CHECK(dwb_check_z(n_z, offsets, scales, counts, soft));
     if (!x || n <= 0) return fail("null or empty vector");
-    CHECK(dwb_ctx(c));
-    csr_ctx::Dwb &d = c->dwb;
-    CHECK(d.xBuf.reserve(8 * (size_t)n));
-    HIPOK(hipMemcpyAsync(d.xBuf.ptr, x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    return dwb_vector_tail(c, (const double *)d.xBuf.ptr, n, n_z, offsets, scales, counts, soft);
+    CHECK(ctx_or_default(c));
+    const double *dx = nullptr;
+    CHECK(stage_vector(c, c->dwb.xBuf, x, n, &dx));
+    return dwb_vector_tail(c, dx, n, n_z, offsets, scales, counts, soft);
 }
 
 // reads the chain's resident score track (csr_batch_rocco_scores / csr_batch_upload_scores); changes nothing resident
@@ -409,8 +393,7 @@ extern "C" int csr_batch_dwb_observed(csr_ctx *c, int32_t chain, int32_t n_z, co
                                       int64_t *counts, double *soft) {
     CHECK(need(c));
     CHECK(dwb_check_z(n_z, offsets, scales, counts, soft));
-    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
-    if (!c->rocco.scores || !c->rocco.haveScores[chain]) return fail("chain %d has no scores", chain);
-    const ChainInfo &ci = c->chains[chain];
-    return dwb_vector_tail(c, c->rocco.scores + ci.off, ci.n, n_z, offsets, scales, counts, soft);
+    CHECK(check_chain(c, chain));
+    if (!c->scores.has(chain)) return fail("chain %d has no scores", chain);
+    return dwb_vector_tail(c, c->scores.at(c, chain), c->chains[chain].n, n_z, offsets, scales, counts, soft);
 }

@@ -7,11 +7,6 @@
 // the number of lags in it, so when every scan of the call ends within 512 lags the first round holds them all (maxLag = 256, four
 // dependence spans of 64, would otherwise pay a second walk for its last lag).
 
-static int ess_value_error(const char *msg) {
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return CSR_ESS_ERR_VALUE;
-}
-
 constexpr int64_t ESS_ROUND_FIRST = 256, ESS_ROUND_WHOLE = 512, ESS_ROUND_MAX = 4096;
 
 struct EssSpec {
@@ -209,31 +204,28 @@ extern "C" int csr_ess_scan(const double *values, int64_t n, int64_t max_lag, co
                             int64_t window_intervals, csr_ess_out *out) {
     DEFAULT_CTX_GUARD;
     if (!out || (n > 0 && !values) || n < 0) return fail("null argument");
-    if (window_intervals < 0) return ess_value_error("windowIntervals must be nonnegative");
+    if (window_intervals < 0) return value_error("windowIntervals must be nonnegative");
     const bool gen = general != 0 || active_mask != nullptr || window_intervals != 0;
     int64_t active = 0;
     if (gen)
         for (int64_t i = 0; i < n; ++i) {
             if (active_mask && active_mask[i] == 0) continue;
-            if (!std::isfinite(values[i])) return ess_value_error("active values must be finite");
+            if (!std::isfinite(values[i])) return value_error("active values must be finite");
             ++active;
         }
     if ((gen ? active : n) < 2) {
         *out = csr_ess_out{(double)(gen ? active : n), 1.0, 0};
         return 0;
     }
-    csr_ctx *c = default_ctx();
-    if (!c) return -1;
-    CHECK(ctx_select(c));
+    csr_ctx *c = nullptr;
+    CHECK(ctx_or_default(c));
     csr_ctx::EssWs &ws = c->essWs;
-    CHECK(ws.xBuf.reserve(8 * (size_t)n));
-    HIPOK(hipMemcpyAsync(ws.xBuf.ptr, values, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    EssSpec sp;
+    CHECK(stage_vector(c, ws.xBuf, values, n, &sp.src));
     if (active_mask) {
         CHECK(ws.maskBuf.reserve((size_t)n));
         HIPOK(hipMemcpyAsync(ws.maskBuf.ptr, active_mask, (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
-    EssSpec sp;
-    sp.src = (const double *)ws.xBuf.ptr;
     sp.mask = active_mask ? (const unsigned char *)ws.maskBuf.ptr : nullptr;
     sp.n = n;
     sp.maxLag = max_lag;
@@ -242,8 +234,8 @@ extern "C" int csr_ess_scan(const double *values, int64_t n, int64_t max_lag, co
     sp.active = active;
     std::vector<int> status;
     CHECK(ess_run(c, {sp}, out, status));
-    if (status[0] == 1) return ess_value_error("variance estimate must be finite");
-    if (status[0] == 2) return ess_value_error("autocorrelation estimate must be finite");
+    if (status[0] == 1) return value_error("variance estimate must be finite");
+    if (status[0] == 2) return value_error("autocorrelation estimate must be finite");
     return 0;
 }
 
@@ -257,18 +249,14 @@ extern "C" int csr_batch_rocco_excess_ranks(csr_ctx *c, const double *levels, co
                                             double *mid) {
     CHECK(need(c));
     if (!levels || !count || !mid) return fail("null argument");
-    const int nc = (int)c->chains.size();
-    if (!c->rocco.scores) return fail("no scores: call csr_batch_rocco_scores or csr_batch_upload_scores first");
-    std::vector<NullTrackHost> tracks;
     std::vector<int> idx;
-    for (int i = 0; i < nc; ++i) {
-        if (chain_mask && !chain_mask[i]) continue;
-        if (!c->rocco.haveScores[i]) return fail("chain %d has no scores", i);
+    const int missing = select_chains(c, chain_mask, c->scores, idx, NO_SCORES);
+    std::vector<NullTrackHost> tracks;
+    for (int i : idx) {         // (the chains in front of one without scores still answer for their own level first)
         if (!std::isfinite(levels[i])) return fail("chain %d: the reference level must be finite", i);
-        const ChainInfo &ci = c->chains[i];
-        tracks.push_back(NullTrackHost{c->rocco.scores + ci.off, ci.n, nullptr, false, 0.0, 0.0});
-        idx.push_back(i);
+        tracks.push_back(NullTrackHost{c->scores.at(c, i), c->chains[i].n, nullptr, false, 0.0, 0.0});
     }
+    CHECK(missing);
     if (tracks.empty()) return 0;
     NullEngine E;
     E.c = c;
@@ -302,17 +290,11 @@ extern "C" int csr_batch_rocco_excess_ranks(csr_ctx *c, const double *levels, co
 // the mask of one chain as the caller decided it (the contiguous-window fallback of `solveChromROCCO`, peaks.py:1812-1835): from
 // then on csr_batch_rocco_download / csr_batch_rocco_runs serve it like a mask the solver left
 extern "C" int csr_batch_rocco_upload(csr_ctx *c, int32_t chain, const unsigned char *solution) {
-    CHECK(need(c));
-    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
-    if (!solution) return fail("null host buffer");
-    if (!c->rocco.sol) return fail("no ROCCO solution buffers: call csr_batch_rocco first");
-    const ChainInfo &ci = c->chains[chain];
-    for (int64_t i = 0; i < ci.n; ++i)
+    CHECK(need_chain(c, chain, solution));
+    if (!c->sol.d) return fail("no ROCCO solution buffers: call csr_batch_rocco first");
+    for (int64_t i = 0; i < c->chains[chain].n; ++i)
         if (solution[i] > 1) return fail("a selection mask holds 0 and 1 only");
-    HIPOK(hipMemcpyAsync(c->rocco.sol + ci.off, solution, (size_t)ci.n, hipMemcpyHostToDevice, c->stream));
-    HIPOK(hipStreamSynchronize(c->stream));
-    c->rocco.haveSol[chain] = 1;
-    return 0;
+    return c->sol.upload(c, chain, solution);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -325,18 +307,13 @@ extern "C" int csr_batch_ess(csr_ctx *c, int32_t kind, int32_t n_z, const double
     if (!thresholds || !scales || !max_lags || !out) return fail("null argument");
     if (kind != ESS_SERIES_OCCUPANCY && kind != ESS_SERIES_SOFT && kind != ESS_SERIES_INTEGRATED) return fail("bad series kind %d", kind);
     if (n_z < 1 || n_z > ESS_MAX_Z) return fail("n_z must be in [1, %d]", ESS_MAX_Z);
-    const int nc = (int)c->chains.size();
-    if (!c->rocco.scores) return fail("no scores: call csr_batch_rocco_scores or csr_batch_upload_scores first");
-    for (int i = 0; i < nc; ++i)
-        if ((!chain_mask || chain_mask[i]) && !c->rocco.haveScores[i]) return fail("chain %d has no scores", i);
-    std::vector<EssSpec> specs;
     std::vector<int> idx;
-    for (int i = 0; i < nc; ++i) {
-        if (chain_mask && !chain_mask[i]) continue;
-        const ChainInfo &ci = c->chains[i];
+    CHECK(select_chains(c, chain_mask, c->scores, idx, NO_SCORES));
+    std::vector<EssSpec> specs;
+    for (int i : idx) {
         EssSpec sp;
-        sp.src = c->rocco.scores + ci.off;
-        sp.n = ci.n;
+        sp.src = c->scores.at(c, i);
+        sp.n = c->chains[i].n;
         sp.kind = kind;
         sp.nz = n_z;
         for (int k = 0; k < n_z; ++k) {
@@ -345,12 +322,11 @@ extern "C" int csr_batch_ess(csr_ctx *c, int32_t kind, int32_t n_z, const double
         }
         sp.maxLag = max_lags[i];
         specs.push_back(sp);
-        idx.push_back(i);
     }
     if (specs.empty()) return 0;
     std::vector<csr_ess_out> res(specs.size());
     std::vector<int> status;
     CHECK(ess_run(c, specs, res.data(), status));
-    for (size_t k = 0; k < idx.size(); ++k) out[idx[k]] = res[k];
+    scatter_chains(idx, res.data(), out);
     return 0;
 }

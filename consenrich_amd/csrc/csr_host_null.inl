@@ -5,11 +5,6 @@
 // call.  A track whose central support falls short of minSupport is not decided here: the reference then orders the track by an
 // unstable argsort, so the caller decides it with NumPy (csr_null_out::host_fallback).
 
-static int null_value_error(const char *msg) {
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return CSR_NULL_ERR_VALUE;
-}
-
 // np.quantile(.., method="interpolated_inverted_cdf") on n sorted values = lerp(v[lo], v[hi], g)
 static void null_qranks(int64_t n, double q, int64_t &lo, int64_t &hi, double &g) {
     const double v = (double)n * q - 1.0, fl = std::floor(v);
@@ -549,16 +544,9 @@ static int null_scale_device(csr_ctx *c, const double *dx, int64_t n, double *ou
 }
 
 static int null_check_vector(const char *name, const double *x, int64_t n) {
-    char msg[128];
-    if (n <= 0) {
-        snprintf(msg, sizeof(msg), "`%s` must be non-empty", name);
-        return null_value_error(msg);
-    }
+    if (n <= 0) return value_error("`%s` must be non-empty", name);
     for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(x[i])) {
-            snprintf(msg, sizeof(msg), "`%s` contains non-finite values", name);
-            return null_value_error(msg);
-        }
+        if (!std::isfinite(x[i])) return value_error("`%s` contains non-finite values", name);
     return 0;
 }
 
@@ -570,12 +558,12 @@ extern "C" int csr_null_prepare(const double *scores, int64_t n, double bulk_qua
     DEFAULT_CTX_GUARD;
     if (!scores || !out) return fail("null argument");
     CHECK(null_check_vector("scoreTrack", scores, n));
-    csr_ctx *c = default_ctx();
-    if (!c) return -1;
-    CHECK(ctx_select(c));
-    CHECK(c->nullWs.xBuf.reserve(16 * (size_t)n));
-    double *dx = (double *)c->nullWs.xBuf.ptr, *dt = dx + n;
-    HIPOK(hipMemcpyAsync(dx, scores, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    csr_ctx *c = nullptr;
+    CHECK(ctx_or_default(c));
+    const double *dx = nullptr;
+    CHECK(c->nullWs.xBuf.reserve(16 * (size_t)n));      // the track, then its template
+    CHECK(stage_vector(c, c->nullWs.xBuf, scores, n, &dx));
+    double *dt = (double *)c->nullWs.xBuf.ptr + n;
     std::vector<NullTrackHost> tracks{NullTrackHost{dx, n, dt, given != nullptr, given ? given[0] : 0.0, given ? given[1] : 0.0}};
     CHECK(null_prepare_tracks(c, tracks, bulk_quantile, out));
     if (template_out && !out->host_fallback) {
@@ -589,12 +577,11 @@ extern "C" int csr_null_scale(const double *x, int64_t n, double *out) {
     DEFAULT_CTX_GUARD;
     if (!x || !out) return fail("null argument");
     CHECK(null_check_vector("template", x, n));
-    csr_ctx *c = default_ctx();
-    if (!c) return -1;
-    CHECK(ctx_select(c));
-    CHECK(c->nullWs.xBuf.reserve(8 * (size_t)n));
-    HIPOK(hipMemcpyAsync(c->nullWs.xBuf.ptr, x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    return null_scale_device(c, (const double *)c->nullWs.xBuf.ptr, n, out);
+    csr_ctx *c = nullptr;
+    CHECK(ctx_or_default(c));
+    const double *dx = nullptr;
+    CHECK(stage_vector(c, c->nullWs.xBuf, x, n, &dx));
+    return null_scale_device(c, dx, n, out);
 }
 
 // the device's ascending sort of one host vector (what every order statistic above is read from)
@@ -602,14 +589,13 @@ extern "C" int csr_null_sort(const double *x, int64_t n, double *out) {
     DEFAULT_CTX_GUARD;
     if (!x || !out) return fail("null argument");
     CHECK(null_check_vector("values", x, n));
-    csr_ctx *c = default_ctx();
-    if (!c) return -1;
-    CHECK(ctx_select(c));
-    CHECK(c->nullWs.xBuf.reserve(8 * (size_t)n));
-    HIPOK(hipMemcpyAsync(c->nullWs.xBuf.ptr, x, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    csr_ctx *c = nullptr;
+    CHECK(ctx_or_default(c));
+    const double *dx = nullptr;
+    CHECK(stage_vector(c, c->nullWs.xBuf, x, n, &dx));
     NullEngine E;
     E.c = c;
-    CHECK(E.setup({NullTrackHost{(const double *)c->nullWs.xBuf.ptr, n, nullptr, false, 0.0, 0.0}}, false));
+    CHECK(E.setup({NullTrackHost{dx, n, nullptr, false, 0.0, 0.0}}, false));
     CHECK(E.sort());
     HIPOK(hipMemcpyAsync(out, E.sorted, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
@@ -620,65 +606,32 @@ extern "C" int csr_null_sort(const double *x, int64_t n, double *out) {
 // batch context: the resident score tracks in, one resident template per chain out (a buffer of its own, allocated at first use,
 // freed with the batch); neither the scores nor any array of the fit changes
 // ---------------------------------------------------------------------------------------------------------------
-static int null_batch_buffers(csr_ctx *c) {
-    csr_ctx::NullRes &r = c->nullRes;
-    if (r.tmpl) return 0;
-    CHECK(dalloc(c, &r.tmpl, c->Npad + 64));
-    HIPOK(hipMemsetAsync(r.tmpl, 0, 8 * (size_t)(c->Npad + 64), c->stream));
-    r.have.assign(c->chains.size(), 0);
-    return 0;
-}
-
 extern "C" int csr_batch_null_prepare(csr_ctx *c, double bulk_quantile, const unsigned char *chain_mask, csr_null_out *out) {
     CHECK(need(c));
     if (!out) return fail("null argument");
-    const int nc = (int)c->chains.size();
-    if (!c->rocco.scores) return fail("no scores: call csr_batch_rocco_scores or csr_batch_upload_scores first");
-    for (int i = 0; i < nc; ++i)
-        if ((!chain_mask || chain_mask[i]) && !c->rocco.haveScores[i]) return fail("chain %d has no scores", i);
-    CHECK(null_batch_buffers(c));
-    std::vector<NullTrackHost> tracks;
     std::vector<int> idx;
-    for (int i = 0; i < nc; ++i) {
-        if (chain_mask && !chain_mask[i]) continue;
-        const ChainInfo &ci = c->chains[i];
-        tracks.push_back(NullTrackHost{c->rocco.scores + ci.off, ci.n, c->nullRes.tmpl + ci.off, false, 0.0, 0.0});
-        idx.push_back(i);
-    }
+    CHECK(select_chains(c, chain_mask, c->scores, idx, NO_SCORES));
+    CHECK(c->tmpl.ensure(c));
+    std::vector<NullTrackHost> tracks;
+    for (int i : idx) tracks.push_back(NullTrackHost{c->scores.at(c, i), c->chains[i].n, c->tmpl.at(c, i), false, 0.0, 0.0});
     if (tracks.empty()) return 0;
     std::vector<csr_null_out> res(tracks.size());
-    for (int i : idx) c->nullRes.have[i] = 0;
+    for (int i : idx) c->tmpl.set(i, false);
     CHECK(null_prepare_tracks(c, tracks, bulk_quantile, res.data()));
-    for (size_t k = 0; k < idx.size(); ++k) {
-        out[idx[k]] = res[k];
-        c->nullRes.have[idx[k]] = res[k].host_fallback ? 0 : 1;
-    }
+    scatter_chains(idx, res.data(), out);
+    for (int i : idx) c->tmpl.set(i, !out[i].host_fallback);
     return 0;
 }
 
 extern "C" int csr_batch_null_template_download(csr_ctx *c, int32_t chain, double *host_dst) {
-    CHECK(need(c));
-    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
-    if (!host_dst) return fail("null host buffer");
-    if (!c->nullRes.tmpl || !c->nullRes.have[chain]) return fail("chain %d has no null template", chain);
-    const ChainInfo &ci = c->chains[chain];
-    HIPOK(hipMemcpyAsync(host_dst, c->nullRes.tmpl + ci.off, 8 * (size_t)ci.n, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(hipStreamSynchronize(c->stream));
-    return 0;
+    CHECK(need_chain(c, chain, host_dst));
+    return c->tmpl.download(c, chain, host_dst);
 }
 
 extern "C" int csr_batch_null_template_upload(csr_ctx *c, int32_t chain, const double *tmpl) {
-    CHECK(need(c));
-    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
-    if (!tmpl) return fail("null host buffer");
-    const ChainInfo &ci = c->chains[chain];
-    for (int64_t i = 0; i < ci.n; ++i)
-        if (!std::isfinite(tmpl[i])) return fail("`template` contains non-finite values");
-    CHECK(null_batch_buffers(c));
-    HIPOK(hipMemcpyAsync(c->nullRes.tmpl + ci.off, tmpl, 8 * (size_t)ci.n, hipMemcpyHostToDevice, c->stream));
-    HIPOK(hipStreamSynchronize(c->stream));
-    c->nullRes.have[chain] = 1;
-    return 0;
+    CHECK(need_chain(c, chain, tmpl));
+    CHECK(check_finite("template", tmpl, c->chains[chain].n));
+    return c->tmpl.upload(c, chain, tmpl);
 }
 
 // `_estimateTemplateScale` of the selected chains' resident templates, concatenated in chain order (unpadded: NumPy's chunks of
@@ -686,22 +639,18 @@ extern "C" int csr_batch_null_template_upload(csr_ctx *c, int32_t chain, const d
 extern "C" int csr_batch_null_pooled_scale(csr_ctx *c, const unsigned char *chain_mask, double *out) {
     CHECK(need(c));
     if (!out) return fail("null argument");
-    const int nc = (int)c->chains.size();
+    std::vector<int> idx;
+    CHECK(select_chains(c, chain_mask, c->tmpl, idx));
     int64_t total = 0;
-    for (int i = 0; i < nc; ++i) {
-        if (chain_mask && !chain_mask[i]) continue;
-        if (!c->nullRes.tmpl || !c->nullRes.have[i]) return fail("chain %d has no null template", i);
-        total += c->chains[i].n;
-    }
-    if (total <= 0) return null_value_error("`template` must be non-empty");
+    for (int i : idx) total += c->chains[i].n;
+    if (total <= 0) return value_error("`template` must be non-empty");
     CHECK(c->nullWs.xBuf.reserve(8 * (size_t)total));
     double *dx = (double *)c->nullWs.xBuf.ptr;
     int64_t at = 0;
-    for (int i = 0; i < nc; ++i) {
-        if (chain_mask && !chain_mask[i]) continue;
-        const ChainInfo &ci = c->chains[i];
-        HIPOK(hipMemcpyAsync(dx + at, c->nullRes.tmpl + ci.off, 8 * (size_t)ci.n, hipMemcpyDeviceToDevice, c->stream));
-        at += ci.n;
+    for (int i : idx) {
+        const int64_t n = c->chains[i].n;
+        HIPOK(hipMemcpyAsync(dx + at, c->tmpl.at(c, i), 8 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+        at += n;
     }
     return null_scale_device(c, dx, total, out);
 }
@@ -711,14 +660,14 @@ extern "C" int csr_batch_null_pooled_scale(csr_ctx *c, const unsigned char *chai
 extern "C" int csr_batch_dwb_panel_begin(csr_ctx *c, const int32_t *bandwidth, const char *kernel, const double *noise, int64_t noise_len,
                                          int32_t n_draws, int32_t draws_per_group) {
     CHECK(need(c));
-    const int nc = (int)c->chains.size();
-    std::vector<int64_t> len((size_t)nc);
-    std::vector<const double *> tp((size_t)nc);
-    for (int i = 0; i < nc; ++i) {
-        if (!c->nullRes.tmpl || !c->nullRes.have[i]) return fail("chain %d has no null template", i);
-        len[i] = c->chains[i].n;
-        tp[i] = c->nullRes.tmpl + c->chains[i].off;
+    std::vector<int> idx;
+    CHECK(select_chains(c, nullptr, c->tmpl, idx));
+    std::vector<int64_t> len;
+    std::vector<const double *> tp;
+    for (int i : idx) {
+        len.push_back(c->chains[i].n);
+        tp.push_back(c->tmpl.at(c, i));
     }
-    return dwb_panel_begin(c, nc, len.data(), bandwidth, kernel, tp.data(), hipMemcpyDeviceToDevice, noise, noise_len, n_draws,
+    return dwb_panel_begin(c, (int)idx.size(), len.data(), bandwidth, kernel, tp.data(), hipMemcpyDeviceToDevice, noise, noise_len, n_draws,
                            draws_per_group);
 }

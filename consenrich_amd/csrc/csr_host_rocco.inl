@@ -254,9 +254,8 @@ extern "C" int csr_rocco_solve(int32_t n_chains, const int64_t *chain_len, const
                                const csr_rocco_cfg *cfg, csr_rocco_out *out, uint8_t *solution) {
     DEFAULT_CTX_GUARD;
     if (n_chains <= 0 || !chain_len || !scores || !cfg || !out) return fail("null or empty argument");
-    csr_ctx *c = default_ctx();
-    if (!c) return -1;
-    CHECK(ctx_select(c));
+    csr_ctx *c = nullptr;
+    CHECK(ctx_or_default(c));
     int64_t tot = 0, pad = 0;
     std::vector<RoccoChainIn> chains((size_t)n_chains);
     for (int i = 0; i < n_chains; ++i) {
@@ -267,8 +266,7 @@ extern "C" int csr_rocco_solve(int32_t n_chains, const int64_t *chain_len, const
         pad += (chain_len[i] + 63) / 64 * 64;
     }
     if (pad >= (int64_t)1 << 31) return fail("too many bins: %lld (limit 2^31)", (long long)pad);
-    for (int64_t i = 0; i < tot; ++i)
-        if (!std::isfinite(scores[i])) return fail("`scores` contains non-finite values");
+    CHECK(check_finite("scores", scores, tot));
     // device arena: scores | costs | mask | backtrace words
     const size_t oS = 0, oC = oS + 8 * (size_t)pad, oSol = oC + (switch_costs ? 8 * (size_t)pad : 0), oBt = oSol + (size_t)pad,
                  total = oBt + (size_t)pad / 4 + 64;
@@ -282,8 +280,7 @@ extern "C" int csr_rocco_solve(int32_t n_chains, const int64_t *chain_len, const
         HIPOK(hipMemcpyAsync(base + oS + 8 * ch.off, scores + so, 8 * (size_t)ch.n, hipMemcpyHostToDevice, c->stream));
         if (switch_costs) {
             ch.hostCosts = switch_costs + co;
-            for (int64_t k = 0; k + 1 < ch.n; ++k)
-                if (!std::isfinite(ch.hostCosts[k])) return fail("`switchCosts` contains non-finite values");
+            CHECK(check_finite("switchCosts", ch.hostCosts, ch.n - 1));
             if (ch.n > 1)
                 HIPOK(hipMemcpyAsync(base + oC + 8 * ch.off, ch.hostCosts, 8 * (size_t)(ch.n - 1), hipMemcpyHostToDevice, c->stream));
             co += ch.n - 1;
@@ -308,34 +305,24 @@ extern "C" int csr_rocco_solve(int32_t n_chains, const int64_t *chain_len, const
 // batch context: scores, masks and work space of their own (allocated at first use, freed with the batch); the resident
 // arrays of the fit and the record of its last pass are only read
 // ---------------------------------------------------------------------------------------------------------------
-static int rocco_batch_buffers(csr_ctx *c) {
+static int rocco_buffers(csr_ctx *c) {
+    CHECK(c->scores.ensure(c));
+    CHECK(c->sol.ensure(c));
     csr_ctx::Rocco &r = c->rocco;
-    if (r.scores) return 0;
-    const size_t nc = c->chains.size();
-    CHECK(dalloc(c, &r.scores, c->Npad + 64));
-    CHECK(dalloc(c, &r.sol, c->Npad + 64));
+    if (r.bt) return 0;
+    const int64_t nc = (int64_t)c->chains.size();
     CHECK(dalloc(c, &r.bt, c->Npad / 32 + 64));
-    CHECK(dalloc(c, &r.mx, (int64_t)nc));
-    CHECK(dalloc(c, &r.bad, (int64_t)nc));
-    HIPOK(hipMemsetAsync(r.scores, 0, 8 * (size_t)(c->Npad + 64), c->stream));
-    HIPOK(hipMemsetAsync(r.sol, 0, (size_t)(c->Npad + 64), c->stream));
-    r.haveScores.assign(nc, 0);
-    r.haveSol.assign(nc, 0);
+    CHECK(dalloc(c, &r.mx, nc));
+    CHECK(dalloc(c, &r.bad, nc));
     return 0;
 }
 
 extern "C" int csr_batch_upload_scores(csr_ctx *c, int32_t chain, const double *scores) {
-    CHECK(need(c));
-    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
-    if (!scores) return fail("null host buffer");
-    const ChainInfo &ci = c->chains[chain];
-    for (int64_t i = 0; i < ci.n; ++i)
-        if (!std::isfinite(scores[i])) return fail("`scores` contains non-finite values");
-    CHECK(rocco_batch_buffers(c));
-    HIPOK(hipMemcpyAsync(c->rocco.scores + ci.off, scores, 8 * (size_t)ci.n, hipMemcpyHostToDevice, c->stream));
-    HIPOK(hipStreamSynchronize(c->stream));
-    c->rocco.haveScores[chain] = 1;
-    c->rocco.haveSol[chain] = 0;
+    CHECK(need_chain(c, chain, scores));
+    CHECK(check_finite("scores", scores, c->chains[chain].n));
+    CHECK(rocco_buffers(c));
+    CHECK(c->scores.upload(c, chain, scores));
+    scores_changed(c, chain);
     return 0;
 }
 
@@ -343,15 +330,13 @@ extern "C" int csr_batch_rocco_scores(csr_ctx *c, int32_t mode, double z) {
     CHECK(need(c));
     CHECK(settle(c));
     if (mode != CSR_ROCCO_SCORE_STATE && mode != CSR_ROCCO_SCORE_LOWER_CONFIDENCE) return fail("bad score mode %d", mode);
-    if (mode == CSR_ROCCO_SCORE_LOWER_CONFIDENCE && (!std::isfinite(z) || z < 0.0)) {
-        fail("`uncertaintyScoreZ` must be finite and non-negative");
-        return CSR_ROCCO_ERR_VALUE;
-    }
+    if (mode == CSR_ROCCO_SCORE_LOWER_CONFIDENCE && (!std::isfinite(z) || z < 0.0))
+        return value_error("`uncertaintyScoreZ` must be finite and non-negative");
     if (!c->haveBwd) return fail("no smoothed results to score");
     // the scores are built from the reference-layout copies of xs / Ps: the conversion csr_batch_export(CSR_EXPORT_SMOOTH) makes,
     // a no-op when those copies are current; values and blocked copies stay what they are
     CHECK(export_impl(c, CSR_EXPORT_SMOOTH));
-    CHECK(rocco_batch_buffers(c));
+    CHECK(rocco_buffers(c));
     const int nc = (int)c->chains.size();
     csr_ctx::Rocco &r = c->rocco;
     std::vector<double> mx((size_t)nc, -INFINITY);
@@ -362,7 +347,7 @@ extern "C" int csr_batch_rocco_scores(csr_ctx *c, int32_t mode, double z) {
     a.xs = c->nat[CSR_ARR_XS]; a.Ps = c->nat[CSR_ARR_PS]; a.d = c->mdl.state_dim;
     a.lower = mode == CSR_ROCCO_SCORE_LOWER_CONFIDENCE; a.z = z;
     a.off = c->dChainOff; a.len = c->dChainLen; a.active = nullptr;
-    a.scores = r.scores; a.mx = r.mx; a.bad = r.bad;
+    a.scores = c->scores.d; a.mx = r.mx; a.bad = r.bad;
     int64_t longest = 0;
     for (const ChainInfo &ci : c->chains) longest = std::max(longest, ci.n);
     const dim3 grid((unsigned)std::min<int64_t>((longest + 255) / 256, 1024), (unsigned)nc);
@@ -374,60 +359,41 @@ extern "C" int csr_batch_rocco_scores(csr_ctx *c, int32_t mode, double z) {
     std::vector<int> bad((size_t)nc, 0);
     HIPOK(hipMemcpyAsync(bad.data(), r.bad, 4 * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < nc; ++i) {
-        r.haveScores[i] = 0;
-        r.haveSol[i] = 0;
-    }
+    c->scores.clear_all();
+    for (int i = 0; i < nc; ++i) scores_changed(c, i);
     for (int i = 0; i < nc; ++i)
-        if (bad[i]) {
-            fail("`uncertainty` must be non-negative for lower_confidence (chain %d)", i);
-            return CSR_ROCCO_ERR_VALUE;
-        }
-    for (int i = 0; i < nc; ++i) r.haveScores[i] = 1;
+        if (bad[i]) return value_error("`uncertainty` must be non-negative for lower_confidence (chain %d)", i);
+    for (int i = 0; i < nc; ++i) c->scores.set(i, true);
     return 0;
 }
 
 extern "C" int csr_batch_download_scores(csr_ctx *c, int32_t chain, double *host_dst) {
-    CHECK(need(c));
-    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
-    if (!host_dst) return fail("null host buffer");
-    if (!c->rocco.scores || !c->rocco.haveScores[chain]) return fail("chain %d has no scores", chain);
-    const ChainInfo &ci = c->chains[chain];
-    HIPOK(hipMemcpyAsync(host_dst, c->rocco.scores + ci.off, 8 * (size_t)ci.n, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(hipStreamSynchronize(c->stream));
-    return 0;
+    CHECK(need_chain(c, chain, host_dst));
+    return c->scores.download(c, chain, host_dst);
 }
 
 extern "C" int csr_batch_rocco(csr_ctx *c, const csr_rocco_cfg *cfg, const unsigned char *chain_mask, csr_rocco_out *out) {
     CHECK(need(c));
     if (!cfg || !out) return fail("null argument");
-    const int nc = (int)c->chains.size();
-    if (!c->rocco.scores) return fail("no scores: call csr_batch_rocco_scores or csr_batch_upload_scores first");
-    std::vector<RoccoChainIn> chains;
     std::vector<int> idx;
-    for (int i = 0; i < nc; ++i) {
-        if (chain_mask && !chain_mask[i]) continue;
-        if (!c->rocco.haveScores[i]) return fail("chain %d has no scores", i);
+    const int missing = select_chains(c, chain_mask, c->scores, idx, NO_SCORES);
+    std::vector<RoccoChainIn> chains;
+    for (int i : idx) {         // (the chains in front of one without scores still answer for their own arguments first)
         CHECK(rocco_check_cfg(cfg[i], i, true));
         chains.push_back(RoccoChainIn{c->chains[i].off, c->chains[i].n, cfg[i].gamma, nullptr, cfg[i], &out[i]});
-        idx.push_back(i);
     }
-    RoccoDev dv{c->rocco.scores, nullptr, c->rocco.sol, c->rocco.bt};
-    for (int i : idx) c->rocco.haveSol[i] = 0;
+    CHECK(missing);
+    RoccoDev dv{c->scores.d, nullptr, c->sol.d, c->rocco.bt};
+    for (int i : idx) c->sol.set(i, false);
     CHECK(rocco_run(c, dv, chains));
-    for (int i : idx) c->rocco.haveSol[i] = 1;
+    for (int i : idx) c->sol.set(i, true);
     return 0;
 }
 
 extern "C" int csr_batch_rocco_download(csr_ctx *c, int32_t chain, uint8_t *solution) {
-    CHECK(need(c));
-    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
-    if (!solution) return fail("null host buffer");
-    if (!c->rocco.sol || !c->rocco.haveSol[chain]) return fail("chain %d has no ROCCO solution", chain);
-    const ChainInfo &ci = c->chains[chain];
-    HIPOK(hipMemcpyAsync(solution, c->rocco.sol + ci.off, (size_t)ci.n, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(hipStreamSynchronize(c->stream));
-    c->roccoWs.stats.d2h_bytes += ci.n;
+    CHECK(need_chain(c, chain, solution));
+    CHECK(c->sol.download(c, chain, solution));
+    c->roccoWs.stats.d2h_bytes += c->chains[chain].n;
     return 0;
 }
 
@@ -436,10 +402,10 @@ extern "C" int csr_batch_rocco_download(csr_ctx *c, int32_t chain, uint8_t *solu
 extern "C" int csr_batch_rocco_runs(csr_ctx *c, int32_t chain, int32_t max_gap_bins, int64_t capacity, int64_t *count,
                                     int64_t *starts, int64_t *ends) {
     CHECK(need(c));
-    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
+    CHECK(check_chain(c, chain));
     if (!count) return fail("null argument");
     if (capacity < 0 || (capacity > 0 && (!starts || !ends))) return fail("bad capacity / output buffers");
-    if (!c->rocco.sol || !c->rocco.haveSol[chain]) return fail("chain %d has no ROCCO solution", chain);
+    if (!c->sol.has(chain)) return fail("chain %d has no ROCCO solution", chain);
     const ChainInfo &ci = c->chains[chain];
     const int64_t nb = (ci.n + 1023) / 1024;
     const size_t oB = 0, oS = (8 * (size_t)(nb + 1) + 255) / 256 * 256, oE = oS + (8 * (size_t)capacity + 255) / 256 * 256,
@@ -447,7 +413,7 @@ extern "C" int csr_batch_rocco_runs(csr_ctx *c, int32_t chain, int32_t max_gap_b
     CHECK(c->roccoWs.runBuf.reserve(total));
     char *base = (char *)c->roccoWs.runBuf.ptr;
     RoccoRunArgs a;
-    a.sol = c->rocco.sol + ci.off;
+    a.sol = c->sol.at(c, chain);
     a.n = ci.n;
     a.gap = std::min<int64_t>(max_gap_bins > 0 ? max_gap_bins : 0, ci.n);
     a.blockSum = (unsigned long long *)(base + oB);

@@ -4,14 +4,6 @@
 // in the context: the row counts and counters come back at once (phase 1), views whose chosen set the values do not determine
 // are handed to the caller one by one (csr_segments_flagged*), and csr_segments_fetch copies the rows (phase 2).
 
-static int seg_value_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return CSR_SEG_ERR_VALUE;
-}
-
 // the device work space of the segment runs (the rows of the last run stay: they are host memory)
 static void seg_release(csr_ctx *c) {
     csr_ctx::Seg &g = c->seg;
@@ -257,9 +249,9 @@ extern "C" int csr_segments_run(csr_ctx *c, const double *scores, int64_t n, int
                                 int32_t min_run_bins, int32_t max_gap_bins, int32_t max_segments_per_view, int64_t *n_rows,
                                 int64_t *counters, int32_t *n_flagged) {
     DEFAULT_CTX_GUARD;
-    if (n_thresholds != n_null_scales) return seg_value_error("thresholds and nullScales must have the same length");
+    if (n_thresholds != n_null_scales) return value_error("thresholds and nullScales must have the same length");
     if (!n_rows || !counters || !n_flagged) return fail("null argument");
-    CHECK(dwb_ctx(c));
+    CHECK(ctx_or_default(c));
     csr_ctx::Seg &g = c->seg;
     g.have = false;
     if (n <= 0 || n_scales <= 0 || n_thresholds <= 0) {
@@ -270,10 +262,10 @@ extern "C" int csr_segments_run(csr_ctx *c, const double *scores, int64_t n, int
     if (!scores) return fail("null argument");
     SegSpec sp{1, &n_scales, scales, &n_thresholds, thresholds, null_scales, min_run_bins, max_gap_bins, max_segments_per_view};
     CHECK(seg_check_spec(sp));
-    CHECK(g.xBuf.reserve(8 * (size_t)n));
-    HIPOK(hipMemcpyAsync(g.xBuf.ptr, scores, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    const double *dx = nullptr;
+    CHECK(stage_vector(c, g.xBuf, scores, n, &dx));
     const int64_t off = 0;
-    CHECK(seg_run(c, (const double *)g.xBuf.ptr, (n + 63) / 64 * 64, 1, &off, &n, sp));
+    CHECK(seg_run(c, dx, (n + 63) / 64 * 64, 1, &off, &n, sp));
     seg_report(g, n_rows, counters, n_flagged);
     return 0;
 }
@@ -288,15 +280,16 @@ extern "C" int csr_batch_segments_run(csr_ctx *c, const int32_t *n_scales, const
     const int nc = (int)c->chains.size();
     SegSpec sp{nc, n_scales, scales, n_views, thresholds, null_scales, min_run_bins, max_gap_bins, max_segments_per_view};
     CHECK(seg_check_spec(sp));
+    std::vector<int> idx;
+    CHECK(select_chains(c, nullptr, c->scores, idx));
     std::vector<int64_t> off((size_t)nc), len((size_t)nc);
     int64_t rowLen = 64;
-    for (int i = 0; i < nc; ++i) {
-        if (!c->rocco.scores || !c->rocco.haveScores[i]) return fail("chain %d has no scores", i);
+    for (int i : idx) {
         off[i] = c->chains[i].off;
         len[i] = c->chains[i].n;
         rowLen = std::max(rowLen, (off[i] + len[i] + 63) / 64 * 64);
     }
-    CHECK(seg_run(c, c->rocco.scores, rowLen, 1, off.data(), len.data(), sp));
+    CHECK(seg_run(c, c->scores.d, rowLen, 1, off.data(), len.data(), sp));
     seg_report(c->seg, rows, counters, n_flagged);
     return 0;
 }
@@ -310,7 +303,7 @@ extern "C" int csr_dwb_panel_segments(csr_ctx *c, int32_t first_draw, int32_t n_
     DEFAULT_CTX_GUARD;
     if (!rows || !counters || !n_flagged) return fail("null argument");
     if (max_segments_per_view <= 0) return fail("the panel needs max_segments_per_view > 0");
-    CHECK(dwb_ctx(c));
+    CHECK(ctx_or_default(c));
     csr_ctx::Dwb &d = c->dwb;
     if (!d.ready) return fail("no DWB panel: call csr_dwb_panel_begin first");
     if (first_draw < 0 || n_draws <= 0 || n_draws > d.group || (int64_t)first_draw + n_draws > d.nDraws)
@@ -334,7 +327,7 @@ extern "C" int csr_dwb_panel_segments(csr_ctx *c, int32_t first_draw, int32_t n_
 // flagged views and phase 2 (the result of the context's last run)
 // ---------------------------------------------------------------------------------------------------------------
 static int seg_result(csr_ctx *&c, int32_t k, bool indexed) {
-    CHECK(dwb_ctx(c));
+    CHECK(ctx_or_default(c));
     if (!c->seg.have) return fail("no segment run on this context");
     if (indexed && (k < 0 || k >= (int)c->seg.flagged.size())) return fail("flagged view index out of range");
     return 0;

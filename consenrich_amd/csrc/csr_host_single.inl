@@ -25,6 +25,20 @@ static csr_ctx *default_ctx() {
     }
     return g_default;
 }
+// The entry into a call that takes host vectors: NULL addresses the default context, and the context's device is selected.  (The
+// entry itself holds DEFAULT_CTX_GUARD: the lock lives in its scope.)
+static int ctx_or_default(csr_ctx *&c) {
+    if (!c) c = default_ctx();
+    if (!c) return -1;
+    return ctx_select(c);
+}
+// *dev := the n doubles at `host`, copied into `buf` on c->stream
+static int stage_vector(csr_ctx *c, DevBuf &buf, const double *host, int64_t n, const double **dev) {
+    CHECK(buf.reserve(8 * (size_t)n));
+    HIPOK(hipMemcpyAsync(buf.ptr, host, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    *dev = (const double *)buf.ptr;
+    return 0;
+}
 
 // Freshly allocated NumPy outputs are unmapped pages: a D2H copy into them runs at the first-touch page-fault rate
 // (~10 GB/s on one thread, scripts/ubench/pcie.hip) -- five times slower than the PCIe copy itself, and at chr1 x 32 the

@@ -16,6 +16,7 @@
 #include "csr_segments.h"
 #include "csr_ess.h"
 #include "csr_step_groups.h"
+#include "csr_chain_tracks.h"
 
 #include <algorithm>
 #include <array>
@@ -49,6 +50,14 @@ static int fail(const char *fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return -1;
+}
+// an argument or input the reference answers with ValueError: its text, and CSR_ERR_VALUE instead of -1
+static int value_error(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return CSR_ERR_VALUE;
 }
 #define HIPOK(expr)                                                                                       \
     do {                                                                                                  \
@@ -145,6 +154,21 @@ struct PinBuf {
         return 0;
     }
     operator T *() const { return ptr; }
+};
+// A resident per-chain track of the batch and which chains hold one (ChainFlags, csr_chain_tracks.h): Npad + 64 elements laid out
+// like the reference-layout arrays (chain i at ChainInfo::off), from dalloc -- it dies with the batch -- allocated and zeroed at
+// first use.  `what` is how the error texts name the track.
+struct csr_ctx;
+template <class T>
+struct ChainTrack : ChainFlags {
+    T *d = nullptr;
+    const char *what;
+    explicit ChainTrack(const char *what_) : what(what_) {}
+    int ensure(csr_ctx *c);
+    T *at(const csr_ctx *c, int chain) const;
+    // the chain's n elements from / to the host, synchronised: upload marks the chain, download fails on a chain without the track
+    int upload(csr_ctx *c, int chain, const T *host);
+    int download(csr_ctx *c, int chain, T *host) const;
 };
 // N device arrays of one element per chain (dalloc: they die with the batch) and the pinned staging of their uploads, one slot each
 // (an upload from pageable memory may hold the host): the masks and run tables of the groups of a pipelined step
@@ -313,21 +337,18 @@ struct BatchState {
     // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)
     bool pnFillValid = false;
     float pnFillQ[4] = {0.f, 0.f, 0.f, 0.f};
-    // ROCCO peak selection (csr_host_rocco.inl): score tracks, masks and backtrace words of the batch's chains (allocated at first
-    // use); its work space is csr_ctx::roccoWs
+    // The per-chain tracks of the peak stages (allocated at first use): the score track (csr_batch_rocco_scores / csr_batch_upload_scores),
+    // the selection mask ROCCO leaves of it, and the DWB residual template of the robust null (csr_batch_null_prepare); which track
+    // invalidates which is scores_changed()
+    ChainTrack<double> scores{"scores"}, tmpl{"null template"};
+    ChainTrack<unsigned char> sol{"ROCCO solution"};
+    // ROCCO's work arrays without presence (csr_host_rocco.inl): backtrace words, per-chain maxima and flags; its growable work
+    // space is csr_ctx::roccoWs
     struct Rocco {
-        double *scores = nullptr, *mx = nullptr;
-        unsigned char *sol = nullptr;
+        double *mx = nullptr;
         unsigned long long *bt = nullptr;
         int *bad = nullptr;
-        std::vector<char> haveScores, haveSol;
     } rocco;
-    // robust null (csr_host_null.inl): one DWB residual template per chain, laid out like the score tracks (allocated at first use);
-    // have[chain]: csr_batch_null_prepare or csr_batch_null_template_upload left one
-    struct NullRes {
-        double *tmpl = nullptr;
-        std::vector<char> have;
-    } nullRes;
     // stats
     csr_run_stats rs{};
 };
@@ -416,7 +437,7 @@ struct csr_ctx : BatchState {
     // CONSENRICH_AMD_EPILOGUE_PCT: share of the batch's bins that final chains without an epilogue must reach for an early epilogue
     // group (0: no early groups)
     int epiPct = 10;
-    // ROCCO (csr_host_rocco.inl): tuning, counters and growable work space; the batch's tracks are BatchState::rocco
+    // ROCCO (csr_host_rocco.inl): tuning, counters and growable work space; the batch's tracks are BatchState::scores / sol
     struct RoccoWs {
         int depth = 0;          // speculation depth of the calibration (0 = default)
         DevBuf work, arena, runBuf;
@@ -519,6 +540,64 @@ int GroupSlots<T, N>::ensure(csr_ctx *c, int nc) {
     for (T *&x : d) CHECK(dalloc(c, &x, nc));
     stride = (size_t)nc;
     return pin.alloc((size_t)N * stride, hipHostMallocDefault);
+}
+
+template <class T>
+int ChainTrack<T>::ensure(csr_ctx *c) {
+    if (d) return 0;
+    CHECK(dalloc(c, &d, c->Npad + 64));
+    HIPOK(hipMemsetAsync(d, 0, sizeof(T) * (size_t)(c->Npad + 64), c->stream));
+    have.assign(c->chains.size(), 0);
+    return 0;
+}
+template <class T>
+T *ChainTrack<T>::at(const csr_ctx *c, int chain) const { return d + c->chains[chain].off; }
+template <class T>
+int ChainTrack<T>::upload(csr_ctx *c, int chain, const T *host) {
+    CHECK(ensure(c));
+    HIPOK(hipMemcpyAsync(at(c, chain), host, sizeof(T) * (size_t)c->chains[chain].n, hipMemcpyHostToDevice, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    set(chain, true);
+    return 0;
+}
+template <class T>
+int ChainTrack<T>::download(csr_ctx *c, int chain, T *host) const {
+    if (!has(chain)) return fail("chain %d has no %s", chain, what);
+    HIPOK(hipMemcpyAsync(host, at(c, chain), sizeof(T) * (size_t)c->chains[chain].n, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+// New scores of a chain: the selection mask made of the previous ones is dropped.  The chain's null template is NOT: it stays
+// present although it came from the previous scores -- that is how the stages have behaved since they landed, kept as it is.
+static void scores_changed(csr_ctx *c, int chain) { c->sol.set(chain, false); }
+
+static int need(csr_ctx *c);    // csr_host_batch.inl
+static int check_chain(const csr_ctx *c, int chain) {
+    if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
+    return 0;
+}
+// what every per-chain transfer entry checks first: a configured batch, the chain index, the caller's buffer
+static int need_chain(csr_ctx *c, int chain, const void *host) {
+    CHECK(need(c));
+    CHECK(check_chain(c, chain));
+    if (!host) return fail("null host buffer");
+    return 0;
+}
+static int check_finite(const char *name, const double *x, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(x[i])) return fail("`%s` contains non-finite values", name);
+    return 0;
+}
+// idx := the chains chain_mask takes (nullptr: every chain), in order.  A taken chain without the track fails with "chain i has no
+// ..."; idx then holds the taken chains in front of it.  ifNone: what a batch that never held the track answers instead
+static const char NO_SCORES[] = "no scores: call csr_batch_rocco_scores or csr_batch_upload_scores first";
+template <class T>
+static int select_chains(csr_ctx *c, const unsigned char *chain_mask, const ChainTrack<T> &track, std::vector<int> &idx,
+                         const char *ifNone = nullptr) {
+    idx.clear();
+    if (ifNone && !track.d) return fail("%s", ifNone);
+    const int missing = take_chains((int)c->chains.size(), chain_mask, track, idx);
+    return missing < 0 ? 0 : fail("chain %d has no %s", missing, track.what);
 }
 
 // Ends the configured batch: its device memory is freed and every BatchState member is back at its default (DevBuf / PinBuf members

@@ -54,12 +54,6 @@ def max_lag(bandwidth: int, kernel="bartlett") -> int:
     return max(8 * bw, 32) if kernel_code(kernel) == 2 else bw
 
 
-def _call(rc: int) -> None:
-    if rc == L.DWB_ERR_VALUE:       # what the reference answers with ValueError
-        raise ValueError(L.last_error())
-    L.check(rc)
-
-
 def _kname(kernel) -> bytes:
     return str(kernel).encode("utf-8")
 
@@ -74,7 +68,7 @@ def cGenerateDWBMultipliersFromNoise(noise, bandwidth, kernel="bartlett"):
         raise ValueError("noise length is too short for the requested DWB bandwidth")
     L.require_gpu()
     out = np.empty(n, np.float64)
-    _call(L.lib().csr_dwb_multipliers(L.dp(z), z.shape[0], bandwidth, _kname(kernel), L.dp(out)))
+    L.check_value(L.lib().csr_dwb_multipliers(L.dp(z), z.shape[0], bandwidth, _kname(kernel), L.dp(out)))
     return out
 
 
@@ -87,7 +81,7 @@ def cApplyStationaryNullDWB(template, multipliers):
     if t.shape[0] == 0:
         return out
     L.require_gpu()
-    _call(L.lib().csr_dwb_apply(L.dp(t), t.shape[0], L.dp(m), m.shape[0], L.dp(out)))
+    L.check_value(L.lib().csr_dwb_apply(L.dp(t), t.shape[0], L.dp(m), m.shape[0], L.dp(out)))
     return out
 
 
@@ -101,7 +95,7 @@ def cStationaryNullDWBDraw(template, bandwidth, rng, kernel="bartlett"):
         raise ValueError("noise length is too short for the requested DWB bandwidth")
     L.require_gpu()
     out = np.empty(t.shape[0], np.float64)
-    _call(L.lib().csr_dwb_draw(L.dp(t), t.shape[0], bandwidth, _kname(kernel), L.dp(noise), noise.shape[0], L.dp(out)))
+    L.check_value(L.lib().csr_dwb_draw(L.dp(t), t.shape[0], bandwidth, _kname(kernel), L.dp(noise), noise.shape[0], L.dp(out)))
     return out
 
 
@@ -145,7 +139,7 @@ def _tail_of_vector(x, thresholds, scales):
     nz = len(thresholds)
     off, sc = np.asarray(thresholds, np.float64), np.asarray(scales, np.float64)
     cnt, soft = np.zeros(nz, np.int64), np.zeros(nz, np.float64)
-    _call(L.lib().csr_dwb_tail_stats(None, L.dp(x), x.shape[0], nz, L.dp(off), L.dp(sc), cnt.ctypes.data_as(L.I64P), L.dp(soft)))
+    L.check_value(L.lib().csr_dwb_tail_stats(None, L.dp(x), x.shape[0], nz, L.dp(off), L.dp(sc), cnt.ctypes.data_as(L.I64P), L.dp(soft)))
     return cnt, soft
 
 
@@ -165,11 +159,11 @@ def _checked_templates(templates, lens):
 def _begin_panel(lib, ctx, n_arr, bw_arr, kernel, tmpl, z_stream, n_draws, draws_per_group):
     bw_p = bw_arr.ctypes.data_as(C.POINTER(C.c_int32))
     if tmpl is None:        # the resident templates of the batch context: nothing is uploaded but the noise
-        _call(lib.csr_batch_dwb_panel_begin(ctx, bw_p, _kname(kernel), L.dp(z_stream), z_stream.shape[0], n_draws, draws_per_group))
+        L.check_value(lib.csr_batch_dwb_panel_begin(ctx, bw_p, _kname(kernel), L.dp(z_stream), z_stream.shape[0], n_draws, draws_per_group))
         return
     t_all = np.ascontiguousarray(np.concatenate(tmpl))
-    _call(lib.csr_dwb_panel_begin(ctx, len(n_arr), n_arr.ctypes.data_as(L.I64P), bw_p, _kname(kernel), L.dp(t_all), L.dp(z_stream),
-                                  z_stream.shape[0], n_draws, draws_per_group))
+    L.check_value(lib.csr_dwb_panel_begin(ctx, len(n_arr), n_arr.ctypes.data_as(L.I64P), bw_p, _kname(kernel), L.dp(t_all), L.dp(z_stream),
+                                          z_stream.shape[0], n_draws, draws_per_group))
 
 
 def _run_panel(ctx, observed, lens, templates, null_centers, null_scales, *, threshold_z_grid, tail_quantiles, bandwidths,
@@ -214,7 +208,7 @@ def _run_panel(ctx, observed, lens, templates, null_centers, null_scales, *, thr
     try:
         # phase A: two order statistics per (draw, z); the lerp and the reductions over the draws on the host
         os_ = np.empty((nc, B, 2 * nz), np.float64)
-        _call(lib.csr_dwb_panel_order_stats(ctx, 2 * nz, ranks.ctypes.data_as(L.I64P), L.dp(os_)))
+        L.check_value(lib.csr_dwb_panel_order_stats(ctx, 2 * nz, ranks.ctypes.data_as(L.I64P), L.dp(os_)))
         out = [[None] * nz for _ in range(nc)]
         off2 = np.empty((nc, nz), np.float64)
         sc = np.empty((nc, nz), np.float64)
@@ -245,7 +239,7 @@ def _run_panel(ctx, observed, lens, templates, null_centers, null_scales, *, thr
         # phase B: tail occupancy and soft tail of every draw at the thresholds phase A gave
         cnt = np.empty((nc, B, nz), np.int64)
         soft = np.empty((nc, B, nz), np.float64)
-        _call(lib.csr_dwb_panel_tail_stats(ctx, nz, L.dp(off2), L.dp(sc), cnt.ctypes.data_as(L.I64P), L.dp(soft)))
+        L.check_value(lib.csr_dwb_panel_tail_stats(ctx, nz, L.dp(off2), L.dp(sc), cnt.ctypes.data_as(L.I64P), L.dp(soft)))
     finally:
         L.check(lib.csr_dwb_panel_end(ctx))
     for c in range(nc):
@@ -363,9 +357,9 @@ def _run_replays(ctx, observed, lens, templates, threshold_views, *, bandwidths,
         for d0 in range(0, R, group):
             g = min(group, R - d0)
             rows, counters, flagged = np.zeros(nc * g, np.int64), np.zeros(nc * g * 3, np.int64), C.c_int32(0)
-            S._call(lib.csr_dwb_panel_segments(ctx, d0, g, n_s.ctypes.data_as(L.I32P), sc_all.ctypes.data_as(L.I64P),
-                                               n_v.ctypes.data_as(L.I32P), L.dp(thr_all), L.dp(ns_all), min_run, gap, view_cap,
-                                               rows.ctypes.data_as(L.I64P), counters.ctypes.data_as(L.I64P), C.byref(flagged)))
+            L.check_value(lib.csr_dwb_panel_segments(ctx, d0, g, n_s.ctypes.data_as(L.I32P), sc_all.ctypes.data_as(L.I64P),
+                                                     n_v.ctypes.data_as(L.I32P), L.dp(thr_all), L.dp(ns_all), min_run, gap, view_cap,
+                                                     rows.ctypes.data_as(L.I64P), counters.ctypes.data_as(L.I64P), C.byref(flagged)))
             # the flagged views of this group are resolved before the next group overwrites its rows
             tracks = S.collect(ctx, rows, counters, flagged.value, view_cap)
             capped += S.last_run_stats()["capped_views"]

@@ -34,12 +34,6 @@ def _c_int(v) -> int:
     return v
 
 
-def _call(rc: int) -> None:
-    if rc == L.ESS_ERR_VALUE:       # what the reference answers with ValueError
-        raise ValueError(L.last_error())
-    L.check(rc)
-
-
 def cEstimateEffectiveSampleSize(values, maxLag, activeMask=None, logPositive=False, windowIntervals=0):
     """pyx:9160-9279: (n_eff, tau, lags_used) of the positive-autocorrelation scan.  Without a mask, a log and a window the
     reference's fast path runs (no finiteness checks); otherwise its general path (pair counts under the mask, Bartlett taper
@@ -75,7 +69,7 @@ def cEstimateEffectiveSampleSize(values, maxLag, activeMask=None, logPositive=Fa
     L.require_gpu()
     out = L.EssOut()
     mp = None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8))
-    _call(L.lib().csr_ess_scan(L.dp(x), n, maxLag, mp, int(general), windowIntervals, C.byref(out)))
+    L.check_value(L.lib().csr_ess_scan(L.dp(x), n, maxLag, mp, int(general), windowIntervals, C.byref(out)))
     return float(out.n_eff), float(out.tau), int(out.lags_used)
 
 

@@ -44,12 +44,6 @@ def _as_float_vector(name: str, values) -> np.ndarray:
     return np.ascontiguousarray(arr)
 
 
-def _call(rc: int) -> None:
-    if rc == L.NULL_ERR_VALUE:
-        raise ValueError(L.last_error())
-    L.check(rc)
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # host-decided tracks: the reference's steps in NumPy
 # ---------------------------------------------------------------------------------------------------------------
@@ -166,7 +160,7 @@ def _device_prepare(z: np.ndarray, bulk_quantile: float, given=None):
     out = L.NullOut()
     template = np.empty(z.shape[0], np.float64)
     g = None if given is None else np.asarray(given, np.float64)
-    _call(L.lib().csr_null_prepare(L.dp(z), z.shape[0], float(bulk_quantile), L.dp(g), C.byref(out), L.dp(template)))
+    L.check_value(L.lib().csr_null_prepare(L.dp(z), z.shape[0], float(bulk_quantile), L.dp(g), C.byref(out), L.dp(template)))
     return out, template
 
 
@@ -206,7 +200,7 @@ def estimate_template_scale(template) -> float:
     t = _as_float_vector("template", template)
     L.require_gpu()
     out = np.empty(4, np.float64)
-    _call(L.lib().csr_null_scale(L.dp(t), t.shape[0], L.dp(out)))
+    L.check_value(L.lib().csr_null_scale(L.dp(t), t.shape[0], L.dp(out)))
     return float(out[0])
 
 
@@ -215,5 +209,5 @@ def sort_values(values) -> np.ndarray:
     v = _as_float_vector("values", values)
     L.require_gpu()
     out = np.empty(v.shape[0], np.float64)
-    _call(L.lib().csr_null_sort(L.dp(v), v.shape[0], L.dp(out)))
+    L.check_value(L.lib().csr_null_sort(L.dp(v), v.shape[0], L.dp(out)))
     return out

@@ -46,12 +46,6 @@ def _c_int(v) -> int:
     return v
 
 
-def _call(rc: int) -> None:
-    if rc == L.SEG_ERR_VALUE:       # what the reference answers with ValueError
-        raise ValueError(L.last_error())
-    L.check(rc)
-
-
 def _i32p(a):
     return a.ctypes.data_as(L.I32P)
 
@@ -65,19 +59,19 @@ def collect(ctx, rows_per_track, counters, n_flagged, cap):
     lib = L.lib()
     for k in range(int(n_flagged)):
         track, si, view, nc = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
-        _call(lib.csr_segments_flagged(ctx, k, C.byref(track), C.byref(si), C.byref(view), C.byref(nc)))
+        L.check_value(lib.csr_segments_flagged(ctx, k, C.byref(track), C.byref(si), C.byref(view), C.byref(nc)))
         score, start = np.empty(nc.value, np.float64), np.empty(nc.value, np.int64)
-        _call(lib.csr_segments_flagged_fetch(ctx, k, L.dp(score), _i64p(start)))
+        L.check_value(lib.csr_segments_flagged_fetch(ctx, k, L.dp(score), _i64p(start)))
         selected = np.argpartition(-score, cap - 1)[:cap]                       # pyx:9634-9635
         selected = selected[np.argsort(start[selected], kind="mergesort")]
         selected = np.ascontiguousarray(selected, np.int64)
-        _call(lib.csr_segments_flagged_select(ctx, k, selected.shape[0], _i64p(selected)))
+        L.check_value(lib.csr_segments_flagged_select(ctx, k, selected.shape[0], _i64p(selected)))
     rows = np.asarray(rows_per_track, np.int64).reshape(-1)
     counters = np.asarray(counters, np.int64).reshape(-1, 3)
     total = int(rows.sum())
     ints = [np.empty(total, np.int64) for _ in range(4)]
     flts = [np.empty(total, np.float64) for _ in range(4)]
-    _call(lib.csr_segments_fetch(ctx, *[_i64p(a) for a in ints], *[L.dp(a) for a in flts]))
+    L.check_value(lib.csr_segments_fetch(ctx, *[_i64p(a) for a in ints], *[L.dp(a) for a in flts]))
     _last["capped_views"] = int(counters[:, 1].sum())
     _last["fallback_views"] = int(n_flagged)
     out, lo = [], 0
@@ -118,8 +112,8 @@ def cMultiscaleCandidateSegmentStats(scores, scales, thresholds, nullScales, min
         return (*[np.zeros(0, np.int64) for _ in range(4)], *[np.zeros(0, np.float64) for _ in range(4)], 0, 0, 0)
     L.require_gpu()
     rows, counters, flagged = np.zeros(1, np.int64), np.zeros(3, np.int64), C.c_int32(0)
-    _call(L.lib().csr_segments_run(None, L.dp(x), x.shape[0], sc.shape[0], _i64p(sc), thr.shape[0], L.dp(thr), ns.shape[0], L.dp(ns),
-                                   min_run, gap, cap, _i64p(rows), _i64p(counters), C.byref(flagged)))
+    L.check_value(L.lib().csr_segments_run(None, L.dp(x), x.shape[0], sc.shape[0], _i64p(sc), thr.shape[0], L.dp(thr), ns.shape[0], L.dp(ns),
+                                           min_run, gap, cap, _i64p(rows), _i64p(counters), C.byref(flagged)))
     return collect(None, rows, counters, flagged.value, max(cap, 0))[0]
 
 

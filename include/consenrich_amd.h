@@ -504,7 +504,10 @@ int csr_batch_gather_tracks(csr_ctx *ctx, csr_comm *comm, int64_t cap_bins, floa
  * changes speed only).  Additive to ABI 6: new functions and structs, no change to existing ones. */
 enum { CSR_ROCCO_FIXED_PENALTY = 0, CSR_ROCCO_TARGET_COUNT = 1 };
 enum { CSR_ROCCO_SCORE_STATE = 0, CSR_ROCCO_SCORE_LOWER_CONFIDENCE = 1 };
-enum { CSR_ROCCO_ERR_VALUE = 2 };   /* return code: an argument or input the reference answers with ValueError (message: csr_last_error) */
+/* return code of every peak-stage call: an argument or input the reference answers with ValueError (message: csr_last_error).  The
+ * stages' own names below are the same value. */
+enum { CSR_ERR_VALUE = 2 };
+enum { CSR_ROCCO_ERR_VALUE = CSR_ERR_VALUE };
 typedef struct csr_rocco_cfg {
     int32_t mode;               /* CSR_ROCCO_FIXED_PENALTY: one solve at `penalty`; CSR_ROCCO_TARGET_COUNT: calibrate (pyx:8773-8844) */
     int32_t max_iter;           /* bisection steps; max(max_iter, 1) are made */
@@ -555,7 +558,7 @@ int csr_get_rocco_stats(csr_ctx *ctx, csr_rocco_stats *out);
  * with the reference's message in csr_last_error; such checks run before any launch.  `kernel`: bartlett / triangle / triangular,
  * parzen, qs / quadratic_spectral (case, surrounding blanks and '-' for '_' do not matter).  A bandwidth below 2 counts as 2;
  * maxLag = bandwidth, or max(8 bandwidth, 32) for qs, at most 512. */
-enum { CSR_DWB_ERR_VALUE = 2 };
+enum { CSR_DWB_ERR_VALUE = CSR_ERR_VALUE };
 int csr_dwb_max_lag(int32_t bandwidth, const char *kernel, int32_t *max_lag);
 /* The natives on host arrays (default context).  out: noise_len - 2 maxLag multipliers / n values. */
 int csr_dwb_multipliers(const double *noise, int64_t noise_len, int32_t bandwidth, const char *kernel, double *out);
@@ -610,7 +613,7 @@ int csr_batch_dwb_observed(csr_ctx *ctx, int32_t chain, int32_t n_z, const doubl
  * run as long as a chromosome (a scale of n, or a threshold below the whole track) is a loop of n / 8 steps of one lane group.
  * R * S * V may not exceed 65535.  The reference's one ValueError (different numbers of thresholds and null scales) returns
  * CSR_SEG_ERR_VALUE before any launch; n, n_scales or n_thresholds <= 0 gives no rows and zero counters. */
-enum { CSR_SEG_ERR_VALUE = 2 };
+enum { CSR_SEG_ERR_VALUE = CSR_ERR_VALUE };
 int csr_segments_run(csr_ctx *ctx, const double *scores, int64_t n, int32_t n_scales, const int64_t *scales, int32_t n_thresholds,
                      const double *thresholds, int32_t n_null_scales, const double *null_scales, int32_t min_run_bins,
                      int32_t max_gap_bins, int32_t max_segments_per_view, int64_t *n_rows, int64_t *counters, int32_t *n_flagged);
@@ -643,7 +646,7 @@ int csr_segments_fetch(csr_ctx *ctx, int64_t *start, int64_t *end, int64_t *scal
  * then takes an UNSTABLE argsort of the track, whose tie order the values do not determine: the caller decides such a track with
  * NumPy; the fields up to support_size are filled as far as they were reached, no template is left.
  * A non-finite or empty vector returns CSR_NULL_ERR_VALUE with the reference's ValueError text, before any launch. */
-enum { CSR_NULL_ERR_VALUE = 2 };
+enum { CSR_NULL_ERR_VALUE = CSR_ERR_VALUE };
 enum { CSR_NULL_LOWER_BULK = 0, CSR_NULL_FULL_TRACK = 1 };                  /* bulk_source */
 enum { CSR_NULL_HALF_SAMPLE_MODE = 0, CSR_NULL_MEDIAN = 1 };                /* center_method (after the bulk source) */
 enum { CSR_NULL_CENTRAL_SUPPORT = 0, CSR_NULL_NEAREST_SUPPORT = 1 };        /* null_method */
@@ -689,7 +692,7 @@ int csr_batch_dwb_panel_begin(csr_ctx *ctx, const int32_t *bandwidth, const char
  * scanned on the reference's fast path.  thresholds / scales: [chain][n_z] (n_z <= 16; kinds 1 and 2 read the first pair);
  * max_lags[chain]; chain_mask: n_chains bytes or NULL = all; out: n_chains records, those of the other chains untouched.  No
  * resident array changes. */
-enum { CSR_ESS_ERR_VALUE = 2 };
+enum { CSR_ESS_ERR_VALUE = CSR_ERR_VALUE };
 enum { CSR_ESS_OCCUPANCY = 1, CSR_ESS_SOFT = 2, CSR_ESS_INTEGRATED = 3 };
 typedef struct csr_ess_out {
     double n_eff, tau;

@@ -47,12 +47,12 @@ def panel(lens, B, bw, group, label):
     os_, cnt, soft = np.empty((nc, B, 2 * nz)), np.empty((nc, B, nz), np.int64), np.empty((nc, B, nz))
     L.check(lib.csr_profile_enable(None, 1))
     t = time.perf_counter()
-    dwb._call(lib.csr_dwb_panel_begin(None, nc, n_arr.ctypes.data_as(L.I64P), bw_arr.ctypes.data_as(C.POINTER(C.c_int32)), b"bartlett",
-                                      L.dp(t_all), L.dp(noise), noise.size, B, group))
+    L.check_value(lib.csr_dwb_panel_begin(None, nc, n_arr.ctypes.data_as(L.I64P), bw_arr.ctypes.data_as(C.POINTER(C.c_int32)), b"bartlett",
+                                          L.dp(t_all), L.dp(noise), noise.size, B, group))
     t_up = time.perf_counter() - t
-    t = time.perf_counter(); dwb._call(lib.csr_dwb_panel_order_stats(None, 2 * nz, ranks.ctypes.data_as(L.I64P), L.dp(os_))); t_a = time.perf_counter() - t
+    t = time.perf_counter(); L.check_value(lib.csr_dwb_panel_order_stats(None, 2 * nz, ranks.ctypes.data_as(L.I64P), L.dp(os_))); t_a = time.perf_counter() - t
     off = np.ascontiguousarray(np.quantile(os_[:, :, 1::2], 0.9, axis=1)); sc = np.ones((nc, nz))
-    t = time.perf_counter(); dwb._call(lib.csr_dwb_panel_tail_stats(None, nz, L.dp(off), L.dp(sc), cnt.ctypes.data_as(L.I64P), L.dp(soft))); t_b = time.perf_counter() - t
+    t = time.perf_counter(); L.check_value(lib.csr_dwb_panel_tail_stats(None, nz, L.dp(off), L.dp(sc), cnt.ctypes.data_as(L.I64P), L.dp(soft))); t_b = time.perf_counter() - t
     kt = (L.KernelTime * 64)(); nk = C.c_int32(0)
     L.check(lib.csr_profile_read(None, kt, 64, C.byref(nk)))
     kernels = {kt[i].name.decode(): round(kt[i].total_ms, 2) for i in range(min(nk.value, 64)) if kt[i].name.decode().startswith("dwb_")}

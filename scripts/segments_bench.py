@@ -179,17 +179,17 @@ def device_workload(name, lens, args):
     L.check(lib.csr_profile_enable(None, 1))
     rows_total = capped = flagged_total = 0
     t0 = time.perf_counter()
-    dwb._call(lib.csr_dwb_panel_begin(None, nc, n_arr.ctypes.data_as(L.I64P), bw_arr.ctypes.data_as(L.I32P), b"bartlett", L.dp(t_all),
-                                      L.dp(noise), noise.shape[0], R, group))
+    L.check_value(lib.csr_dwb_panel_begin(None, nc, n_arr.ctypes.data_as(L.I64P), bw_arr.ctypes.data_as(L.I32P), b"bartlett", L.dp(t_all),
+                                          L.dp(noise), noise.shape[0], R, group))
     t_begin = time.perf_counter() - t0
     t_collect = 0.0
     try:
         for d0 in range(0, R, group):
             g = min(group, R - d0)
             rows, counters, fl = np.zeros(nc * g, np.int64), np.zeros(3 * nc * g, np.int64), C.c_int32(0)
-            S._call(lib.csr_dwb_panel_segments(None, d0, g, n_s.ctypes.data_as(L.I32P), sc_all.ctypes.data_as(L.I64P),
-                                               n_v.ctypes.data_as(L.I32P), L.dp(thr_all), L.dp(ns_all), 1, 0, CAP,
-                                               rows.ctypes.data_as(L.I64P), counters.ctypes.data_as(L.I64P), C.byref(fl)))
+            L.check_value(lib.csr_dwb_panel_segments(None, d0, g, n_s.ctypes.data_as(L.I32P), sc_all.ctypes.data_as(L.I64P),
+                                                     n_v.ctypes.data_as(L.I32P), L.dp(thr_all), L.dp(ns_all), 1, 0, CAP,
+                                                     rows.ctypes.data_as(L.I64P), counters.ctypes.data_as(L.I64P), C.byref(fl)))
             t1 = time.perf_counter()
             S.collect(None, rows, counters, fl.value, CAP)
             t_collect += time.perf_counter() - t1

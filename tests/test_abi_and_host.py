@@ -234,6 +234,23 @@ def test_step_groups_header_hands_out_chains_as_the_pipelined_step_expects(tmp_p
     assert r.returncode == 0 and "step_groups_check ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def test_chain_tracks_header_selects_chains_as_the_peak_stages_expect(tmp_path):
+    """consenrich_amd/csrc/csr_chain_tracks.h is plain C++17: tests/chain_tracks_check.cpp (presence flags of a per-chain track,
+    the chains a mask takes and the first of them without the track, the scatter of compact results) built stand-alone under
+    the address and undefined-behaviour sanitizers."""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "chain_tracks_check"
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "consenrich_amd", "csrc"), os.path.join(ROOT, "tests", "chain_tracks_check.cpp"),
+                           "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "chain_tracks_check ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+
+
 def test_qseed_posterior_fails_loudly_without_a_gpu():
     """The grid posterior of the Q0 seed (pyx:1905-2146) runs on the device since round 2 (csr_qseed_post.h; its golden
     vectors are checked under -m gpu, tests/test_gpu_qseed.py): without a GPU the call must raise, not compute on the host."""
