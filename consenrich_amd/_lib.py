@@ -169,6 +169,8 @@ ROCCO_SCORE_STATE, ROCCO_SCORE_LOWER_CONFIDENCE = 0, 1
 ERR_VALUE = 2       # CSR_ERR_VALUE: what the reference answers with ValueError (check_value); the stages' own names are aliases
 ROCCO_ERR_VALUE = DWB_ERR_VALUE = SEG_ERR_VALUE = NULL_ERR_VALUE = ESS_ERR_VALUE = ERR_VALUE
 ESS_OCCUPANCY, ESS_SOFT, ESS_INTEGRATED = 1, 2, 3
+PEAK_P, PEAK_Q, PEAK_Q_MAX_P = 1, 2, 4
+PEAK_BAD_OBSERVED, PEAK_BAD_POOL = 1, 2
 
 
 class KernelTime(C.Structure):
@@ -307,6 +309,20 @@ SYMBOLS = {
     "csr_batch_ess": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, DP, DP, I64P, C.c_char_p, C.POINTER(EssOut)]),
     "csr_batch_rocco_excess_ranks": (C.c_int, [C.c_void_p, DP, C.c_char_p, I64P, DP]),
     "csr_batch_rocco_upload": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8)]),
+    "csr_peakscore_segments": (C.c_int, [DP, C.c_int64, C.c_int64, I64P, I64P, C.c_int32, DP, DP, DP, DP, DP, DP, I32P]),
+    "csr_batch_peakscore_segments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, I64P, I64P, C.c_int32, DP, DP, DP, DP, DP, DP,
+                                               I32P]),
+    "csr_peakscore_pq": (C.c_int, [DP, C.c_int64, DP, C.c_int64, C.c_int64, C.c_int32, C.c_int32, DP, DP, I64P,
+                                   C.POINTER(C.c_uint32)]),
+    "csr_dwb_panel_pool_begin": (C.c_int, [C.c_void_p, C.c_int64]),
+    "csr_dwb_panel_pool_append": (C.c_int, [C.c_void_p, C.c_int32, I32P]),
+    "csr_dwb_panel_pool_flagged": (C.c_int, [C.c_void_p, C.c_int32, I32P, I32P, I64P]),
+    "csr_dwb_panel_pool_flagged_fetch": (C.c_int, [C.c_void_p, C.c_int32, I64P, I64P, I64P, I64P, DP, DP, DP, DP]),
+    "csr_dwb_panel_pool_flagged_upload": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, DP, DP, DP]),
+    "csr_dwb_panel_pool_draw_stats": (C.c_int, [C.c_void_p, I64P, I64P, I64P, DP, I64P]),
+    "csr_dwb_panel_pool_pq": (C.c_int, [C.c_void_p, C.c_int32, DP, C.c_int64, C.c_int32, DP, DP, I64P, C.POINTER(C.c_uint32)]),
+    "csr_dwb_panel_pool_download": (C.c_int, [C.c_void_p, C.c_int32, I64P, DP, DP, DP]),
+    "csr_dwb_panel_pool_end": (C.c_int, [C.c_void_p]),
 }
 
 _lib = None

@@ -781,6 +781,62 @@ class DeviceBatch:
                               max_segments=max_segments, max_segments_per_view=max_segments_per_view,
                               draws_per_group=draws_per_group, noise=noise)
 
+    # -- the best score of segments across threshold views (consenrich_amd/peakscore.py) -----------------------------------
+    def best_segment_scores(self, chain: int, threshold_views, starts=None, ends=None, *, max_gap_bins: int = 0):
+        """`peakscore.best_segment_scores` of one chain's RESIDENT score track (rocco_scores / upload_scores): the reference's
+        score dict per segment.  starts / ends None: the runs of the chain's ROCCO mask (rocco_runs), the exported peaks of a
+        first pass.  Reads the track; no resident array changes and no track is downloaded."""
+        from . import peakscore as P
+
+        if (starts is None) != (ends is None):
+            raise ValueError("starts and ends must be given together")
+        if starts is None:
+            starts, ends = self.rocco_runs(chain, max_gap_bins)
+        views = P._Views(threshold_views)
+        if not views.keys:
+            return [dict(P._ZERO) for _ in range(len(starts))]
+        return P.score_details(P.segment_score_arrays(self._ctx, int(chain), None, starts, ends, views), views)
+
+    def dwb_peak_scoring(self, threshold_views, *, bandwidths, peaks=None, templates=None, num_replay=64, kernel="bartlett",
+                         random_seed=0, scale_bins=None, min_run_bins=1, max_gap_bins=0, max_segments=20000,
+                         max_segments_per_view=1000, draws_per_group=0, noise=None, num_bootstrap=None):
+        """The numeric content of the reference's `_addDWBPeakScoringToPeakMeta` (peaks.py:2605-3157) for every chain:
+        `peakscore.score_candidate_regions` of the chain's observed candidates and null replays (dwb_replay), with the exported
+        peaks scored on the RESIDENT score track.  peaks: None = the runs of each chain's ROCCO mask, or (starts, ends) per
+        chain.  num_replay <= 0 and a chain without peaks give the reference's early exits (enabled=False with its reason).
+        Returns one dict per chain: enabled, candidate_details, peaks, summary.  No resident array changes, no track of the fit
+        or of the scores is downloaded, and the rows of the replays stay on the device in a pool of the panel's own
+        (`peakscore.ReplayPool`; `peakscore.last_pool_stats()` counts the draws that had to be decided on the host)."""
+        from . import peakscore as P
+
+        nc = len(self.chain_lens)
+        if len(threshold_views) != nc or (peaks is not None and len(peaks) != nc):
+            raise ValueError("one set of threshold views (and of peaks) per chain")
+        spans = [(self.rocco_runs(c) if peaks is None else peaks[c]) for c in range(nc)]
+        spans = [list(zip([int(a) for a in s[0]], [int(b) for b in s[1]])) for s in spans]
+        if int(num_replay) <= 0:
+            return [P.disabled("no_peaks", 0) if not spans[c] else P.disabled("no_bootstrap_draws", len(spans[c])) for c in range(nc)]
+        if not any(spans):
+            return [P.disabled("no_peaks", 0) for _ in range(nc)]
+        pool = P.ReplayPool(self._ctx, list(self.chain_lens), templates, threshold_views, bandwidths=bandwidths, num_replay=num_replay,
+                            kernel=kernel, random_seed=random_seed, scale_bins=scale_bins, min_run_bins=min_run_bins,
+                            max_gap_bins=max_gap_bins, max_segments=max_segments, max_segments_per_view=max_segments_per_view,
+                            draws_per_group=draws_per_group, noise=noise)
+        # the observed side first: while the pool is open a segment run leaves its rows on the device
+        observed = self._segment_tracks(pool.views, pool.scales, pool.min_run, pool.gap, pool.total_cap, pool.view_cap)
+        scores = [self.best_segment_scores(c, threshold_views[c], [a for a, _ in spans[c]], [b for _, b in spans[c]]) if spans[c] else []
+                  for c in range(nc)]
+        out = []
+        with pool:
+            for c in range(nc):
+                if not spans[c]:
+                    out.append(P.disabled("no_peaks", 0))
+                    continue
+                out.append(P.score_candidate_regions(observed[c], None, spans[c], scores[c], self.chain_lens[c],
+                                                     num_bootstrap=num_bootstrap, scale_bins=pool.scales[c], min_run_bins=min_run_bins,
+                                                     dependence_span=int(pool.bws[c]), random_seed=random_seed, pool=pool.chain(c)))
+        return out
+
     def export(self, what: int):
         L.check(self._lib.csr_batch_export(self._ctx, int(what)))
 

@@ -347,6 +347,7 @@ extern "C" int csr_dwb_panel_end(csr_ctx *c) {
     HIPOK(hipStreamSynchronize(c->stream));
     for (DevBuf *b : {&d.rowBuf, &d.noiseBuf, &d.tmplBuf, &d.partBuf, &d.outBuf, &d.meanBuf}) b->release();
     seg_release(c);     // the work space of csr_dwb_panel_segments goes with the panel
+    peak_pool_release(c);       // ... and so does its replay pool
     return 0;
 }
 

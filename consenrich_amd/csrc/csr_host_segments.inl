@@ -224,7 +224,7 @@ static int seg_run(csr_ctx *c, const double *dRows, int64_t rowLen, int nRows, c
         a.oMax = (double *)(ob + 5 * slot);
         HIPOK(hipMemcpyAsync(g.baseBuf.ptr, base.data(), 8 * nJobs, hipMemcpyHostToDevice, c->stream));
         CHECK(launch(c, "seg_emit", "k_seg_emit", k_seg_emit, jobs, dim3(256), 0, c->stream, a));
-        {
+        if (!g.deviceOnly) {
             Scope sc(c, "seg_download");
             void *dst[6] = {g.oStart.data(), g.oEnd.data(), g.oScore.data(), g.oInteg.data(), g.oMean.data(), g.oMax.data()};
             for (int k = 0; k < 6; ++k) HIPOK(hipMemcpyAsync(dst[k], ob + k * slot, 8 * n, hipMemcpyDeviceToHost, c->stream));
@@ -379,6 +379,7 @@ extern "C" int csr_segments_fetch(csr_ctx *c, int64_t *start, int64_t *end, int6
     DEFAULT_CTX_GUARD;
     CHECK(seg_result(c, 0, false));
     const csr_ctx::Seg &g = c->seg;
+    if (g.deviceOnly) return fail("the rows of this run stayed on the device: a replay pool is open (csr_dwb_panel_pool_append takes them)");
     for (const auto &f : g.flagged)
         if (!f.resolved) return fail("a flagged view has not been resolved (csr_segments_flagged_select)");
     if (g.oStart.empty()) return 0;

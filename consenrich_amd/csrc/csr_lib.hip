@@ -15,6 +15,7 @@
 #include "csr_null.h"
 #include "csr_segments.h"
 #include "csr_ess.h"
+#include "csr_peakscore.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
 
@@ -467,6 +468,7 @@ struct csr_ctx : BatchState {
     struct Seg {
         DevBuf chainBuf, prefixBuf, excessBuf, exPrefixBuf, cntBuf, runBuf, keepBuf, statBuf, metaBuf, baseBuf, outBuf, xBuf;
         bool have = false;
+        bool deviceOnly = false;    // a replay pool is open (csr_dwb_panel_pool_begin): a run's rows stay on the device
         int cap = 0;
         std::vector<int64_t> rowsPerTrack, counters;    // [track], [track][3]
         std::vector<int64_t> oStart, oEnd, oScale, oView;
@@ -480,6 +482,31 @@ struct csr_ctx : BatchState {
         };
         std::vector<Flagged> flagged;
     } seg;
+    // DWB peak scoring (csr_host_peakscore.inl): growable work space of a call -- an uploaded host track, the segments, views and
+    // results of a scoring call, the observed and pooled statistics with their p / q values (sorted through nullWs)
+    struct PeakWs {
+        DevBuf xBuf, segBuf, pqBuf;
+    } peakWs;
+    // the replay pool of a DWB panel (csr_dwb_panel_pool_*): per chain the three metric columns (score, integrated excess, max
+    // excess) of every replay candidate that survives the total cap, appended group by group; freed by csr_dwb_panel_end
+    struct PeakPool {
+        bool active = false;
+        int nc = 0, nDraws = 0;
+        int64_t totalCap = 0;               // 0: no total cap
+        std::vector<DevBuf> col;            // [chain][3]
+        std::vector<int64_t> n, cap;        // values held / capacity per chain
+        std::vector<int64_t> count, before; // [chain][draw]: candidates after / before the total cap (-1: draw not appended)
+        std::vector<int64_t> counters;      // [chain][draw][3]: phase 1's (eligible, views over the cap, discarded by the per-view cap)
+        std::vector<double> mx;             // [chain][draw]: np.max of the kept scores (0.0 without candidates)
+        struct Flagged {                    // a draw over the total cap with a NaN score: the caller decides it
+            int chain, draw;
+            int64_t rowBase, rows, slot;    // its rows in the last run's output; where its `totalCap` values go in the pool
+            bool resolved;
+        };
+        std::vector<Flagged> flagged;
+        int64_t fetchedTracks = 0;
+        DevBuf jobBuf, outBuf;
+    } pool;
     // profiling
     bool profiling = false;
     std::map<std::string, ProfEntry> prof;
@@ -487,6 +514,7 @@ struct csr_ctx : BatchState {
 };
 
 static int settle(csr_ctx *c);
+static void peak_pool_release(csr_ctx *c);      // csr_host_peakscore.inl
 static int export_impl(csr_ctx *c, uint32_t what);
 
 // The pass that just ran wrote these arrays in the given copies (and not in the other)
@@ -867,3 +895,4 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_null.inl"
 #include "csr_host_segments.inl"
 #include "csr_host_ess.inl"
+#include "csr_host_peakscore.inl"

@@ -635,3 +635,20 @@ def first_pass_peaks_batch(batch: DeviceBatch, *, dependence_spans, threshold_z,
                     r["budget_fallback_window"] = True
         r["starts"], r["ends"] = batch.rocco_runs(ch, max_gap_bins)
     return res
+
+
+def score_peaks_batch(batch: DeviceBatch, first_pass, panel, *, dependence_spans, random_seed, min_run_bins: int = 1,
+                      num_replay: int = 64, draws_per_group: int = 0) -> List[dict]:
+    """The next link after `first_pass_peaks_batch`: the reference's DWB peak scoring (`_addDWBPeakScoringToPeakMeta`,
+    peaks.py:2605-3157) of every chain's first-pass peaks against null replays of the same panel -- empirical p and q values per
+    candidate region and per exported peak.  first_pass: what first_pass_peaks_batch returned (its starts / ends are the exported
+    peaks); panel: the threshold views per chain that `DeviceBatch.dwb_panel` returned for the same seed; the replays are the
+    first min(num_replay, 64) draws of that seed's stream with the chain's dependence span as bandwidth, the candidate scales the
+    reference's five at that span.  Returns `DeviceBatch.dwb_peak_scoring`'s dict per chain."""
+    nc = len(batch.chain_lens)
+    spans = [max(int(s), 2) for s in (dependence_spans if np.ndim(dependence_spans) else [dependence_spans] * nc)]
+    if len(spans) != nc or len(first_pass) != nc or len(panel) != nc:
+        raise ValueError("one dependence span, first-pass record and set of threshold views per chain")
+    peaks = [(r["starts"], r["ends"]) for r in first_pass]
+    return batch.dwb_peak_scoring(panel, bandwidths=spans, peaks=peaks, num_replay=min(int(num_replay), 64), random_seed=random_seed,
+                                  min_run_bins=min_run_bins, draws_per_group=draws_per_group)

@@ -7,7 +7,8 @@ thing is left to NumPy on the host: a view over the cap whose chosen set the val
 candidate score, or equal values at ranks cap and cap + 1) is answered with the reference's own two calls, np.argpartition and
 a mergesort by start, on that view's candidate scores and starts -- the only arrays fetched for it.  No CPU fallback otherwise.
 
-What stays with the caller: the empirical p and q values, merging with exported peaks, every string-valued field but the view key.
+What follows: the empirical p and q values and the merge with exported peaks are `consenrich_amd/peakscore.py`; every
+string-valued field but the view key stays with the caller.
 """
 from __future__ import annotations
 

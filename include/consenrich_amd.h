@@ -712,6 +712,65 @@ int csr_batch_rocco_excess_ranks(csr_ctx *ctx, const double *levels, const unsig
  * csr_batch_rocco of the batch. */
 int csr_batch_rocco_upload(csr_ctx *ctx, int32_t chain, const unsigned char *solution);
 
+/* ---- the numeric side of the DWB peak scoring: peaks.py:2295-2356 `_segmentScoreAgainstThresholdView` and
+ * `_bestSegmentScoreAcrossThresholdViews`, 2182-2203 `_empiricalReplaySegmentPValues`, 2206-2257 `_replayFDRQValues` ------------
+ * Every value equals the reference's bit for bit.
+ * Segment scores: n_seg segments [start, end] (inclusive; clamped to the track as the reference clamps them, end < start after
+ * that: an empty segment, all zeros, view 0) of one float64 track -- a host vector (default context), or a chain's resident score
+ * track, which is only read -- against n_views (threshold, null scale) pairs (1..16; null scales raised to DBL_MIN).  Per segment:
+ * the excess e = clip((s - threshold) / scale, 0, inf) of the best view, integrated = np.sum(e) in NumPy's summation order,
+ * score = integrated / sqrt(len), mean = integrated / len, max_excess = np.max(e), view = the index of that view.  The first view
+ * is the best and a later one replaces it only if its score compares > (a NaN score never replaces).
+ * p and q values: observed[n_metrics][K] statistics against pool[n_metrics][N], the statistics of all replay draws of a metric one
+ * after the other in any order, n_draws = how many draws there were (empty ones count; N > 0 needs n_draws > 0).  Both are
+ * sorted on the device (the null's keys-only sort); c = #(pool >= x) by bisection on `<`, so -0.0 and +0.0 are equal;
+ *   exceed_out = c,  p_out = clip((1 + c) / (N + 1), 0, 1)  (all ones when N == 0),
+ *   q_out = min over the observed y <= x of clip((c(y) / n_draws + pseudo) / max(#(observed >= y), 1), 0, 1),
+ *           pseudo = 1 / (n_draws + 1), or 1 without draws -- c(y) / n_draws is the mean of the per-draw counts the reference takes.
+ * what: CSR_PEAK_P and / or CSR_PEAK_Q; with CSR_PEAK_Q_MAX_P as well q_out = max(q, p), what the scorer keeps (peaks.py:2931-2940).
+ * A non-finite value is found on the device: err_flags (may be NULL) names where, and the call returns CSR_PEAK_ERR_VALUE with the
+ * reference's text before any result is written -- "replay segment statistics contain non-finite values" if p values were asked
+ * for and N > 0, else "replay FDR statistics contain non-finite values" if q values were.  Outputs not asked for may be NULL. */
+enum { CSR_PEAK_ERR_VALUE = CSR_ERR_VALUE };
+enum { CSR_PEAK_P = 1, CSR_PEAK_Q = 2, CSR_PEAK_Q_MAX_P = 4 };              /* what */
+enum { CSR_PEAK_BAD_OBSERVED = 1, CSR_PEAK_BAD_POOL = 2 };                  /* err_flags */
+int csr_peakscore_segments(const double *scores, int64_t n, int64_t n_seg, const int64_t *starts, const int64_t *ends,
+                           int32_t n_views, const double *thresholds, const double *null_scales, double *score, double *integrated,
+                           double *mean, double *max_excess, int32_t *view);
+int csr_batch_peakscore_segments(csr_ctx *ctx, int32_t chain, int64_t n_seg, const int64_t *starts, const int64_t *ends,
+                                 int32_t n_views, const double *thresholds, const double *null_scales, double *score,
+                                 double *integrated, double *mean, double *max_excess, int32_t *view);
+int csr_peakscore_pq(const double *observed, int64_t K, const double *pool, int64_t N, int64_t n_draws, int32_t n_metrics,
+                     int32_t what, double *p_out, double *q_out, int64_t *exceed_out, uint32_t *err_flags);
+/* The replay pool of a DWB panel (ctx NULL = the default context), valid between csr_dwb_panel_begin and csr_dwb_panel_end: per
+ * chain the three metric columns (score, integrated excess, max excess) of every replay candidate `compose` keeps, resident on
+ * the device -- the panel's own memory, freed by csr_dwb_panel_end (or csr_dwb_panel_pool_end).  max_segments: the total cap per
+ * draw (<= 0: none).  While a pool is open csr_dwb_panel_segments leaves its rows on the device (csr_segments_fetch fails; flagged
+ * views are resolved as usual), so run the observed tracks before pool_begin.  After each csr_dwb_panel_segments group, with its
+ * flagged views resolved, pool_append(first_draw) appends every (chain, draw) track of the group: a track over the total cap keeps
+ * the first max_segments rows of the stable descending order on score -- rank #(s[j] > s[i]) + #(s[j] == s[i], j < i), which is
+ * also the row's place in the pool -- and the pool grows by exactly what the group's row counts ask for.  *n_flagged: tracks over
+ * the cap that hold a NaN score, whose order the values do not determine.  pool_flagged names one (chain, draw, rows),
+ * pool_flagged_fetch returns its rows (the eight columns of csr_segments_fetch; the only replay rows that leave the device) and
+ * the caller hands back the max_segments candidates it kept with pool_flagged_upload, before the next group.  draw_stats, once
+ * every draw is in: per (chain, draw) the candidate count after and before the total cap, phase 1's three counters and np.max of
+ * the kept scores (0.0 without candidates); *fetched_tracks (may be NULL) = how many draws' rows were fetched.  pool_pq:
+ * csr_peakscore_pq of observed[3][K] (the pool's column order) against one chain's pool, n_draws = the panel's draws. */
+int csr_dwb_panel_pool_begin(csr_ctx *ctx, int64_t max_segments);
+int csr_dwb_panel_pool_append(csr_ctx *ctx, int32_t first_draw, int32_t *n_flagged);
+int csr_dwb_panel_pool_flagged(csr_ctx *ctx, int32_t k, int32_t *chain, int32_t *draw, int64_t *n_rows);
+int csr_dwb_panel_pool_flagged_fetch(csr_ctx *ctx, int32_t k, int64_t *start, int64_t *end, int64_t *scale, int64_t *view,
+                                     double *score, double *integrated, double *mean, double *max_excess);
+int csr_dwb_panel_pool_flagged_upload(csr_ctx *ctx, int32_t k, int64_t n_values, const double *score, const double *integrated,
+                                      const double *max_excess);
+int csr_dwb_panel_pool_draw_stats(csr_ctx *ctx, int64_t *count, int64_t *before, int64_t *counters, double *max_score,
+                                  int64_t *fetched_tracks);
+int csr_dwb_panel_pool_pq(csr_ctx *ctx, int32_t chain, const double *observed, int64_t K, int32_t what, double *p_out, double *q_out,
+                          int64_t *exceed_out, uint32_t *err_flags);
+/* A chain's pool as it stands: *n = values per column; the first *n of each column go to the non-NULL buffers. */
+int csr_dwb_panel_pool_download(csr_ctx *ctx, int32_t chain, int64_t *n, double *score, double *integrated, double *max_excess);
+int csr_dwb_panel_pool_end(csr_ctx *ctx);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
