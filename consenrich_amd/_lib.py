@@ -173,6 +173,28 @@ PEAK_P, PEAK_Q, PEAK_Q_MAX_P = 1, 2, 4
 PEAK_BAD_OBSERVED, PEAK_BAD_POOL = 1, 2
 
 
+class NestedRegion(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("chain", C.c_int32), ("min_run", C.c_int32)]
+
+
+class NestedCfg(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("selection_penalty", C.c_double), ("budget_scale", C.c_double),
+                ("subtract_floor", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NestedRec(C.Structure):
+    _fields_ = [("required", C.c_int64), ("selected_count", C.c_int64), ("child_base", C.c_int64), ("n_runs", C.c_int32),
+                ("decision", C.c_int32), ("widths_ok", C.c_int32), ("reserved", C.c_int32), ("floor", C.c_double),
+                ("selection_penalty", C.c_double), ("extra_penalty", C.c_double), ("objective", C.c_double),
+                ("penalized", C.c_double), ("boundary_penalty", C.c_double), ("run_penalty_total", C.c_double),
+                ("parent_penalized", C.c_double), ("split_gain", C.c_double)]
+
+
+class NestedNode(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("required", C.c_int64), ("raw_score_max", C.c_double),
+                ("score_sum", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
@@ -323,6 +345,16 @@ SYMBOLS = {
     "csr_dwb_panel_pool_pq": (C.c_int, [C.c_void_p, C.c_int32, DP, C.c_int64, C.c_int32, DP, DP, I64P, C.POINTER(C.c_uint32)]),
     "csr_dwb_panel_pool_download": (C.c_int, [C.c_void_p, C.c_int32, I64P, DP, DP, DP]),
     "csr_dwb_panel_pool_end": (C.c_int, [C.c_void_p]),
+    # (the nested record arrays travel as NumPy structured arrays of the same layout: consenrich_amd/nested.py)
+    "csr_nested_solve": (C.c_int, [DP, C.c_int64, DP, C.c_double, C.c_int32, C.c_int64, C.c_double, C.POINTER(C.c_uint8), C.c_void_p]),
+    "csr_nested_nodes": (C.c_int, [C.c_int32, I64P, DP, DP, C.c_int64, C.c_void_p, C.c_void_p]),
+    "csr_nested_layer": (C.c_int, [C.c_int32, I64P, DP, DP, C.POINTER(C.c_uint8), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   I64P]),
+    "csr_nested_children": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "csr_nested_selected_sum": (C.c_int, [C.c_int32, I64P, DP, I64P, I64P, I64P, DP]),
+    "csr_batch_nested_nodes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "csr_batch_nested_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, I64P]),
+    "csr_batch_nested_selected_sum": (C.c_int, [C.c_void_p, C.c_char_p, I64P, I64P, I64P, DP]),
 }
 
 _lib = None

@@ -48,6 +48,41 @@ _ARR = {"D": L.ARR_D, "xf": L.ARR_XF, "Pf": L.ARR_PF, "pnoise": L.ARR_PNOISE, "x
         "background_next": L.ARR_BACKGROUND_NEXT}
 
 
+class _NestedBackend:
+    """What consenrich_amd.nested.refine_chains needs of a batch: its resident scores and solution masks."""
+
+    def __init__(self, batch):
+        self.batch, self.lens = batch, np.asarray(batch.chain_lens, np.int64)
+        self._lib, self._ctx = batch._lib, batch._ctx
+
+    def initial_runs(self, chain):
+        return self.batch.rocco_runs(chain, 0)
+
+    def nodes(self, regions):
+        from . import nested as N
+
+        out = np.zeros(regions.size, N.NODE)
+        L.check_value(self._lib.csr_batch_nested_nodes(self._ctx, regions.size, N._vp(regions), N._vp(out)))
+        return out
+
+    def layer(self, cfg, take, regions):
+        from . import nested as N
+
+        rec, count = np.zeros(regions.size, N.REC), C.c_int64(0)
+        L.check_value(self._lib.csr_batch_nested_layer(self._ctx, N._vp(cfg), bytes(bytearray(int(t) for t in take)), regions.size,
+                                                       N._vp(regions), N._vp(rec), C.byref(count)))
+        kids = np.zeros(int(count.value), N.NODE)
+        L.check(self._lib.csr_nested_children(self._ctx, kids.size, N._vp(kids)))
+        return rec, kids
+
+    def selected_sums(self, take, n_runs, starts, ends):
+        out = np.zeros(len(self.lens), np.float64)
+        L.check_value(self._lib.csr_batch_nested_selected_sum(self._ctx, bytes(bytearray(int(t) for t in take)),
+                                                              n_runs.ctypes.data_as(L.I64P), starts.ctypes.data_as(L.I64P),
+                                                              ends.ctypes.data_as(L.I64P), L.dp(out)))
+        return out
+
+
 class DeviceBatch:
     """One GPU, many chains.  Thin, explicit wrapper: every method is one C-ABI call.
 
@@ -518,6 +553,64 @@ class DeviceBatch:
             cap = int(cnt.value)
         k = int(cnt.value)
         return starts[:k].copy(), ends[:k].copy()
+
+    def rocco_nested(self, gammas, selection_penalties, *, iters=3, budget_scale=0.75, jaccard_threshold=0.999, intervals=None,
+                     ends=None, min_region_bp=None, min_region_bins=5, chains=None):
+        """`_refineNestedROCCOSolution` (peaks.py:3763-4388) of the chains' RESIDENT scores and solution masks, all chains layer
+        by layer in the same calls.  gammas / selection_penalties: one value per chain (or one for all) -- the first pass's.
+        intervals / ends: None (bin mode), or per chain the bins' start / end coordinates (host arrays; an entry may be None).
+        The refined mask REPLACES the chain's resident solution: rocco_solution, rocco_runs, best_segment_scores and
+        dwb_peak_scoring (which take a chain's runs) see it; segment_candidates reads the score tracks only and is unaffected.
+        A minimum child run above 255 bins is refused with ValueError before any launch (with mixed bin widths by a bound:
+        ceil(min_region_bp / the smallest positive width inside a first-pass run)), so the masks are never left partly refined.  chains: optional per-chain booleans; a chain with False keeps its mask.  The scores and the
+        arrays of the fit are only read.  Returns the reference's `details` per chain (None where not taken).  The device does
+        the per-region and per-node arithmetic; the hierarchy, the stop rule and the geometry are decided on the host from compact
+        records (consenrich_amd/nested.py)."""
+        from . import nested as N
+
+        take, _ = self._chain_mask(chains)
+        nc = len(take)
+
+        def per_chain(v):
+            if isinstance(v, (list, tuple, np.ndarray)):
+                if len(v) != nc:
+                    raise ValueError("one value per chain")
+                return list(v)
+            return [v] * nc
+
+        g, p = per_chain(gammas), per_chain(selection_penalties)
+        iv = [None] * nc if intervals is None else list(intervals)
+        en = [None] * nc if ends is None else list(ends)
+        if len(iv) != nc or len(en) != nc:
+            raise ValueError("one intervals / ends entry per chain")
+        state = [N._Chain(i, self.chain_lens[i], g[i], p[i], iters, budget_scale, jaccard_threshold, iv[i], en[i], min_region_bp,
+                          min_region_bins) for i in range(nc) if take[i]]
+        details = N.refine_chains(_NestedBackend(self), state)
+        out = [None] * nc
+        for ch, d in zip(state, details):
+            out[ch.index] = d
+            self._rocco_count[ch.index] = int(d["final_selected_count"])
+        return out
+
+    def rocco_objective(self, gammas, chains=None):
+        """`_roccoObjectiveForSolution` (peaks.py:2017-2031) of every chain's resident mask and scores: np.sum of the selected
+        scores in NumPy's order (on the device) minus max(gamma, 0) times the number of switches.  One float per chain (None where
+        not taken)."""
+        from . import nested as N
+
+        take, _ = self._chain_mask(chains)
+        nc = len(take)
+        g = list(gammas) if isinstance(gammas, (list, tuple, np.ndarray)) else [gammas] * nc
+        if len(g) != nc:
+            raise ValueError("one value per chain")
+        runs = {c: self.rocco_runs(c, 0) for c in range(nc) if take[c]}
+        n_runs = np.asarray([runs[c][0].size if take[c] else 0 for c in range(nc)], np.int64)
+        starts = np.ascontiguousarray(np.concatenate([runs[c][0] for c in range(nc) if take[c]] + [np.zeros(0, np.int64)]), np.int64)
+        ends = np.ascontiguousarray(np.concatenate([runs[c][1] for c in range(nc) if take[c]] + [np.zeros(0, np.int64)]), np.int64)
+        sums = _NestedBackend(self).selected_sums(take, n_runs, starts, ends)
+        return [None if not take[c] else
+                N.rocco_objective(float(sums[c]), list(zip(runs[c][0].tolist(), runs[c][1].tolist())), self.chain_lens[c], float(g[c]))
+                for c in range(nc)]
 
     def set_rocco_depth(self, depth: int = 0):
         """Speculation depth D of the penalty calibration (1..8, 0 = default 6).  Changes speed only."""

@@ -273,7 +273,7 @@ __device__ __forceinline__ double dwb_excess(double x, double off, double s) {
 // NumPy's pairwise sum of f(x[i]) over a block of 8 <= n <= 128 values (eight strided accumulators, then the remainder in order)
 // or of n < 8 values (in order); f is evaluated once per element, in the order NumPy adds them
 template <class F>
-__device__ __forceinline__ double dwb_leaf_f(const double *x, int n, F &f) {
+__host__ __device__ __forceinline__ double dwb_leaf_f(const double *x, int n, F &f) {
     if (n < 8) {
         double res = 0.0;
         for (int i = 0; i < n; ++i) res = res + f(x[i]);
@@ -293,7 +293,7 @@ __device__ __forceinline__ double dwb_leaf_f(const double *x, int n, F &f) {
 }
 // the pairwise tree of one chunk (n <= DWB_CHUNK): blocks above 128 values split at n/2 - (n/2) % 8
 template <class F>
-__device__ double dwb_chunk_sum_f(const double *x, int n, F &f) {
+__host__ __device__ inline double dwb_chunk_sum_f(const double *x, int n, F &f) {
     int lo[12], len[12], stage[12];
     double left[12];
     int sp = 0;

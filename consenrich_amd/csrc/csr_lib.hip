@@ -16,6 +16,7 @@
 #include "csr_segments.h"
 #include "csr_ess.h"
 #include "csr_peakscore.h"
+#include "csr_nested.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
 
@@ -444,6 +445,13 @@ struct csr_ctx : BatchState {
         DevBuf work, arena, runBuf;
         csr_rocco_stats stats{};
     } roccoWs;
+    // nested ROCCO refinement (csr_host_nested.inl): growable work space of a call -- the staged host arrays, the job / parameter /
+    // order tables, one double and one mask byte per bin, back-pointer words, per-region state and records, and the candidate runs
+    // of the last layer, which stay until the next one so that the caller can fetch them
+    struct NestedWs {
+        DevBuf arena, jobBuf, work, wm, bt, st, rec, kids, part, costs;
+        int64_t nKids = 0;
+    } nestedWs;
     // stationary-null DWB panel (csr_host_dwb.inl): chain table, weights, templates, the seed's noise stream and the rows of one
     // group of draws; growable, the large ones given back by csr_dwb_panel_end
     struct Dwb {
@@ -896,3 +904,4 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_segments.inl"
 #include "csr_host_ess.inl"
 #include "csr_host_peakscore.inl"
+#include "csr_host_nested.inl"

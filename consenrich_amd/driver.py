@@ -637,6 +637,41 @@ def first_pass_peaks_batch(batch: DeviceBatch, *, dependence_spans, threshold_z,
     return res
 
 
+def nested_peaks_batch(batch: DeviceBatch, first_pass, *, interval_bp, intervals=None, ends=None, iters: int = 3,
+                       budget_scale: float = 0.75, jaccard_threshold: float = 0.999, max_gap_bins: int = 0) -> List[dict]:
+    """The link between `first_pass_peaks_batch` and `score_peaks_batch`: the reference's nested refinement of every chain's
+    first-pass solution (`solveRocco`, peaks.py:6827-6852 -> `_refineNestedROCCOSolution`), on the device from the resident scores
+    and masks (`DeviceBatch.rocco_nested`).  gamma and selection_penalty are each chain's first-pass values; minRegionBP is
+    5 * interval_bp and minRegionBins 5, as `solveRocco` sets them.  intervals / ends: per chain the bins' coordinates (None: bins
+    of interval_bp starting at 0).  Returns a copy of every first-pass record with `starts` / `ends` of the REFINED mask, plus
+    first_pass_selected_count, final_selected_count, nested_rocco_stop_reason, nested_rocco (the reference's details) and
+    `objective` = `_roccoObjectiveForSolution` of the refined mask -- accepted by `score_peaks_batch` in place of first_pass."""
+    nc = len(batch.chain_lens)
+    if len(first_pass) != nc:
+        raise ValueError("one first-pass record per chain")
+    step = int(interval_bp)
+    if intervals is None:
+        intervals = [np.arange(n, dtype=np.int64) * step for n in batch.chain_lens]
+        ends = [iv + step for iv in intervals]
+    details = batch.rocco_nested([r["gamma"] for r in first_pass], [r["selection_penalty"] for r in first_pass], iters=iters,
+                                 budget_scale=budget_scale, jaccard_threshold=jaccard_threshold, intervals=intervals, ends=ends,
+                                 min_region_bp=5 * step, min_region_bins=5)
+    out = []
+    # (without a layer -- iters = 0 -- there is no history record to take the objective from)
+    plain = [not d["history"] for d in details]
+    objective = batch.rocco_objective([r["gamma"] for r in first_pass], chains=plain) if any(plain) else [None] * nc
+    for ch, (r, d) in enumerate(zip(first_pass, details)):
+        q = dict(r)
+        q["first_pass_selected_count"] = int(d["initial_selected_count"])
+        q["final_selected_count"] = q["selected_count"] = int(d["final_selected_count"])
+        q["nested_rocco_stop_reason"] = d["stop_reason"]
+        q["nested_rocco"] = d
+        q["objective"] = float(d["history"][-1]["objective"]) if d["history"] else float(objective[ch])
+        q["starts"], q["ends"] = batch.rocco_runs(ch, max_gap_bins)
+        out.append(q)
+    return out
+
+
 def score_peaks_batch(batch: DeviceBatch, first_pass, panel, *, dependence_spans, random_seed, min_run_bins: int = 1,
                       num_replay: int = 64, draws_per_group: int = 0) -> List[dict]:
     """The next link after `first_pass_peaks_batch`: the reference's DWB peak scoring (`_addDWBPeakScoringToPeakMeta`,

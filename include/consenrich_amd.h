@@ -771,6 +771,67 @@ int csr_dwb_panel_pool_pq(csr_ctx *ctx, int32_t chain, const double *observed, i
 int csr_dwb_panel_pool_download(csr_ctx *ctx, int32_t chain, int64_t *n, double *score, double *integrated, double *max_excess);
 int csr_dwb_panel_pool_end(csr_ctx *ctx);
 
+/* ---- nested ROCCO refinement: peaks.py:3519-3720 `_solveParentConditionedSubpeaks`, 2133-2160
+ * `_parentConditionedSubpeakObjective`, 2089-2114 `_nestedSoftSelectionPenalty`, and what `_refineNestedROCCOSolution`
+ * (peaks.py:3763-4388) does per region, per new node and per layer -----------------------------------------------------------
+ * Every value equals the reference's bit for bit.  The device works on regions: bins [start, end] (inclusive) of one chain,
+ * given in ascending order of (chain, start) and disjoint.  The hierarchy (node ids, layers, history, the stop rule) and the
+ * geometry (which regions are too short, `_minimumChildBinsForRegion`) are the caller's: they need intervals / ends, which are
+ * host arrays, and compact records only.
+ *   nodes          per region what `_addNode` records: the leftmost arg-max of the raw scores, that raw score, np.sum of the scores.
+ *   layer          per region peaks.py:4042-4172: required bin, the 25 % floor (cfg.subtract_floor: layers >= 2), the soft selection
+ *                  penalty (cfg.selection_penalty and cfg.budget_scale are the LAYER's: 0 and 1 from layer 2 on), the dynamic
+ *                  programme with min_run + 1 states, both objectives, split gain, gates and decision.  A region that splits or
+ *                  shrinks has its bins of the solution mask replaced.  *n_children = the candidate runs of all regions; region
+ *                  k's are children[rec[k].child_base .. + rec[k].n_runs), each a node record, fetched with csr_nested_children
+ *                  (ctx NULL = the default context of the host-array calls) until the next layer call of that context.
+ *   selected_sum   per chain np.sum(scores[mask > 0]) for the mask that is the union of the given runs (n_runs[chain] of them,
+ *                  ascending and disjoint, concatenated in starts / ends): the float part of `_roccoObjectiveForSolution`.
+ *   solve          one region with general boundary costs (n + 1 of them), a required bin or none (-1): the mask and the record.
+ * min_run is clamped to the region's length; above CSR_NESTED_MAX_MIN_RUN the call returns CSR_ERR_VALUE.  Arguments the
+ * reference answers with ValueError return CSR_ERR_VALUE with its text, before any launch.  The host-array calls take the
+ * chains one after the other (chain_len[n_chains], scores, raw_scores or NULL for the scores themselves, solution in and out); the
+ * batch calls read the resident score tracks and read and write the resident solution masks of the chains chain_mask takes
+ * (NULL: all; a region of a chain it leaves out is an error), and change no other resident array. */
+enum { CSR_NESTED_KEEP_PARENT = 0, CSR_NESTED_SPLIT = 1, CSR_NESTED_SHRINK = 2, CSR_NESTED_INFEASIBLE = -1 };   /* decision */
+#define CSR_NESTED_MAX_MIN_RUN 255
+typedef struct csr_nested_region {
+    int64_t start, end;
+    int32_t chain, min_run;
+} csr_nested_region;
+typedef struct csr_nested_cfg {     /* per chain and layer */
+    double gamma;               /* the PARENT's gamma: an inner boundary costs max(0.25 gamma, 1e-9) */
+    double selection_penalty, budget_scale;
+    int32_t subtract_floor, reserved;
+} csr_nested_cfg;
+typedef struct csr_nested_rec {     /* per region */
+    int64_t required;           /* the required bin, as an index of the chain (-1: none) */
+    int64_t selected_count;
+    int64_t child_base;
+    int32_t n_runs, decision, widths_ok, reserved;
+    double floor, selection_penalty, extra_penalty;
+    double objective, penalized, boundary_penalty, run_penalty_total, parent_penalized, split_gain;
+} csr_nested_rec;
+typedef struct csr_nested_node {
+    int64_t start, end, required;   /* indices of the chain */
+    double raw_score_max, score_sum;
+} csr_nested_node;
+int csr_nested_solve(const double *scores, int64_t n, const double *boundary_costs, double selection_penalty, int32_t min_run,
+                     int64_t required, double run_penalty, uint8_t *mask, csr_nested_rec *out);
+int csr_nested_nodes(int32_t n_chains, const int64_t *chain_len, const double *scores, const double *raw_scores, int64_t n_regions,
+                     const csr_nested_region *regions, csr_nested_node *nodes);
+int csr_nested_layer(int32_t n_chains, const int64_t *chain_len, const double *scores, const double *raw_scores, uint8_t *solution,
+                     const csr_nested_cfg *cfg, int64_t n_regions, const csr_nested_region *regions, csr_nested_rec *rec,
+                     int64_t *n_children);
+int csr_nested_children(csr_ctx *ctx, int64_t capacity, csr_nested_node *children);
+int csr_nested_selected_sum(int32_t n_chains, const int64_t *chain_len, const double *scores, const int64_t *n_runs,
+                            const int64_t *starts, const int64_t *ends, double *sums);
+int csr_batch_nested_nodes(csr_ctx *ctx, int64_t n_regions, const csr_nested_region *regions, csr_nested_node *nodes);
+int csr_batch_nested_layer(csr_ctx *ctx, const csr_nested_cfg *cfg, const unsigned char *chain_mask, int64_t n_regions,
+                           const csr_nested_region *regions, csr_nested_rec *rec, int64_t *n_children);
+int csr_batch_nested_selected_sum(csr_ctx *ctx, const unsigned char *chain_mask, const int64_t *n_runs, const int64_t *starts,
+                                  const int64_t *ends, double *sums);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
