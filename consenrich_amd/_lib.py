@@ -195,6 +195,26 @@ class NestedNode(C.Structure):
                 ("score_sum", C.c_double)]
 
 
+EXPORT_SPLIT_FROM_PARENT, EXPORT_TRIMMED, EXPORT_HAS_LOCAL_P, EXPORT_DROPPED_MEDIAN = 1, 2, 4, 8
+EXPORT_NONFINITE_SIGNAL = 1
+
+
+class ExportCfg(C.Structure):
+    _fields_ = [("selection_penalty", C.c_double), ("boundary_cost", C.c_double), ("trim_floor", C.c_double),
+                ("multiplier", C.c_double), ("min_run", C.c_int32), ("split", C.c_int32), ("trim", C.c_int32), ("filter", C.c_int32)]
+
+
+class ExportParent(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("chain", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ExportPeak(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("untrimmed_start", C.c_int64), ("untrimmed_end", C.c_int64),
+                ("summit", C.c_int64), ("chain", C.c_int32), ("parent", C.c_int32), ("num_subpeaks", C.c_int32),
+                ("flags", C.c_int32), ("median_state", C.c_double), ("local_median_p", C.c_double), ("max_state", C.c_double),
+                ("max_score", C.c_double), ("subpeak_objective", C.c_double), ("subpeak_boundary_penalty", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
@@ -355,6 +375,10 @@ SYMBOLS = {
     "csr_batch_nested_nodes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "csr_batch_nested_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, I64P]),
     "csr_batch_nested_selected_sum": (C.c_int, [C.c_void_p, C.c_char_p, I64P, I64P, I64P, DP]),
+    # (the export record arrays are NumPy structured arrays too: consenrich_amd/narrowpeak.py)
+    "csr_export_peaks": (C.c_int, [C.c_int32, I64P, DP, DP, DP, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, I64P]),
+    "csr_batch_export_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, I64P]),
+    "csr_export_fetch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

@@ -592,6 +592,93 @@ class DeviceBatch:
             self._rocco_count[ch.index] = int(d["final_selected_count"])
         return out
 
+    def narrowpeak_rows(self, selection_penalties, gammas, *, intervals=None, ends=None, interval_bp=None, chroms=None,
+                        prefix="consenrich", min_subpeak_bins=5, trim_score_floor=0.0, multiplier=2.0, use_uncertainty=True,
+                        chains=None, split_subpeaks=True):
+        """The reference's first-pass narrowPeak rows (`_solutionToChromNarrowPeakRows`, peaks.py:5202-5567, without a width policy
+        and without a hierarchy) of every chain's RESIDENT mask, in one device call for all parents of all chains: sub-peaks of
+        every run with the min-run dynamic programme (selection penalty = the chain's, boundary cost = 0.25 gamma,
+        `min_subpeak_bins`), the trim around each summit, the medians, the maxima and the median filter.  The device reads the
+        resident score tracks, as signal float64 of xs[:,0] and as uncertainty the float32 square root of Ps00 (use_uncertainty) of
+        the smoothed fit; no resident array changes.  intervals / ends: per chain the bins' coordinates (None: bins of interval_bp
+        starting at 0); chroms: the chains' names (None: "chain<i>").  The host cuts the runs at coordinate gaps and does the
+        coordinate work from compact records (consenrich_amd/narrowpeak.py).  A chain with a non-finite signal value inside a
+        selected run has its signal-dependent numbers redone with NumPy on its downloaded tracks (`decided_on_host`).  Returns per
+        chain (None where not taken) a dict: rows, peak_meta, export_details, decided_on_host; `narrowpeak_stats` holds the last
+        call's counts and its time on the device and in all."""
+        import time
+
+        from . import narrowpeak as P
+
+        t_start = time.perf_counter()
+        take, mask = self._chain_mask(chains)
+        nc = len(take)
+
+        def per_chain(v):
+            if isinstance(v, (list, tuple, np.ndarray)):
+                if len(v) != nc:
+                    raise ValueError("one value per chain")
+                return list(v)
+            return [v] * nc
+
+        pen, gam = per_chain(selection_penalties), per_chain(gammas)
+        mult = P.validate_multiplier(multiplier)
+        names = [f"chain{i}" for i in range(nc)] if chroms is None else [str(c) for c in chroms]
+        iv = [None] * nc if intervals is None else list(intervals)
+        en = [None] * nc if ends is None else list(ends)
+        if len(iv) != nc or len(en) != nc or len(names) != nc:
+            raise ValueError("one intervals / ends / chroms entry per chain")
+        cfg = np.zeros(nc, P.CFG)
+        parents, spans, details = [], [], [None] * nc
+        for c in range(nc):
+            if not take[c]:
+                continue
+            n = self.chain_lens[c]
+            if iv[c] is None or en[c] is None:
+                if iv[c] is not None or en[c] is not None:
+                    raise ValueError("`intervals` and `ends` must be supplied together")
+                if interval_bp is None:
+                    raise ValueError("`interval_bp` is needed where no coordinates are given")
+                iv[c] = np.arange(n, dtype=np.int64) * int(interval_bp)
+                en[c] = iv[c] + int(interval_bp)
+            iv[c] = np.asarray(iv[c], dtype=np.int64).ravel()
+            en[c] = np.asarray(en[c], dtype=np.int64).ravel()
+            if iv[c].size != n or en[c].size != n:
+                raise ValueError("`intervals`, `ends`, `state`, `scores`, and `solution` must match length")
+            cfg[c] = P.chain_cfg(pen[c], 0.25 * float(gam[c]), trim_score_floor, mult, min_subpeak_bins, split_subpeaks, use_uncertainty)
+            details[c] = P.export_details(mult, bool(use_uncertainty))
+            ps, pe, cuts = P.cut_parents(*self.rocco_runs(c, 0), iv[c], en[c])
+            details[c]["num_coordinate_gap_splits"] = cuts
+            spans.append((c, len(parents), len(parents) + ps.size))
+            parents += [(a, b, c, 0) for a, b in zip(ps.tolist(), pe.tolist())]
+        par = np.asarray(parents, P.PARENT) if parents else np.zeros(0, P.PARENT)
+        flags = np.zeros(par.size, np.int32)
+        count = C.c_int64(0)
+        t_device = time.perf_counter()
+        L.check_value(self._lib.csr_batch_export_peaks(self._ctx, P._vp(cfg), mask, par.size, P._vp(par), P._vp(flags), C.byref(count)))
+        peaks = np.zeros(int(count.value), P.PEAK)
+        L.check(self._lib.csr_export_fetch(self._ctx, peaks.size, P._vp(peaks)))
+        t_device = time.perf_counter() - t_device
+        first = np.searchsorted(peaks["parent"], np.arange(par.size + 1), "left")      # (the peaks come in parent order)
+        out = [None] * nc
+        stats = {"chains": len(spans), "parents": int(par.size), "peaks": int(peaks.size), "decided_on_host": 0}
+        for c, a, b in spans:
+            mine = peaks[first[a]:first[b]]
+            host = bool(np.any(flags[a:b] & L.EXPORT_NONFINITE_SIGNAL))
+            if host:
+                state = self.download(c, "xs")[:, 0].astype(np.float64)
+                unc = np.sqrt(self.download(c, "Ps")[:, 0, 0]).astype(np.float64) if use_uncertainty else None
+                with np.errstate(invalid="ignore"):
+                    P.redo_on_host(mine, state, self.download_scores(c), unc, cfg[c])
+                stats["decided_on_host"] += 1
+            rows, meta = P.assemble(names[c], iv[c], en[c], prefix, mine, mult, trim_score_floor, details[c])
+            out[c] = {"rows": rows, "peak_meta": meta, "export_details": details[c], "decided_on_host": host}
+        # (device_seconds: the library call and the fetch of the records; the rest is the host's share: runs, gaps, assembly)
+        stats["device_seconds"] = t_device
+        stats["seconds"] = time.perf_counter() - t_start
+        self.narrowpeak_stats = stats
+        return out
+
     def rocco_objective(self, gammas, chains=None):
         """`_roccoObjectiveForSolution` (peaks.py:2017-2031) of every chain's resident mask and scores: np.sum of the selected
         scores in NumPy's order (on the device) minus max(gamma, 0) times the number of switches.  One float per chain (None where

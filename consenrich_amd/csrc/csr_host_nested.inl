@@ -49,6 +49,8 @@ static int nested_jobs(const NestedLay &L, int64_t nr, const csr_nested_region *
         jb.costs = nullptr;
         jb.minRun = (int32_t)m;
         jb.chain = r.chain;
+        jb.uniform = 0;
+        jb.reserved = 0;
         words += (n + NESTED_WORD - 1) / NESTED_WORD;
     }
     return 0;

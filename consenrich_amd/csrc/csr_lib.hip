@@ -17,6 +17,7 @@
 #include "csr_ess.h"
 #include "csr_peakscore.h"
 #include "csr_nested.h"
+#include "csr_export.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
 
@@ -452,6 +453,12 @@ struct csr_ctx : BatchState {
         DevBuf arena, jobBuf, work, wm, bt, st, rec, kids, part, costs;
         int64_t nKids = 0;
     } nestedWs;
+    // narrowPeak export (csr_host_export.inl): the staged host tracks, the parent records, the first peak of every parent and the
+    // peaks of the last call, which stay until the next one so that the caller can fetch them; the rest is nestedWs
+    struct ExportWs {
+        DevBuf arena, par, base, peaks;
+        int64_t nPeaks = 0;
+    } exportWs;
     // stationary-null DWB panel (csr_host_dwb.inl): chain table, weights, templates, the seed's noise stream and the rows of one
     // group of draws; growable, the large ones given back by csr_dwb_panel_end
     struct Dwb {
@@ -905,3 +912,4 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_ess.inl"
 #include "csr_host_peakscore.inl"
 #include "csr_host_nested.inl"
+#include "csr_host_export.inl"

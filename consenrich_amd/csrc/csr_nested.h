@@ -50,6 +50,8 @@ struct NestedJob {
     const double *costs;    // solve mode: n + 1 boundary costs; layer mode: nullptr (edge / internal)
     int32_t minRun;         // already clamped to [1, n]
     int32_t chain;          // row of the parameter table
+    int32_t uniform;        // export mode (csr_export.h): `internal` is the cost of all n + 1 boundaries, the outer ones included
+    int32_t reserved;
 };
 struct NestedChain {
     double internal;        // max(0.25 gamma, 1000 edge): cost of an inner boundary, and the run penalty
@@ -88,6 +90,7 @@ CSR_HD bool nested_better(double v, int c, double bv, int bc) {
 }
 CSR_HD double nested_cost(const NestedJob &jb, double internal, int64_t i) {
     if (jb.costs) return jb.costs[i];
+    if (jb.uniform) return internal;
     return (i == 0 || i == jb.n) ? NESTED_EDGE : internal;
 }
 struct NestedShift {

@@ -672,6 +672,32 @@ def nested_peaks_batch(batch: DeviceBatch, first_pass, *, interval_bp, intervals
     return out
 
 
+def export_peaks_batch(batch: DeviceBatch, nested, *, interval_bp, intervals=None, ends=None, chroms=None, prefix="consenrich",
+                       multiplier: float = 2.0, use_uncertainty: bool = True) -> List[dict]:
+    """The link between `nested_peaks_batch` and `score_peaks_batch`: what the reference exports and then scores is not the refined
+    mask's runs but what `_solutionToChromNarrowPeakRows` makes of them (`solveRocco`, peaks.py:6987-7006): runs broken at coordinate
+    gaps, split into sub-peaks, trimmed around their summits, filtered by the median test and the 200 bp minimum.  On the device
+    from the resident scores, masks and smoothed fit (`DeviceBatch.narrowpeak_rows`), with the arguments `solveRocco` passes:
+    subpeakSelectionPenalty = the chain's selection_penalty, subpeakBoundaryCost = 0.25 gamma, minSubpeakBins 5, trimScoreFloor 0.
+    nested: what nested_peaks_batch (or first_pass_peaks_batch) returned.  intervals / ends: per chain the bins' coordinates (None:
+    bins of interval_bp starting at 0).  Returns a copy of every record with `rows`, `peak_meta`, `export_details`,
+    `decided_on_host`, and `starts` / `ends` = the KEPT peaks' start_idx / end_idx -- accepted by `score_peaks_batch` unchanged."""
+    nc = len(batch.chain_lens)
+    if len(nested) != nc:
+        raise ValueError("one record per chain")
+    got = batch.narrowpeak_rows([r["selection_penalty"] for r in nested], [r["gamma"] for r in nested], intervals=intervals, ends=ends,
+                                interval_bp=interval_bp, chroms=chroms, prefix=prefix, min_subpeak_bins=5, trim_score_floor=0.0,
+                                multiplier=multiplier, use_uncertainty=use_uncertainty)
+    out = []
+    for r, g in zip(nested, got):
+        q = dict(r)
+        q.update(rows=g["rows"], peak_meta=g["peak_meta"], export_details=g["export_details"], decided_on_host=g["decided_on_host"])
+        q["starts"] = np.asarray([m["start_idx"] for m in g["peak_meta"]], np.int64)
+        q["ends"] = np.asarray([m["end_idx"] for m in g["peak_meta"]], np.int64)
+        out.append(q)
+    return out
+
+
 def score_peaks_batch(batch: DeviceBatch, first_pass, panel, *, dependence_spans, random_seed, min_run_bins: int = 1,
                       num_replay: int = 64, draws_per_group: int = 0) -> List[dict]:
     """The next link after `first_pass_peaks_batch`: the reference's DWB peak scoring (`_addDWBPeakScoringToPeakMeta`,

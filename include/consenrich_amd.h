@@ -832,6 +832,55 @@ int csr_batch_nested_layer(csr_ctx *ctx, const csr_nested_cfg *cfg, const unsign
 int csr_batch_nested_selected_sum(csr_ctx *ctx, const unsigned char *chain_mask, const int64_t *n_runs, const int64_t *starts,
                                   const int64_t *ends, double *sums);
 
+/* ---- narrowPeak export: the numeric part of `_solutionToChromNarrowPeakRows` (peaks.py:5202-5567) without a width policy and
+ * without a hierarchy -- `_solveParentConditionedSubpeakSegments` (4507-4576), `_trimChildSegmentAroundSummit` (4789-4824), the
+ * two medians, the two maxima and the median filter ------------------------------------------------------------------------
+ * Every value equals the reference's bit for bit.  A PARENT is a run of the solution mask that holds no coordinate gap: bins
+ * [start, end] (inclusive) of one chain, ascending by (chain, start) and disjoint; cutting the mask's runs at gaps is the
+ * caller's (it needs the coordinates).  Per parent (cfg.split): the required bin is the leftmost arg-max of the scores, the
+ * dynamic programme of the nested layer runs with max(boundary_cost, 0) on ALL n + 1 boundaries, the given selection penalty,
+ * min(max(min_run, 1), n) and no run penalty; its runs are the children, each with the parent's number of sub-peaks, penalized
+ * objective and boundary penalty.  Without cfg.split the parent is its only child.  Per child: the summit (leftmost arg-max
+ * of the signal over the untrimmed child), the trim (cfg.trim: the maximal stretch of scores > trim_floor around the summit,
+ * none if the summit's score is not above it), and over the trimmed child np.median and np.max of the signal, np.max of the
+ * scores, np.median of the finite uncertainty values (cfg.filter; CSR_EXPORT_HAS_LOCAL_P if there is one) and the flag
+ * median < -multiplier * that median (CSR_EXPORT_DROPPED_MEDIAN: the child still comes back, the caller counts it).
+ * *count = the children of all parents; csr_export_fetch hands them out in the reference's order (chain, parent, child from
+ * left to right; ctx NULL = the default context of the host-array call) until the next export call of that context.
+ * parent_flags (n_parents, may be NULL): CSR_EXPORT_NONFINITE_SIGNAL where the signal of a parent holds a non-finite value --
+ * NumPy's maxima and medians then propagate NaN in ways no order statistic does; the caller decides such a chain on the host.
+ * Non-finite scores inside a parent, a non-finite penalty, boundary cost or multiplier and a negative multiplier return
+ * CSR_ERR_VALUE with the reference's text, a minimum run above CSR_NESTED_MAX_MIN_RUN the same CSR_ERR_VALUE as the nested
+ * calls; the host-array call checks before any launch, the batch call finds non-finite resident scores in its first kernel and
+ * ends there.  The host-array call takes float64 state / scores / uncertainty (NULL: none), the chains one after the other.  The
+ * batch call reads the resident score tracks, as signal (double) xs[:,0] and as uncertainty (double)(float) sqrt(Ps00) of the
+ * reference-layout copies of the smoothed fit -- the values and the side-effect rule of csr_batch_rocco_scores -- and changes no
+ * resident array of the fit, score, mask or template.  Additive to ABI 6. */
+enum { CSR_EXPORT_SPLIT_FROM_PARENT = 1, CSR_EXPORT_TRIMMED = 2, CSR_EXPORT_HAS_LOCAL_P = 4, CSR_EXPORT_DROPPED_MEDIAN = 8 };
+enum { CSR_EXPORT_NONFINITE_SIGNAL = 1 };
+typedef struct csr_export_cfg {     /* per chain */
+    double selection_penalty, boundary_cost, trim_floor, multiplier;
+    int32_t min_run;            /* minSubpeakBins; clamped to [1, n] per parent */
+    int32_t split, trim, filter;    /* switches: sub-peaks; trim (off: floor None or non-finite); the median filter */
+} csr_export_cfg;
+typedef struct csr_export_parent {
+    int64_t start, end;
+    int32_t chain, reserved;
+} csr_export_parent;
+typedef struct csr_export_peak {
+    int64_t start, end;                         /* the trimmed child, indices of the chain */
+    int64_t untrimmed_start, untrimmed_end, summit;
+    int32_t chain, parent;                      /* parent: index into the call's parent list */
+    int32_t num_subpeaks, flags;
+    double median_state, local_median_p, max_state, max_score, subpeak_objective, subpeak_boundary_penalty;
+} csr_export_peak;
+int csr_export_peaks(int32_t n_chains, const int64_t *chain_len, const double *state, const double *scores,
+                     const double *uncertainty, const csr_export_cfg *cfg, int64_t n_parents, const csr_export_parent *parents,
+                     int32_t *parent_flags, int64_t *count);
+int csr_batch_export_peaks(csr_ctx *ctx, const csr_export_cfg *cfg, const unsigned char *chain_mask, int64_t n_parents,
+                           const csr_export_parent *parents, int32_t *parent_flags, int64_t *count);
+int csr_export_fetch(csr_ctx *ctx, int64_t capacity, csr_export_peak *peaks);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
