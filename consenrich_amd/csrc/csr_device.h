@@ -307,10 +307,17 @@ struct BinStats {
     double s0, zbar, s2c, logr;
 };
 
+// weight 1/R of one cell.  An infinite variance ("no observation") weighs exactly 0, as the reference's division gives it:
+// v_rcp_f64 returns 0 for it, and the Newton steps of rcp_nr would turn that into NaN (fma(-inf, 0, 1)).  A NaN stays NaN.
+__device__ __forceinline__ double obs_weight(double R) {
+    const double w = rcp_nr(R);
+    return R == __builtin_huge_val() ? 0.0 : w;
+}
+
 // One pass over the m samples (register-light, so 8 waves/SIMD hide the HBM latency): weighted sums about the
 // pivot z_0 (first sample), then zbar = z_0 + A/S0 and S2c = B - A^2/S0.  The shift keeps the cancellation in B - A^2/S0
 // at (z_0 - zbar)^2 / var, i.e. a relative error of ~1e-16 * that ratio -- >= 8 digits of headroom to the 1e-5 budget
-// even for a 10^4-sigma pivot.  1/R uses v_rcp_f64 + two Newton steps (<= 1 ulp).
+// even for a 10^4-sigma pivot.  1/R uses v_rcp_f64 + two Newton steps (<= 1 ulp; obs_weight).
 // UN = sample rows loaded together (2 * UN loads in flight per thread)
 template <int UN = 8>
 __device__ __forceinline__ BinStats bin_stats(const float *__restrict__ data, const float *__restrict__ munc,
@@ -332,7 +339,7 @@ __device__ __forceinline__ BinStats bin_stats(const float *__restrict__ data, co
         for (int u = 0; u < UN; ++u) {
             double R = (double)v[u] + pad;
             if (R < 1.0e-12) R = 1.0e-12;
-            const double w = rcp_nr(R);
+            const double w = obs_weight(R);
             const double dz = (double)z[u] - piv;
             s0 += w;
             A = fma(w, dz, A);
@@ -348,7 +355,7 @@ __device__ __forceinline__ BinStats bin_stats(const float *__restrict__ data, co
     for (; j < m; ++j) {
         double R = (double)mp[(int64_t)j * stride] + pad;
         if (R < 1.0e-12) R = 1.0e-12;
-        const double w = rcp_nr(R);
+        const double w = obs_weight(R);
         const double dz = (double)(dp[(int64_t)j * stride] - bgv) - piv;
         s0 += w;
         A = fma(w, dz, A);
@@ -395,7 +402,7 @@ __device__ __forceinline__ void bin_stats4(const float *__restrict__ data, const
             for (int q = 0; q < 4; ++q) {
                 double R = (double)vv[q] + pad;
                 if (R < 1.0e-12) R = 1.0e-12;
-                const double w = rcp_nr(R);
+                const double w = obs_weight(R);
                 const double dz = (double)(zz[q] - bgv[q]) - piv[q];
                 s0[q] += w;
                 A[q] = fma(w, dz, A[q]);
@@ -422,7 +429,7 @@ __device__ __forceinline__ void bin_stats4(const float *__restrict__ data, const
         for (int q = 0; q < 4; ++q) {
             double R = (double)vv[q] + pad;
             if (R < 1.0e-12) R = 1.0e-12;
-            const double w = rcp_nr(R);
+            const double w = obs_weight(R);
             const double dz = (double)(zz[q] - bgv[q]) - piv[q];
             s0[q] += w;
             A[q] = fma(w, dz, A[q]);
@@ -3742,6 +3749,22 @@ __global__ __launch_bounds__(256) void k_copy_active_f32(Prm p, const float *src
     const int64_t b = G * 64 + l;
     if (b >= p.NB || !chain_on(p, b)) return;
     dst[slot] = src[slot];
+}
+
+// constant process noise as blocked rows (Prm::tQ): a pass with one constant matrix per chain stores none; a MASKED pass with
+// per-bin process noise stores the rows of its own chains only, and the chains outside its mask get theirs here first -- the
+// same float32 rows that the constant fill of the reference-layout array holds (pn_fill_values; per-chain Q0: the chain's)
+__global__ __launch_bounds__(256) void k_fill_blocked_q(Prm p, float4 *dst, float4 q) {
+    const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int l = (int)(slot & 63);
+    const int64_t G = (slot >> 6) / p.B;
+    const int64_t b = G * 64 + l;
+    if (b >= p.NB) return;
+    if (p.chainQ != nullptr) {
+        const double *cq = p.chainQ + 4 * (int64_t)p.blkChain[b];
+        q = make_float4((float)cq[0], (float)cq[1], (float)cq[2], (float)cq[3]);
+    }
+    dst[slot] = q;
 }
 
 // blocked -> natural for a list of arrays in ONE launch: a workgroup owns a (wave-group, 32-step) tile, reads 32

@@ -456,7 +456,9 @@ static int need_blocked(csr_ctx *c, std::initializer_list<int> ids, const unsign
     for (int id : ids) {
         if (c->where[id].blocked) continue;
         const float *src = c->nat[id];
-        if (id == CSR_ARR_XF || id == CSR_ARR_XS)
+        if (id == CSR_ARR_D)
+            CHECK(launch(c, nullptr, "k_import_tiled<float>", k_import_tiled<float>, grid, dim3(256), 0, c->stream, p, src, p.tD, (int64_t)0));
+        else if (id == CSR_ARR_XF || id == CSR_ARR_XS)
             CHECK(launch(c, nullptr, "k_import_tiled<float2>", k_import_tiled<float2>, grid, dim3(256), 0, c->stream, p,
                          reinterpret_cast<const float2 *>(src), id == CSR_ARR_XF ? p.tXf : p.tXs, (int64_t)0));
         else
@@ -676,6 +678,13 @@ static int launch_pn_fill(csr_ctx *c, const Prm &p, float *dst, hipStream_t st) 
     c->pnFillValid = true;
     return 0;
 }
+// the same rows in the blocked layout, for every chain (forward_impl: in front of a masked pass with per-bin process noise)
+static int launch_pn_fill_blocked(csr_ctx *c) {
+    float q[4];
+    pn_fill_values(c, c->p, q);
+    return launch(c, "pnoise_blocked_fill", "k_fill_blocked_q", k_fill_blocked_q, dim3(grid_slots(c)), dim3(256), 0, c->stream, c->p, c->p.tQ,
+                  make_float4(q[0], q[1], q[2], q[3]));
+}
 
 // Bit-exact mode: the state chain keeps at most 5/8 of the SIMDs busy for milliseconds and is bound by latency, not by
 // bandwidth.  The reference-layout outputs that depend on the covariance chain alone -- Pf, and the process noise when it
@@ -729,10 +738,15 @@ static int forward_impl(csr_ctx *c, const FwdPass &pass) {
     // a MASKED pass rewrites the blocked xf / Pf of its own chains only: when the resident pass left them in the reference layout
     // alone, the chains outside the mask get their blocked copies back first (they keep their resident results)
     // (whether or not new statistics have invalidated those results since: the masked chains get new ones, the others keep the old)
-    if (active != nullptr) CHECK(need_blocked(c, {CSR_ARR_XF, CSR_ARR_PF}, nullptr));
+    // (the same for the NIS / NLL track: an epilogue that wrote D straight into the reference layout left the blocked D of every
+    // chain stale, and the next export converts the blocked D of every chain)
+    if (active != nullptr) CHECK(need_blocked(c, {CSR_ARR_D, CSR_ARR_XF, CSR_ARR_PF}, nullptr));
+    // ... and for the process noise: the resident pass ran with one constant matrix per chain and stored no rows; a masked pass
+    // with per-bin process noise stores the rows of ITS chains, and the export that follows converts the blocked rows of every chain
+    if (active != nullptr && const_q(c) && (flags & (F_APN | F_QSCALE | F_KAPPA))) CHECK(launch_pn_fill_blocked(c));
     c->sbp.active = false;
     join_pf(c);         // (an early export nobody asked for afterwards still reads the arrays this pass overwrites)
-    new_forward_pass(c);        // GAP: claims a current blocked D for the chains outside a mask even when the resident pass wrote D in the reference layout only
+    new_forward_pass(c);
     c->gainNat = false;
     Prm p = c->p;
     p.flags = flags;

@@ -193,7 +193,8 @@ int csr_batch_sums(csr_ctx *ctx, double *sum_d, double *sum_nll);
 /* a8-a9 over all chains in lock-step; out: n_chains entries; nll_path: n_chains*max_iters or NULL. */
 int csr_batch_ecm(csr_ctx *ctx, const csr_ecm_cfg *cfg, uint32_t flags, csr_ecm_out *out, double *nll_path);
 /* Same, restricted to the chains with chain_mask[c] != 0 (NULL: all); the others keep the resident results of their last
- * fit untouched (out[c].skipped = 2) -- chromosomes of a batch stop their outer background/ECM alternation independently. */
+ * fit untouched (out[c].skipped = 2) -- chromosomes of a batch stop their outer background/ECM alternation independently.
+ * (Every array csr_batch_export hands out, the process-noise rows of a constant-Q fit included, and the per-chain sums.) */
 int csr_batch_ecm_masked(csr_ctx *ctx, const csr_ecm_cfg *cfg, uint32_t flags, const unsigned char *chain_mask,
                          csr_ecm_out *out, double *nll_path);
 
@@ -348,7 +349,11 @@ int csr_batch_phase_tracks(csr_ctx *ctx, int32_t chain, int32_t use_lambda, doub
  * reference sorts m rows of n float64 values on the host; here a byte-wise radix select on the device (csrc/csr_gain.h), exact.
  * out: m * 9 doubles.  (ABI 6) */
 int csr_batch_gain_summary(csr_ctx *ctx, int32_t chain, int32_t use_lambda, double pad, double lam_lo, double lam_hi, double *out);
-/* csr_batch_forward for the chains with chain_mask[c] != 0 only (NULL: all); the others keep their resident results. */
+/* csr_batch_forward for the chains with chain_mask[c] != 0 only (NULL: all); the others keep their resident results: the
+ * NIS / NLL track, the filtered state and covariance, the process-noise rows and the per-chain sums.  (Whether the
+ * process noise is one constant matrix is one property of the whole batch, taken from the LAST pass's flags: a masked pass that
+ * turns kappa / qScale / adaptive process noise ON keeps the constant rows of the other chains; one that turns them OFF after
+ * a resident pass that had them on makes the other chains' rows read as the constant matrix -- not supported.) */
 int csr_batch_forward_masked(csr_ctx *ctx, uint32_t flags, const unsigned char *chain_mask, double *sum_d,
                              double *sum_nll);
 

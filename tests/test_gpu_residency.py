@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 F = np.asarray(cases.F_TREND, np.float32)
 Q0 = np.diag([1e-3, 1e-4]).astype(np.float32)
-ARRS = ("xf", "Pf", "xs", "Ps", "lag")
+ARRS = ("D", "xf", "Pf", "xs", "Ps", "lag")
 
 
 @pytest.fixture(scope="module")
@@ -41,7 +41,7 @@ def _oracle_pass(oracle, d_, v_):
                         blockCount=1, stateInit=0.0, stateCovarInit=1000.0, stateForward=xf, stateCovarForward=Pf,
                         pNoiseForward=pn, vectorD=D, returnNLL=True)
     bw = oracle.cbackwardPass(matrixData=d_, matrixF=F, stateForward=xf, stateCovarForward=Pf, pNoiseForward=pn)
-    return {"xf": xf, "Pf": Pf, "xs": bw[0], "Ps": bw[1], "lag": bw[2][: n - 1]}
+    return {"D": D, "xf": xf, "Pf": Pf, "xs": bw[0], "Ps": bw[1], "lag": bw[2][: n - 1]}
 
 
 def _close(got, ref, lvl, msg):
@@ -62,6 +62,7 @@ def test_a_masked_pass_after_a_step_leaves_the_other_chains_resident(product, or
     'chain c is left exactly as it is') -- and equal to the oracle."""
     from consenrich_amd import _lib as L
     from consenrich_amd.batch import DeviceBatch, ModelParams
+    from test_gpu_parity import close_mostly
 
     monkeypatch.setenv("CONSENRICH_AMD_NATIN", natin)
     n_list, m = [70000, 33000, 4, 50001], 4
@@ -91,17 +92,20 @@ def test_a_masked_pass_after_a_step_leaves_the_other_chains_resident(product, or
             ref = _oracle_pass(oracle, *sets[c]) if n_list[c] > 8 else None
             for a in ARRS:
                 got = b.download(c, a)
-                # What was NOT recomputed must come back bit for bit: every array of a chain outside an ECM call's mask, the
-                # filtered arrays of a chain outside a forward pass's mask.  What WAS recomputed (the masked chains' forward
+                # What was NOT recomputed must come back bit for bit: every array of a chain outside an ECM call's mask, the NIS
+                # track and the filtered arrays of a chain outside a forward pass's mask.  What WAS recomputed (the masked chains' forward
                 # results; after `forward_masked` the smoothed arrays of every chain, by `backward()`): the same bits in the exact
                 # mode (one sequential recursion whatever the kernel form and window); in the 2-ulp mode another pass may accept
                 # other carries -- within the mode's tolerance, the oracle gate below
-                untouched = not mask[c] and (then == "ecm_masked" or a in ("xf", "Pf"))
+                untouched = not mask[c] and (then == "ecm_masked" or a in ("D", "xf", "Pf"))
                 if untouched or xtol == 0:
                     assert np.array_equal(got, before[(c, a)]), (then, xtol, natin, c, a)
                 if ref is not None:
                     lvl = np.maximum(np.abs(ref["xs"][:, :1].astype(np.float64)), 1.0)
-                    _close(got[: ref[a].shape[0]], ref[a], lvl, (c, a))
+                    if a == "D":        # (NIS amplifies one ulp of the level: the parity suite's gate for it)
+                        close_mostly(got, ref[a], msg=str((c, a)))
+                    else:
+                        _close(got[: ref[a].shape[0]], ref[a], lvl, (c, a))
 
 
 @pytest.mark.parametrize("xtol", [2, 0], ids=["ulp2", "exact"])
@@ -188,11 +192,13 @@ def test_remembered_conversions_follow_the_resident_fit(product):
         b.export(L.EXPORT_MULT | L.EXPORT_SMOOTH)
         k2, x2 = b.download(0, "kappa"), b.download(0, "xs")
         assert not np.array_equal(k1, k2) and not np.array_equal(x1, x2)
+        k2_chain1 = b.download(1, "kappa")
+        assert not np.all(k2_chain1 == 1.0)         # (the E-steps moved it off the cold start: a reset would be seen)
         new = np.full(n_list[0], 1.5, np.float32)
         b.upload_multipliers(0, kappa=new)
         b.export(L.EXPORT_MULT)
         assert np.array_equal(b.download(0, "kappa"), new)
-        assert np.array_equal(b.download(1, "kappa"), b.download(1, "kappa")) and np.all(np.isfinite(rel))
+        assert np.array_equal(b.download(1, "kappa").view(np.uint32), k2_chain1.view(np.uint32)) and np.all(np.isfinite(rel))
 
 
 @pytest.mark.parametrize("use_lambda", [False, True], ids=["plain", "lambda"])
@@ -285,7 +291,9 @@ def test_every_call_sequence_launches_the_recorded_conversions(product, monkeypa
     epilogue, per-chain sums, multiplier imports, summaries; statistics, chains with their fix-up and check launches, state
     chains, E-steps) of the call sequences in tests/golden/launch_cases.py against tests/golden/conversion_launches.json,
     recorded with the library of the commit before the passes became descriptors (FwdPass / BwdPass, csr_ctx::last): every count
-    of every sequence equal, and no pipeline replay."""
+    of every sequence equal, and no pipeline replay.  (Recorded again when a masked pass began to bring the NIS / NLL track back
+    into the blocked layout for the chains outside its mask: one more `state_reblock_out` in the three sequences with a masked
+    pass behind a step, wherever xf / Pf did not already open that scope; nothing else moved.)"""
     import launch_cases
 
     # (the record holds the launches of the library's default forms: under another mode switch of scripts/suite_variants.sh the
