@@ -215,6 +215,18 @@ class ExportPeak(C.Structure):
                 ("max_score", C.c_double), ("subpeak_objective", C.c_double), ("subpeak_boundary_penalty", C.c_double)]
 
 
+class DepspanCfg(C.Structure):
+    _fields_ = [("window_bins", C.c_int64), ("max_lag_bins", C.c_int32), ("smoothing_bins", C.c_int32),
+                ("persistence_bins", C.c_int32), ("min_finite_pairs", C.c_int32), ("acf_threshold", C.c_double),
+                ("min_finite_pair_coverage", C.c_double)]
+
+
+# csr_depspan_window as a NumPy record (the records travel as one structured array: consenrich_amd/depspan.py)
+DEPSPAN_WINDOW = [("status", "<i4"), ("crossing_lag", "<i4"), ("support_cap_lag", "<i4"), ("last_crossing_start", "<i4"),
+                  ("valid_rows", "<i4"), ("valid_rows_at_crossing", "<i4"), ("flags", "<i4"), ("reserved", "<i4"),
+                  ("finite_pair_min", "<f8"), ("finite_pair_coverage_min", "<f8"), ("revival", "<f8"), ("margin", "<f8")]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double)]
 
@@ -379,6 +391,16 @@ SYMBOLS = {
     "csr_export_peaks": (C.c_int, [C.c_int32, I64P, DP, DP, DP, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, I64P]),
     "csr_batch_export_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, I64P]),
     "csr_export_fetch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    # (mats: an array of pointers to float32 matrices; the window records are a NumPy structured array: consenrich_amd/depspan.py)
+    "csr_depspan_unique_rows": (C.c_int, [C.c_int32, I64P, C.POINTER(C.c_void_p), C.c_int64, I32P, I32P]),
+    "csr_depspan_window_scores": (C.c_int, [C.c_int32, I64P, C.POINTER(C.c_void_p), C.c_int64, C.c_int32, I32P, C.c_int64,
+                                            C.c_double, DP, I64P]),
+    "csr_depspan_window_acf": (C.c_int, [C.c_int32, I64P, C.POINTER(C.c_void_p), C.c_int64, C.c_int32, I32P,
+                                         C.POINTER(DepspanCfg), C.c_int64, I32P, I64P, C.c_void_p, DP]),
+    "csr_batch_depspan_unique_rows": (C.c_int, [C.c_void_p, C.c_int32, I32P, I32P, I32P]),
+    "csr_batch_depspan_window_scores": (C.c_int, [C.c_void_p, C.c_int32, I32P, C.c_int32, I32P, C.c_int64, C.c_double, DP, I64P]),
+    "csr_batch_depspan_window_acf": (C.c_int, [C.c_void_p, C.c_int32, I32P, C.c_int32, I32P, C.POINTER(DepspanCfg), C.c_int64,
+                                               I32P, I64P, C.c_void_p, DP]),
 }
 
 _lib = None

@@ -803,6 +803,16 @@ class DeviceBatch:
                             calibration_quantile=calibration_quantile, pooled_floors=pooled_floors,
                             draws_per_group=draws_per_group, noise=noise)
 
+    # -- dependence span from the resident matrices (consenrich_amd/depspan.py) ---------------------------------------------------
+    def dependence_span(self, names, interval_bp, *, chains=None, **kw):
+        """`cchooseDependenceSpan` (pyx:3360-4120) of the RESIDENT data: names[k] is the chromosome of chains[k] (default: every
+        chain in order; a fold chain is left out by not listing it).  The keywords are the reference's (windowBP, windowCount,
+        maxLagBP, ...) and `period_diagnostics`.  Returns (point, lower, upper, diagnostics) like the drop-in, from the same
+        kernels; no resident array changes."""
+        from . import depspan as D
+
+        return D.batch_dependence_span(self, names, interval_bp, chains=chains, **kw)
+
     # -- ROCCO budget: effective sample size of a series of the resident scores, and the budget policy (consenrich_amd/ess.py) ----
     def ess(self, kind: str, thresholds, scales, max_lags, chains=None):
         """`cEstimateEffectiveSampleSize` (pyx:9160-9279, its fast path) of a series built on the device from every chain's RESIDENT

@@ -31,7 +31,7 @@ __all__ = [
     "cfixedBackgroundECMLevel", "cExpectedTransitionResidualSums", "cExpectedTransitionResidualSumsLevel",
     "csolvePenalizedChainROCCO", "ccalibrateSelectionPenaltyROCCO", "csolveChromROCCOExact",
     "cGenerateDWBMultipliersFromNoise", "cApplyStationaryNullDWB", "cStationaryNullDWBDraw",
-    "cEstimateEffectiveSampleSize",
+    "cEstimateEffectiveSampleSize", "cchooseDependenceSpan",
 ]
 
 
@@ -637,3 +637,6 @@ from .segments import cMultiscaleCandidateSegmentStats  # noqa: E402,F401
 
 # effective sample size scan behind the ROCCO budget (pyx:9160-9279), implemented in consenrich_amd/ess.py
 from .ess import cEstimateEffectiveSampleSize  # noqa: E402,F401
+
+# dependence span from the per-chromosome matrices (pyx:3360-4120), implemented in consenrich_amd/depspan.py
+from .depspan import cchooseDependenceSpan  # noqa: E402,F401

@@ -18,6 +18,7 @@
 #include "csr_peakscore.h"
 #include "csr_nested.h"
 #include "csr_export.h"
+#include "csr_depspan.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
 
@@ -497,6 +498,12 @@ struct csr_ctx : BatchState {
         };
         std::vector<Flagged> flagged;
     } seg;
+    // dependence span (csr_host_depspan.inl): growable work space of a call -- a staged host matrix or window set, the matrix / window /
+    // row / pair tables, the difference flags, and per (window, row) of a group the compacted and the centred values, the finite
+    // counts, the lag sums and pair counts, the per-lag pooling arrays and the window records
+    struct DepWs {
+        DevBuf stageBuf, matBuf, winBuf, rowBuf, pairTab, diffBuf, compBuf, cenBuf, nfinBuf, sumBuf, pairBuf, lagBuf, medBuf, recBuf;
+    } depWs;
     // DWB peak scoring (csr_host_peakscore.inl): growable work space of a call -- an uploaded host track, the segments, views and
     // results of a scoring call, the observed and pooled statistics with their p / q values (sorted through nullWs)
     struct PeakWs {
@@ -913,3 +920,4 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_peakscore.inl"
 #include "csr_host_nested.inl"
 #include "csr_host_export.inl"
+#include "csr_host_depspan.inl"

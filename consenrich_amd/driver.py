@@ -582,6 +582,22 @@ def call_peaks_batch(batch: DeviceBatch, *, budget=None, gamma=0.5, selection_pe
     return res
 
 
+def dependence_span_batch(batch: DeviceBatch, names, interval_bp, **kw) -> dict:
+    """The reference's `_ensureSampledDependenceSpan` (consenrich.py:7063-7134) from the matrices resident in a batch:
+    `DeviceBatch.dependence_span` (chains=..., and the keywords of `cchooseDependenceSpan`), then the working span in intervals,
+    the context length and the reference's two consistency checks.  `span_intervals` is what
+    `first_pass_peaks_batch(dependence_spans=...)` takes."""
+    point, lower, upper, diagnostics = batch.dependence_span(names, interval_bp, **kw)
+    working = float(diagnostics["workingSpanBP"])
+    if not math.isclose(working, float(diagnostics["fullSampleWorkingSpanBP"]), rel_tol=0.0, abs_tol=1.0e-9):
+        raise RuntimeError("workingSpanBP must equal the full-sample KM quantile")
+    if int(point) != int(math.ceil(float(diagnostics["estimateBP"]) / float(interval_bp))):
+        raise RuntimeError("correlation-radius tuple and BP diagnostic disagree")
+    span_intervals = int(math.ceil(working / float(interval_bp)))
+    return {"point": int(point), "lower": int(lower), "upper": int(upper), "diagnostics": diagnostics,
+            "span_intervals": span_intervals, "context_bp": int(2 * span_intervals * int(interval_bp) + 1)}
+
+
 def first_pass_peaks_batch(batch: DeviceBatch, *, dependence_spans, threshold_z, threshold_z_grid, num_bootstrap, random_seed,
                            gamma, gamma_scale, selection_penalty=None, score_mode, z, max_gap_bins,
                            pooled_floors=None) -> List[dict]:

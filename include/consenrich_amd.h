@@ -886,6 +886,52 @@ int csr_batch_export_peaks(csr_ctx *ctx, const csr_export_cfg *cfg, const unsign
                            const csr_export_parent *parents, int32_t *parent_flags, int64_t *count);
 int csr_export_fetch(csr_ctx *ctx, int64_t capacity, csr_export_peak *peaks);
 
+/* ---- the dependence span: the device stages of pyx:3360-4120 `cchooseDependenceSpan` (helpers pyx:2645-3357) ------------------
+ * Three stages, each on host arrays (default context; mats[k] = n_rows x n_bins[k] float32 in C order, staged one chromosome or one
+ * window set at a time) and on the RESIDENT data of the listed chains of a batch (chains[k]: a chain index; a fold chain is left
+ * out by not listing it; no resident array changes).  The caller composes the rest (consenrich_amd/depspan.py).
+ *   unique_rows    retained[0 .. *n_retained): row j is dropped iff an earlier row is byte-identical to it in every matrix (32-bit
+ *                  patterns: -0.0 != 0.0, NaN payloads count) -- what `_dependenceUniqueRows` keeps.
+ *   window_scores  for every full window of window_bins bins of every matrix that holds one, in matrix order: count[w] = the rows
+ *                  with a finite count > 0 and finiteCount / window_bins >= rank_coverage_min, score[w] = np.median of their
+ *                  window_bins / finiteCount * np.sum(np.maximum(v[finite], 0)) (NaN for count 0).  Bit for bit (pyx:3664-3703).
+ *   window_acf     `_dependenceFinitePairWindow` (pyx:2916-3148) of the retained rows of every listed window (win_mat / win_chain:
+ *                  index into the matrices / the chain list; win_start: first bin).  Up to the centred values every number equals
+ *                  the reference's bit for bit; the lag sums are compensated dot products in index order, about an ulp from the
+ *                  exact sums (the reference takes them from an FFT).  rec[w]: the decisions of the window; pooled[w][max_lag_bins]:
+ *                  its pooled ACF (NaN from the support cap on).  margin: the smallest |smoothed ACF - acf_threshold| over the lags
+ *                  the persistence scan examined -- a window whose margin is within the FFT's error is decided by the caller.
+ * At most 4096 rows.  The order statistics behind the clip order -0.0 in front of +0.0 (NumPy: equal): a clip bound, and through it
+ * a centred value, may differ from the reference's in the sign of a zero, in nothing else. */
+typedef struct csr_depspan_cfg {
+    int64_t window_bins;
+    int32_t max_lag_bins, smoothing_bins, persistence_bins, min_finite_pairs;
+    double acf_threshold, min_finite_pair_coverage;
+} csr_depspan_cfg;
+enum { CSR_DEPSPAN_TINY_LAG_ZERO = 1 };     /* flags: a row's lag-zero covariance lies in the underflow range */
+typedef struct csr_depspan_window {
+    int32_t status;                 /* 0: the reference answers None; 1: a result */
+    int32_t crossing_lag;           /* -1: right-censored */
+    int32_t support_cap_lag, last_crossing_start, valid_rows, valid_rows_at_crossing;
+    int32_t flags, reserved;
+    double finite_pair_min, finite_pair_coverage_min;
+    double revival;                 /* max |pooled ACF| from crossing_lag + persistence_bins - 1 on (NaN: none) */
+    double margin;
+} csr_depspan_window;
+int csr_depspan_unique_rows(int32_t n_mats, const int64_t *n_bins, const float *const *mats, int64_t n_rows, int32_t *retained,
+                            int32_t *n_retained);
+int csr_depspan_window_scores(int32_t n_mats, const int64_t *n_bins, const float *const *mats, int64_t n_rows_total, int32_t n_rows,
+                              const int32_t *rows, int64_t window_bins, double rank_coverage_min, double *score, int64_t *count);
+int csr_depspan_window_acf(int32_t n_mats, const int64_t *n_bins, const float *const *mats, int64_t n_rows_total, int32_t n_rows,
+                           const int32_t *rows, const csr_depspan_cfg *cfg, int64_t n_windows, const int32_t *win_mat,
+                           const int64_t *win_start, csr_depspan_window *rec, double *pooled);
+int csr_batch_depspan_unique_rows(csr_ctx *ctx, int32_t n_listed, const int32_t *chains, int32_t *retained, int32_t *n_retained);
+int csr_batch_depspan_window_scores(csr_ctx *ctx, int32_t n_listed, const int32_t *chains, int32_t n_rows, const int32_t *rows,
+                                    int64_t window_bins, double rank_coverage_min, double *score, int64_t *count);
+int csr_batch_depspan_window_acf(csr_ctx *ctx, int32_t n_listed, const int32_t *chains, int32_t n_rows, const int32_t *rows,
+                                 const csr_depspan_cfg *cfg, int64_t n_windows, const int32_t *win_chain, const int64_t *win_start,
+                                 csr_depspan_window *rec, double *pooled);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
