@@ -29,6 +29,7 @@
 #include <type_traits>
 #include <utility>
 #include <stdint.h>
+#include "csr_resid_form.h"
 
 namespace csr {
 
@@ -1212,40 +1213,45 @@ struct BwdTrendT {
     __device__ static __forceinline__ Gain gain(const Prm &p, const float4 &pf, const float4 &q) {
         Gain g;
         const double f00 = pf.x, f01 = pf.y, f10 = pf.z, f11 = pf.w;
+        // The reference's own operations in its own order (pyx:6765-6800: rounded products, sums from the left, the determinant
+        // unfused, four IEEE quotients, J unfused).  Where a chain starts from a wide prior the predicted covariance is nearly
+        // singular (pp00 pp11 / det up to 4e5 at bin 0 of a levelTrend chain with P0 = 1000) and J = (Pf F^T) Pp^-1 is a cancelling
+        // sum of terms that large: a fused determinant, a reciprocal one ulp from the quotient or a fused J moved Ps[0][1,1] and
+        // lag[0] by up to 1e-4 relative there (tests/test_gpu_many_samples.py; with J fused again the difference came back).  With
+        // F = [[1, f], [0, 1]] the products by 1 and 0 are exact and left out.
         if constexpr (UF) {
-            const double a00 = fma(p.F01, f10, f00), a01 = fma(p.F01, f11, f01);      // F Pf with F = [[1, f], [0, 1]]: a10 = f10, a11 = f11
-            g.pp00 = fma(a01, p.F01, a00 + (double)q.x);
+            const double a00 = f00 + p.F01 * f10, a01 = f01 + p.F01 * f11;            // F Pf: a10 = f10, a11 = f11
+            g.pp00 = (a00 + a01 * p.F01) + (double)q.x;
             g.pp01 = a01 + (double)q.y;
-            g.pp10 = fma(f11, p.F01, f10 + (double)q.z);
+            g.pp10 = (f10 + f11 * p.F01) + (double)q.z;
             g.pp11 = f11 + (double)q.w;
         } else {
-            const double a00 = fma(p.F01, f10, p.F00 * f00);      // F Pf
-            const double a01 = fma(p.F01, f11, p.F00 * f01);
-            const double a10 = fma(p.F11, f10, p.F10 * f00);
-            const double a11 = fma(p.F11, f11, p.F10 * f01);
-            g.pp00 = fma(a01, p.F01, fma(a00, p.F00, (double)q.x));
-            g.pp01 = fma(a01, p.F11, fma(a00, p.F10, (double)q.y));
-            g.pp10 = fma(a11, p.F01, fma(a10, p.F00, (double)q.z));
-            g.pp11 = fma(a11, p.F11, fma(a10, p.F10, (double)q.w));
+            const double a00 = p.F00 * f00 + p.F01 * f10;         // F Pf
+            const double a01 = p.F00 * f01 + p.F01 * f11;
+            const double a10 = p.F10 * f00 + p.F11 * f10;
+            const double a11 = p.F10 * f01 + p.F11 * f11;
+            g.pp00 = (a00 * p.F00 + a01 * p.F01) + (double)q.x;
+            g.pp01 = (a00 * p.F10 + a01 * p.F11) + (double)q.y;
+            g.pp10 = (a10 * p.F00 + a11 * p.F01) + (double)q.z;
+            g.pp11 = (a10 * p.F10 + a11 * p.F11) + (double)q.w;
         }
-        const double det = fma(g.pp00, g.pp11, -(g.pp01 * g.pp10));   // unguarded, pyx:6780
-        const double rd = rcp_nr(det);
-        const double v00 = g.pp11 * rd, v01 = -g.pp01 * rd, v10 = -g.pp10 * rd, v11 = g.pp00 * rd;
+        const double det = (g.pp00 * g.pp11) - (g.pp01 * g.pp10);     // unguarded, pyx:6780
+        const double v00 = g.pp11 / det, v01 = -g.pp01 / det, v10 = -g.pp10 / det, v11 = g.pp00 / det;
         if constexpr (UF) {
-            g.c00 = fma(f01, p.F01, f00);                     // Pf F^T
+            g.c00 = f00 + f01 * p.F01;                        // Pf F^T
             g.c01 = f01;
-            g.c10 = fma(f11, p.F01, f10);
+            g.c10 = f10 + f11 * p.F01;
             g.c11 = f11;
         } else {
-            g.c00 = fma(f01, p.F01, f00 * p.F00);             // Pf F^T
-            g.c01 = fma(f01, p.F11, f00 * p.F10);
-            g.c10 = fma(f11, p.F01, f10 * p.F00);
-            g.c11 = fma(f11, p.F11, f10 * p.F10);
+            g.c00 = f00 * p.F00 + f01 * p.F01;                // Pf F^T
+            g.c01 = f00 * p.F10 + f01 * p.F11;
+            g.c10 = f10 * p.F00 + f11 * p.F01;
+            g.c11 = f10 * p.F10 + f11 * p.F11;
         }
-        g.J00 = fma(g.c01, v10, g.c00 * v00);
-        g.J01 = fma(g.c01, v11, g.c00 * v01);
-        g.J10 = fma(g.c11, v10, g.c10 * v00);
-        g.J11 = fma(g.c11, v11, g.c10 * v01);
+        g.J00 = g.c00 * v00 + g.c01 * v10;
+        g.J01 = g.c00 * v01 + g.c01 * v11;
+        g.J10 = g.c10 * v00 + g.c11 * v10;
+        g.J11 = g.c10 * v01 + g.c11 * v11;
         return g;
     }
     struct Out {            // what one bin contributes to the outputs
@@ -3860,23 +3866,28 @@ __device__ __forceinline__ void resid_prologue_check(const Prm &p) {
 }
 // (wg: the workgroup's index within the run of bins [0, nBins) that the pointers start at)
 __device__ __forceinline__ void resid_dev(const Prm &p, const float *xsNat, int xsStride, float *resid, int64_t nBins, int64_t wg) {
-    extern __shared__ float tileR[];                 // [m][65]
+    extern __shared__ float tileR[];                 // [min(m, RESID_SLAB_PLAIN)][65]
     const int64_t g0 = wg * 64;
     const int t = threadIdx.x;
     const int gl = t & 63, r0 = t >> 6;
     const int64_t g = g0 + gl;
     float x = 0.f;
     if (g < nBins) x = xsNat[g * xsStride];
-    for (int j = r0; j < p.m; j += 4) {
-        float v = 0.f;
-        if (g < nBins) v = (float)((double)(p.data[(int64_t)j * p.Npad + g] - (p.bg ? p.bg[g] : 0.f)) - (double)x);
-        tileR[j * 65 + gl] = v;
-    }
-    __syncthreads();
-    const int total = 64 * p.m;
-    for (int e = t; e < total; e += 256) {
-        const int bin = e / p.m, j = e - bin * p.m;
-        if (g0 + bin < nBins) resid[(g0 + bin) * (int64_t)p.m + j] = tileR[j * 65 + bin];
+    // the sample rows [j0, j0 + ms) at a time (csr_resid_form.h): one slab up to m = RESID_SLAB_PLAIN
+    for (int j0 = 0; j0 < p.m; j0 += RESID_SLAB_PLAIN) {
+        const int ms = min(p.m - j0, RESID_SLAB_PLAIN);
+        if (j0) __syncthreads();                     // the previous slab has been written out
+        for (int j = r0; j < ms; j += 4) {
+            float v = 0.f;
+            if (g < nBins) v = (float)((double)(p.data[(int64_t)(j0 + j) * p.Npad + g] - (p.bg ? p.bg[g] : 0.f)) - (double)x);
+            tileR[j * 65 + gl] = v;
+        }
+        __syncthreads();
+        const int total = 64 * ms;
+        for (int e = t; e < total; e += 256) {
+            const int bin = e / ms, j = e - bin * ms;
+            if (g0 + bin < nBins) resid[(g0 + bin) * (int64_t)p.m + j0 + j] = tileR[j * 65 + bin];
+        }
     }
 }
 __global__ __launch_bounds__(256) void k_resid(Prm p, const float *xsNat, int xsStride, float *resid, int64_t nBins) {
@@ -3889,7 +3900,7 @@ __global__ __launch_bounds__(256) void k_resid(Prm p, const float *xsNat, int xs
 // sweep are in flight together (K = 1 leaves the kernel latency-bound: 2 loads per thread at m = 32).
 template <int K>
 __device__ __forceinline__ void resid_v4_dev(const Prm &p, const float *xsNat, int xsStride, float *resid, int64_t nBins, int64_t wg) {
-    extern __shared__ float tileR[];                 // [m][K*64+4]: the row stride keeps float4 rows 16-B aligned
+    extern __shared__ float tileR[];                 // [rows of a slab][K*64+4]: the row stride keeps float4 rows 16-B aligned
     constexpr int RS = K * 64 + 4;
     const int64_t g0 = wg * (K * 64);
     const int t = threadIdx.x;
@@ -3909,35 +3920,45 @@ __device__ __forceinline__ void resid_v4_dev(const Prm &p, const float *xsNat, i
             if (p.bg) bg4[u] = *reinterpret_cast<const float4 *>(p.bg + g);
         }
     }
-    for (int j = r0; j < p.m; j += 16) {
-        float4 z[K];
+    // The sample rows [j0, j0 + ms) at a time (csr_resid_form.h).  K = 2 is chosen only while all m rows fit (resid_form): one
+    // slab, the loop below runs once with j0 = 0 and ms = m; K = 1 walks slabs of RESID_SLAB_V4_K1 rows, a multiple of 4.
+    int j0 = 0;
+    for (;;) {
+        const int ms = K == 1 ? min(p.m - j0, RESID_SLAB_V4_K1) : p.m;
+        for (int j = r0; j < ms; j += 16) {
+            float4 z[K];
 #pragma unroll
-        for (int u = 0; u < K; ++u) {
-            z[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ok[u]) z[u] = *reinterpret_cast<const float4 *>(p.data + (int64_t)j * p.Npad + g0 + u * 64 + 4 * q);
-        }
-#pragma unroll
-        for (int u = 0; u < K; ++u) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ok[u]) {
-                v.x = (float)((double)(z[u].x - bg4[u].x) - (double)x[u][0]);
-                v.y = (float)((double)(z[u].y - bg4[u].y) - (double)x[u][1]);
-                v.z = (float)((double)(z[u].z - bg4[u].z) - (double)x[u][2]);
-                v.w = (float)((double)(z[u].w - bg4[u].w) - (double)x[u][3]);
+            for (int u = 0; u < K; ++u) {
+                z[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ok[u]) z[u] = *reinterpret_cast<const float4 *>(p.data + (int64_t)(j0 + j) * p.Npad + g0 + u * 64 + 4 * q);
             }
-            *reinterpret_cast<float4 *>(tileR + j * RS + u * 64 + 4 * q) = v;
+#pragma unroll
+            for (int u = 0; u < K; ++u) {
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ok[u]) {
+                    v.x = (float)((double)(z[u].x - bg4[u].x) - (double)x[u][0]);
+                    v.y = (float)((double)(z[u].y - bg4[u].y) - (double)x[u][1]);
+                    v.z = (float)((double)(z[u].z - bg4[u].z) - (double)x[u][2]);
+                    v.w = (float)((double)(z[u].w - bg4[u].w) - (double)x[u][3]);
+                }
+                *reinterpret_cast<float4 *>(tileR + j * RS + u * 64 + 4 * q) = v;
+            }
         }
-    }
-    __syncthreads();
-    const int m4 = p.m >> 2;
-    const int total4 = K * 64 * m4;
-    for (int e = t; e < total4; e += 256) {
-        const int bin = e / m4, j = (e - bin * m4) << 2;
-        if (g0 + bin < nBins) {
-            const float4 o = make_float4(tileR[(j + 0) * RS + bin], tileR[(j + 1) * RS + bin],
-                                         tileR[(j + 2) * RS + bin], tileR[(j + 3) * RS + bin]);
-            *reinterpret_cast<float4 *>(resid + (g0 + bin) * (int64_t)p.m + j) = o;
+        __syncthreads();
+        const int m4 = ms >> 2;
+        const int total4 = K * 64 * m4;
+        for (int e = t; e < total4; e += 256) {
+            const int bin = e / m4, j = (e - bin * m4) << 2;
+            if (g0 + bin < nBins) {
+                const float4 o = make_float4(tileR[(j + 0) * RS + bin], tileR[(j + 1) * RS + bin],
+                                             tileR[(j + 2) * RS + bin], tileR[(j + 3) * RS + bin]);
+                *reinterpret_cast<float4 *>(resid + (g0 + bin) * (int64_t)p.m + j0 + j) = o;
+            }
         }
+        if constexpr (K != 1) break;
+        j0 += ms;
+        if (j0 >= p.m) break;
+        __syncthreads();                             // the slab has been written out: its tile is free
     }
 }
 template <int K>

@@ -1336,19 +1336,9 @@ static int need_natural_mult(csr_ctx *c, ExpList &L, int id) {
     return need_natural(c, L, id, id == CSR_ARR_LAMBDA ? c->p.tLam : (id == CSR_ARR_KAPPA ? c->p.tKap : c->p.tQs), 1, 1, 0);
 }
 
-// The form of the residual kernels for this batch: K 64-bin sub-tiles per workgroup, rows of m floats padded by `padRows` rows in
-// LDS: the 16-byte form (m a multiple of 4) with K = 2 (measured best: 0.665 vs 0.684 ms with 1 or 4, round 3) while its tile
-// fits 64 KB, else with K = 1
-struct ResidForm { bool v4; int K; size_t lds; };
-static ResidForm resid_form(const csr_ctx *c) {
-    int K = 1, padRows = 1;
-    const bool v4 = (c->m & 3) == 0;
-    if (v4) {
-        padRows = 4;
-        K = sizeof(float) * (size_t)(2 * 64 + 4) * c->m <= 65536 ? 2 : 1;
-    }
-    return {v4, K, sizeof(float) * (size_t)(K * 64 + padRows) * c->m};
-}
+// The form of the residual kernels for this batch (csr_resid_form.h): K 64-bin sub-tiles per workgroup, the sample rows staged in
+// LDS all at once or, past 64 KB, in slabs
+static ResidForm resid_form(const csr_ctx *c) { return resid_form(c->m); }
 // residuals of the bins [off, off + nb) of the batch's natural layout (whole chains: off and nb are multiples of 64)
 static int launch_resid(csr_ctx *c, int64_t off, int64_t nb, bool foldCheck) {
     const int d = c->mdl.state_dim;

@@ -149,7 +149,10 @@ int csr_set_tuning(csr_ctx *ctx, int32_t block_len, int32_t warm_p, int32_t warm
  * the contract is per pass, not through an ECM loop.  CONSENRICH_AMD_XTOL_ULPS overrides the default of both. */
 int csr_set_validation(csr_ctx *ctx, int32_t x_tol_ulps);
 
-/* Describe a batch: n_chains independent chains (chromosomes) of chain_len[c] bins, m samples each. (Re)allocates. */
+/* Describe a batch: n_chains independent chains (chromosomes) of chain_len[c] bins, m samples each. (Re)allocates.
+ * Any m > 0: device memory alone bounds it.  No kernel's LDS request grows with m beyond 64 KB (the residual kernels walk the
+ * samples in slabs past m = 240 / 252, csrc/csr_resid_form.h); tested up to m = 631.  The one call with a ceiling of its own
+ * is csr_batch_gain_summary: m <= 65535. */
 int csr_batch_configure(csr_ctx *ctx, const csr_model *mdl, int64_t m, int32_t n_chains,
                         const int64_t *chain_len);
 /* Replace the model parameters (same state_dim) without reallocating or re-uploading. */

@@ -234,6 +234,24 @@ def test_step_groups_header_hands_out_chains_as_the_pipelined_step_expects(tmp_p
     assert r.returncode == 0 and "step_groups_check ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def test_resid_form_header_bounds_the_lds_request_for_every_sample_count(tmp_path):
+    """consenrich_amd/csrc/csr_resid_form.h is plain C++17: tests/resid_form_check.cpp (every m in 1 .. 65535: LDS request within
+    64 KB, slabs of sample rows that tile [0, m) exactly, multiples of 4 in the 16-byte form; the one-slab forms at m = 4, 124,
+    125, 128, 240, 251 as a literal table; 244, 252, 253, 256, 604, 631 bounded) built stand-alone under the address and
+    undefined-behaviour sanitizers."""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "resid_form_check"
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "consenrich_amd", "csrc"), os.path.join(ROOT, "tests", "resid_form_check.cpp"),
+                           "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "resid_form_check ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+
+
 def test_chain_tracks_header_selects_chains_as_the_peak_stages_expect(tmp_path):
     """consenrich_amd/csrc/csr_chain_tracks.h is plain C++17: tests/chain_tracks_check.cpp (presence flags of a per-chain track,
     the chains a mask takes and the first of them without the track, the scatter of compact results) built stand-alone under
