@@ -215,6 +215,44 @@ class ExportPeak(C.Structure):
                 ("max_score", C.c_double), ("subpeak_objective", C.c_double), ("subpeak_boundary_penalty", C.c_double)]
 
 
+# the massive sub-peak clean-up (consenrich_amd/cleanup.py holds the records as NumPy structured arrays)
+CLEANUP_MAX_SEGMENTS, CLEANUP_MAX_DEPTH, CLEANUP_SORT_TILE = 20, 32, 2048
+CLEANUP_OP_FORCE, CLEANUP_OP_SPLIT, CLEANUP_OP_CONTRACT = 0, 1, 2
+CLEANUP_MODES = (None, "unsplit", "split", "adaptive_core", "width_capped_core")
+CLEANUP_CANDIDATE, CLEANUP_APPLIED, CLEANUP_HAS_SPLIT, CLEANUP_HAS_CORE_WIDTH = 1, 2, 4, 8
+CLEANUP_HAS_CORE_FLOOR, CLEANUP_MOVED, CLEANUP_SPLIT_FROM_PARENT = 16, 32, 64
+
+
+class CleanupPolicy(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("contract_threshold", C.c_double), ("split_quantile", C.c_double),
+                ("min_split_z", C.c_double), ("boundary_cost", C.c_double), ("min_run", C.c_int32), ("max_depth", C.c_int32)]
+
+
+class CleanupChild(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64)]
+
+
+class CleanupBatchChild(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("edge_base", C.c_int64), ("chain", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CleanupSegment(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("core_width_bp", C.c_int64), ("gain", C.c_double), ("z", C.c_double),
+                ("core_score_floor", C.c_double), ("gap_bins", C.c_int32), ("mode", C.c_int32), ("flags", C.c_int32),
+                ("child", C.c_int32)]
+
+
+class CleanupCounts(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("candidates", "splits", "segments_added", "evaluated", "contracts", "n_segments", "flags",
+                                         "reserved")]
+
+
+class CleanupNode(C.Structure):
+    _fields_ = [("a", C.c_int64), ("b", C.c_int64), ("width", C.c_int64)] + \
+               [(k, C.c_double) for k in ("baseline", "scale", "deficit", "gain", "z", "floor")] + \
+               [(k, C.c_int32) for k in ("found", "mode", "gap_bins", "reserved")]
+
+
 class DepspanCfg(C.Structure):
     _fields_ = [("window_bins", C.c_int64), ("max_lag_bins", C.c_int32), ("smoothing_bins", C.c_int32),
                 ("persistence_bins", C.c_int32), ("min_finite_pairs", C.c_int32), ("acf_threshold", C.c_double),
@@ -391,6 +429,10 @@ SYMBOLS = {
     "csr_export_peaks": (C.c_int, [C.c_int32, I64P, DP, DP, DP, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, I64P]),
     "csr_batch_export_peaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, I64P]),
     "csr_export_fetch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "csr_batch_cleanup_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, I64P, C.c_int64, C.c_int64,
+                                         C.c_void_p, I64P, C.c_void_p]),
+    "csr_cleanup_plan": (C.c_int, [C.c_int32, C.c_int64, DP, I64P, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_void_p, I64P, C.c_void_p, C.c_void_p]),
     # (mats: an array of pointers to float32 matrices; the window records are a NumPy structured array: consenrich_amd/depspan.py)
     "csr_depspan_unique_rows": (C.c_int, [C.c_int32, I64P, C.POINTER(C.c_void_p), C.c_int64, I32P, I32P]),
     "csr_depspan_window_scores": (C.c_int, [C.c_int32, I64P, C.POINTER(C.c_void_p), C.c_int64, C.c_int32, I32P, C.c_int64,

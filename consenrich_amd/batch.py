@@ -594,7 +594,8 @@ class DeviceBatch:
 
     def narrowpeak_rows(self, selection_penalties, gammas, *, intervals=None, ends=None, interval_bp=None, chroms=None,
                         prefix="consenrich", min_subpeak_bins=5, trim_score_floor=0.0, multiplier=2.0, use_uncertainty=True,
-                        chains=None, split_subpeaks=True):
+                        chains=None, split_subpeaks=True, width_policy=None, massive_subpeak_cleanup=True,
+                        split_quantile=0.25, split_z=2.0):
         """The reference's first-pass narrowPeak rows (`_solutionToChromNarrowPeakRows`, peaks.py:5202-5567, without a width policy
         and without a hierarchy) of every chain's RESIDENT mask, in one device call for all parents of all chains: sub-peaks of
         every run with the min-run dynamic programme (selection penalty = the chain's, boundary cost = 0.25 gamma,
@@ -605,9 +606,18 @@ class DeviceBatch:
         coordinate work from compact records (consenrich_amd/narrowpeak.py).  A chain with a non-finite signal value inside a
         selected run has its signal-dependent numbers redone with NumPy on its downloaded tracks (`decided_on_host`).  Returns per
         chain (None where not taken) a dict: rows, peak_meta, export_details, decided_on_host; `narrowpeak_stats` holds the last
-        call's counts and its time on the device and in all."""
+        call's counts and its time on the device and in all.
+
+        width_policy (a dict of `cleanup.learn_massive_subpeak_width_policy`; None: the first pass above, unchanged): the export
+        under the massive sub-peak clean-up, as `solveRocco`'s second pass makes it.  Still from resident data alone and without
+        changing any: after the children, their final segments come from one `csr_batch_cleanup_plan` call for all chains (only if
+        the policy is active and has a threshold; the coordinates travel as a step where `interval_bp` serves every chain,
+        otherwise as the children's own edges), and the finishing step runs per SEGMENT -- `csr_batch_export_peaks` again with the
+        segments as parents that do not split.  The meta keys and export details of the clean-up are filled as the reference fills
+        them, for an inactive policy too; `narrowpeak_stats` gains the five counters."""
         import time
 
+        from . import cleanup as K
         from . import narrowpeak as P
 
         t_start = time.perf_counter()
@@ -622,6 +632,7 @@ class DeviceBatch:
             return [v] * nc
 
         pen, gam = per_chain(selection_penalties), per_chain(gammas)
+        uniform = intervals is None and ends is None        # every chain's bins are interval_bp wide
         mult = P.validate_multiplier(multiplier)
         names = [f"chain{i}" for i in range(nc)] if chroms is None else [str(c) for c in chroms]
         iv = [None] * nc if intervals is None else list(intervals)
@@ -658,10 +669,63 @@ class DeviceBatch:
         L.check_value(self._lib.csr_batch_export_peaks(self._ctx, P._vp(cfg), mask, par.size, P._vp(par), P._vp(flags), C.byref(count)))
         peaks = np.zeros(int(count.value), P.PEAK)
         L.check(self._lib.csr_export_fetch(self._ctx, peaks.size, P._vp(peaks)))
-        t_device = time.perf_counter() - t_device
         first = np.searchsorted(peaks["parent"], np.arange(par.size + 1), "left")      # (the peaks come in parent order)
-        out = [None] * nc
         stats = {"chains": len(spans), "parents": int(par.size), "peaks": int(peaks.size), "decided_on_host": 0}
+        by_start = [{} for _ in range(nc)]
+        if width_policy is not None:
+            active = bool(massive_subpeak_cleanup and bool(width_policy.get("active", False)))
+            stats.update({k: 0 for k in K.COUNTERS})
+            for c, _, _ in spans:
+                details[c]["massive_subpeak_cleanup_active"] = active
+                details[c]["massive_subpeak_width_policy"] = dict(width_policy)
+            if active and width_policy.get("width_threshold_bp") is not None and peaks.size:
+                # the children of all chains through one plan call, then the finishing step per segment
+                pol = np.zeros(nc, K.POLICY)
+                for c, _, _ in spans:
+                    pol[c] = K.policy_row(width_policy, cfg[c]["boundary_cost"], int(max(int(min_subpeak_bins), 1)), split_quantile, split_z)
+                kids = np.zeros(peaks.size, K.BATCH_CHILD)
+                kids["start"], kids["end"], kids["chain"] = peaks["untrimmed_start"], peaks["untrimmed_end"], peaks["chain"]
+                edges = None
+                if not uniform:
+                    lens = (kids["end"] - kids["start"] + 2).astype(np.int64)
+                    kids["edge_base"] = np.concatenate(([0], np.cumsum(lens)[:-1]))
+                    edges = np.ascontiguousarray(np.concatenate([np.concatenate((iv[int(k["chain"])][int(k["start"]):int(k["end"]) + 1],
+                                                                                 en[int(k["chain"])][int(k["end"]):int(k["end"]) + 1]))
+                                                                 for k in kids]), dtype=np.int64)
+                seg = np.zeros(K.MAX_SEGMENTS * kids.size, K.SEGMENT)
+                cnt = np.zeros(kids.size, K.COUNTS)
+                total = C.c_int64(0)
+                L.check_value(self._lib.csr_batch_cleanup_plan(
+                    self._ctx, P._vp(pol), mask, kids.size, P._vp(kids), 0 if edges is None else edges.size,
+                    None if edges is None else edges.ctypes.data_as(L.I64P), int(interval_bp) if edges is None else 0, seg.size,
+                    P._vp(seg), C.byref(total), P._vp(cnt)))
+                seg = seg[:int(total.value)]
+                flat = cfg.copy()
+                flat["split"] = 0
+                spar = np.zeros(seg.size, P.PARENT)
+                spar["start"], spar["end"], spar["chain"] = seg["start"], seg["end"], peaks["chain"][seg["child"]]
+                sflags = np.zeros(spar.size, np.int32)
+                L.check_value(self._lib.csr_batch_export_peaks(self._ctx, P._vp(flat), mask, spar.size, P._vp(spar), P._vp(sflags),
+                                                               C.byref(count)))
+                done = np.zeros(int(count.value), P.PEAK)
+                L.check(self._lib.csr_export_fetch(self._ctx, done.size, P._vp(done)))
+                if done.size != seg.size:
+                    raise L.ConsenrichAMDError("narrowPeak clean-up: one record per segment expected")
+                kid_chain = peaks["chain"][seg["child"]]
+                for c, a, b in spans:
+                    sel = np.flatnonzero(kid_chain == c)
+                    if sel.size:
+                        by_start[c] = K.finish_segments(done[sel[0]:sel[-1] + 1], seg[sel], cnt, peaks)
+                    mine = cnt[first[a]:first[b]]
+                    K.count_details(details[c], mine)
+                    for k in K.COUNTERS:
+                        stats[k] += int(mine[k].sum())
+                # from here on the segments' records stand for the children's: parent order is kept
+                peaks = done
+                first = np.searchsorted(peaks["parent"], np.arange(par.size + 1), "left")
+                stats["peaks"] = int(peaks.size)
+        t_device = time.perf_counter() - t_device
+        out = [None] * nc
         for c, a, b in spans:
             mine = peaks[first[a]:first[b]]
             host = bool(np.any(flags[a:b] & L.EXPORT_NONFINITE_SIGNAL))
@@ -672,6 +736,8 @@ class DeviceBatch:
                     P.redo_on_host(mine, state, self.download_scores(c), unc, cfg[c])
                 stats["decided_on_host"] += 1
             rows, meta = P.assemble(names[c], iv[c], en[c], prefix, mine, mult, trim_score_floor, details[c])
+            if width_policy is not None:
+                K.fill_meta(meta, by_start[c], width_policy)
             out[c] = {"rows": rows, "peak_meta": meta, "export_details": details[c], "decided_on_host": host}
         # (device_seconds: the library call and the fetch of the records; the rest is the host's share: runs, gaps, assembly)
         stats["device_seconds"] = t_device

@@ -21,6 +21,11 @@
 // Signal and uncertainty are read through ExportTrack: a float64 array, or a float32 component of the reference-layout fit
 // ((double) xs[:,0]; (double)(float) sqrt(Ps00), the values csr_batch_rocco_scores forms).  The per-parent and per-child routines
 // are __host__ __device__: tests/native/narrowpeak_host_check.hip runs the same code on the CPU.
+//
+// What the reference does to these children under an active width policy -- `_forceMassiveSubpeakSegments`, the forced splits and
+// the contraction of the widest ones -- is csr_cleanup.h: its plan kernel takes children as this file forms them (bins of a score
+// array without a coordinate gap) and returns their final segments.  The second export pass then runs this file's call once more
+// with the SEGMENTS as parents that do not split: k_export_child finishes a segment exactly as it finishes a child.
 #pragma once
 #include "csr_nested.h"
 

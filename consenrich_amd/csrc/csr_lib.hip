@@ -18,6 +18,7 @@
 #include "csr_peakscore.h"
 #include "csr_nested.h"
 #include "csr_export.h"
+#include "csr_cleanup.h"
 #include "csr_depspan.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
@@ -460,6 +461,11 @@ struct csr_ctx : BatchState {
         DevBuf arena, par, base, peaks;
         int64_t nPeaks = 0;
     } exportWs;
+    // massive sub-peak clean-up (csr_host_cleanup.inl): the staged scores and edges, one work double per bin, the children and per
+    // child its segment records, counters and node record
+    struct CleanupWs {
+        DevBuf arena, work, kids, seg, cnt, node;
+    } cleanupWs;
     // stationary-null DWB panel (csr_host_dwb.inl): chain table, weights, templates, the seed's noise stream and the rows of one
     // group of draws; growable, the large ones given back by csr_dwb_panel_end
     struct Dwb {
@@ -920,4 +926,5 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_peakscore.inl"
 #include "csr_host_nested.inl"
 #include "csr_host_export.inl"
+#include "csr_host_cleanup.inl"
 #include "csr_host_depspan.inl"

@@ -714,6 +714,43 @@ def export_peaks_batch(batch: DeviceBatch, nested, *, interval_bp, intervals=Non
     return out
 
 
+def cleanup_peaks_batch(batch: DeviceBatch, exported, *, interval_bp, intervals=None, ends=None, chroms=None, prefix="consenrichROCCO",
+                        multiplier: float = 2.0, use_uncertainty: bool = True, enabled: bool = True):
+    """The link between `export_peaks_batch` and `score_peaks_batch`: `solveRocco`'s massive sub-peak clean-up (peaks.py:7008-7096).
+    The width policy is learned on the host from the kept widths of ALL chains (`meta["end"] - meta["start"]`) with the reference's
+    constants.  If it is not active, the records come back with `export_details["massive_subpeak_width_policy"]` set and nothing
+    else changed.  If it is active, every chain is exported once more under the policy, from resident data in one more round of
+    device calls (`DeviceBatch.narrowpeak_rows(width_policy=...)`), and `rows`, `peak_meta`, `export_details`, `starts` / `ends`
+    become those of the cleaned peak set.  exported: what export_peaks_batch returned.  Returns (records, policy)."""
+    from . import cleanup as K
+
+    nc = len(batch.chain_lens)
+    if len(exported) != nc:
+        raise ValueError("one record per chain")
+    widths = [float(int(m["end"]) - int(m["start"])) for r in exported for m in r["peak_meta"]]
+    policy = K.learn_massive_subpeak_width_policy(widths, enabled=bool(enabled), minBP=K.MIN_BP, alpha=K.WIDTH_ALPHA,
+                                                  bulkQuantile=K.WIDTH_BULK_QUANTILE, maxFraction=K.MAX_FRACTION,
+                                                  minLogGap=K.MIN_LOG_GAP, minPeaks=K.MIN_PEAKS)
+    out = []
+    if not bool(policy.get("active", False)):
+        for r in exported:
+            q = dict(r)
+            q["export_details"] = dict(r["export_details"], massive_subpeak_width_policy=dict(policy))
+            out.append(q)
+        return out, policy
+    got = batch.narrowpeak_rows([r["selection_penalty"] for r in exported], [r["gamma"] for r in exported], intervals=intervals, ends=ends,
+                                interval_bp=interval_bp, chroms=chroms, prefix=prefix, min_subpeak_bins=5, trim_score_floor=0.0,
+                                multiplier=multiplier, use_uncertainty=use_uncertainty, width_policy=policy, massive_subpeak_cleanup=True,
+                                split_quantile=K.SPLIT_QUANTILE, split_z=K.SPLIT_Z)
+    for r, g in zip(exported, got):
+        q = dict(r)
+        q.update(rows=g["rows"], peak_meta=g["peak_meta"], export_details=g["export_details"], decided_on_host=g["decided_on_host"])
+        q["starts"] = np.asarray([m["start_idx"] for m in g["peak_meta"]], np.int64)
+        q["ends"] = np.asarray([m["end_idx"] for m in g["peak_meta"]], np.int64)
+        out.append(q)
+    return out, policy
+
+
 def score_peaks_batch(batch: DeviceBatch, first_pass, panel, *, dependence_spans, random_seed, min_run_bins: int = 1,
                       num_replay: int = 64, draws_per_group: int = 0) -> List[dict]:
     """The next link after `first_pass_peaks_batch`: the reference's DWB peak scoring (`_addDWBPeakScoringToPeakMeta`,

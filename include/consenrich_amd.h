@@ -889,6 +889,73 @@ int csr_batch_export_peaks(csr_ctx *ctx, const csr_export_cfg *cfg, const unsign
                            const csr_export_parent *parents, int32_t *parent_flags, int64_t *count);
 int csr_export_fetch(csr_ctx *ctx, int64_t capacity, csr_export_peak *peaks);
 
+/* ---- the massive sub-peak clean-up: `_forceMassiveSubpeakSegments` (peaks.py:4579-4786) with `_bestMassiveSubpeakSplit`
+ * (3299-3352) and `_contractMassiveSubpeakSegment` (3355-3460), piece level, on host arrays (default context) ----------------
+ * Every value equals the reference's bit for bit.  A CHILD is bins [start, end] (inclusive) of the score array that hold no
+ * coordinate gap; the children are disjoint and ascending.  The coordinates are the n + 1 bin edges (bin i is
+ * [edges[i], edges[i + 1]), non-decreasing), or edges NULL and edge i = origin + i * step.  One wavefront takes one child.
+ *   CSR_CLEANUP_OP_FORCE     the recursion of one child under the policy: forced splits at the best low-score gap, contraction
+ *                            to an adaptive or width-capped core.  A child of L bins ends in at most CSR_CLEANUP_MAX_SEGMENTS
+ *                            segments (every one holds at least ceil(0.05 L) bins); they come back packed, child after child and
+ *                            left to right, *n_segments of them (capacity >= CSR_CLEANUP_MAX_SEGMENTS * n_children always
+ *                            suffices), with counts[k].n_segments per child (the reference's num_subpeaks) and its five counters.
+ *                            CSR_CLEANUP_SPLIT_FROM_PARENT is set where a child ends in several segments or in a moved one; the
+ *                            caller ORs the child's own flag.  policy.contract_threshold is the caller's
+ *                            min(contract_width_bp or min_bp or 7500, threshold).  A child narrower than the threshold (or any
+ *                            child under a NaN threshold) is its own segment.
+ *   CSR_CLEANUP_OP_SPLIT     nodes[k] = the best split of child k's scores with min_run as `minRunBins` (found 0: None).
+ *   CSR_CLEANUP_OP_CONTRACT  nodes[k] = the contraction of child k with contract_threshold as `thresholdBP` and min_run as
+ *                            `minRunBins` (found 0: None).
+ * Checked before any launch: a non-finite score inside a child that the call would evaluate returns CSR_ERR_VALUE with the
+ * reference's "`scores` contains non-finite values"; a max_depth above CSR_CLEANUP_MAX_DEPTH, a non-finite split quantile,
+ * minimum z or boundary cost return CSR_ERR_VALUE.  Order statistics come from a sort that puts -0.0 and +0.0 in either order
+ * (NumPy: equal): where every score of a node is a zero, `z` of its refused split may differ in the sign of a zero.
+ * CSR_CLEANUP_SORT_TILE: node lengths up to it are sorted in LDS, longer ones in global memory.  Additive to ABI 6. */
+#define CSR_CLEANUP_MAX_SEGMENTS 20
+#define CSR_CLEANUP_MAX_DEPTH 32
+#define CSR_CLEANUP_SORT_TILE 2048
+enum { CSR_CLEANUP_OP_FORCE = 0, CSR_CLEANUP_OP_SPLIT = 1, CSR_CLEANUP_OP_CONTRACT = 2 };
+enum { CSR_CLEANUP_MODE_NONE = 0, CSR_CLEANUP_MODE_UNSPLIT = 1, CSR_CLEANUP_MODE_SPLIT = 2, CSR_CLEANUP_MODE_ADAPTIVE_CORE = 3,
+       CSR_CLEANUP_MODE_WIDTH_CAPPED_CORE = 4 };
+enum { CSR_CLEANUP_CANDIDATE = 1, CSR_CLEANUP_APPLIED = 2, CSR_CLEANUP_HAS_SPLIT = 4, CSR_CLEANUP_HAS_CORE_WIDTH = 8,
+       CSR_CLEANUP_HAS_CORE_FLOOR = 16, CSR_CLEANUP_MOVED = 32, CSR_CLEANUP_SPLIT_FROM_PARENT = 64 };
+enum { CSR_CLEANUP_NONFINITE = 1, CSR_CLEANUP_OVERFLOW = 2 };    /* csr_cleanup_counts.flags */
+typedef struct csr_cleanup_policy {
+    double threshold, contract_threshold, split_quantile, min_split_z, boundary_cost;
+    int32_t min_run, max_depth;
+} csr_cleanup_policy;
+typedef struct csr_cleanup_child {
+    int64_t start, end;
+} csr_cleanup_child;
+typedef struct csr_cleanup_segment {
+    int64_t start, end, core_width_bp;          /* core_width_bp: with CSR_CLEANUP_HAS_CORE_WIDTH */
+    double gain, z, core_score_floor;           /* gain, z, gap_bins: with CSR_CLEANUP_HAS_SPLIT; the floor: HAS_CORE_FLOOR */
+    int32_t gap_bins, mode, flags, child;
+} csr_cleanup_segment;
+typedef struct csr_cleanup_counts {
+    int32_t candidates, splits, segments_added, evaluated, contracts, n_segments, flags, reserved;
+} csr_cleanup_counts;
+typedef struct csr_cleanup_node {
+    int64_t a, b, width;                        /* split: the gap, local to the child; contract: the core's bins and width */
+    double baseline, scale, deficit, gain, z, floor;
+    int32_t found, mode, gap_bins, reserved;
+} csr_cleanup_node;
+/* The same recursion on the RESIDENT score tracks of a batch (no resident array changes): children as (chain, bins of the chain),
+ * ascending by (chain, start) and disjoint, a policy per chain (those of chains the call takes are read), the coordinates as one
+ * packed array -- child k's n_k + 1 edges start at edges[edge_base] -- or edges NULL and equally wide bins of `step`.  The segments
+ * come back in bins of their chain.  A non-finite resident score inside a candidate returns CSR_ERR_VALUE with the reference's
+ * text (found by the kernel). */
+typedef struct csr_cleanup_batch_child {
+    int64_t start, end, edge_base;
+    int32_t chain, reserved;
+} csr_cleanup_batch_child;
+int csr_batch_cleanup_plan(csr_ctx *ctx, const csr_cleanup_policy *policies, const unsigned char *chain_mask, int64_t n_children,
+                           const csr_cleanup_batch_child *children, int64_t n_edges, const int64_t *edges, int64_t step,
+                           int64_t capacity, csr_cleanup_segment *segments, int64_t *n_segments, csr_cleanup_counts *counts);
+int csr_cleanup_plan(int32_t op, int64_t n, const double *scores, const int64_t *edges, int64_t origin, int64_t step,
+                     int64_t n_children, const csr_cleanup_child *children, const csr_cleanup_policy *policy, int64_t capacity,
+                     csr_cleanup_segment *segments, int64_t *n_segments, csr_cleanup_counts *counts, csr_cleanup_node *nodes);
+
 /* ---- the dependence span: the device stages of pyx:3360-4120 `cchooseDependenceSpan` (helpers pyx:2645-3357) ------------------
  * Three stages, each on host arrays (default context; mats[k] = n_rows x n_bins[k] float32 in C order, staged one chromosome or one
  * window set at a time) and on the RESIDENT data of the listed chains of a batch (chains[k]: a chain index; a fold chain is left
