@@ -340,6 +340,7 @@ SYMBOLS = {
     "csr_batch_download_inputs": (C.c_int, [C.c_void_p, C.c_int32, FP, FP]),
     "csr_batch_set_chain_q": (C.c_int, [C.c_void_p, DP]),
     "csr_batch_step": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, DP, DP]),
+    "csr_batch_set_step_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]),
     "csr_batch_step_forward": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, DP, DP]),
     "csr_batch_objective_terms": (C.c_int, [C.c_void_p, C.POINTER(ObjectiveCfg), C.POINTER(ObjectiveTerms)]),
     "csr_batch_phase_tracks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, DP, DP, C.POINTER(C.c_int32)]),

@@ -169,6 +169,21 @@ class DeviceBatch:
                 raise ValueError("Q0 must be (2,2) or (1,1)")
         L.check(self._lib.csr_batch_set_chain_q(self._ctx, L.dp(flat)))
 
+    def set_step_groups(self, tail_groups=None, epilogue_groups=None):
+        """A test seam (csr_batch_set_step_groups): the early group of every chain of a pipelined step -- one index per chain, -1 =
+        the remainder -- for its tails and for its NIS / NLL epilogues; None leaves that kind to the host's clock, both None clear
+        the script.  It holds until cleared or until the batch is configured again.  A bad script raises ValueError and leaves
+        the previous one in force."""
+        arrs = [None if g is None else np.ascontiguousarray(g, np.int32) for g in (tail_groups, epilogue_groups)]
+        for a in arrs:
+            if a is not None and a.ndim != 1:
+                raise ValueError("one group index per chain")
+        sizes = {int(a.size) for a in arrs if a is not None}
+        if len(sizes) > 1:
+            raise ValueError("tail and epilogue groups of different lengths")
+        ptrs = [None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32)) for a in arrs]
+        L.check_value(self._lib.csr_batch_set_step_groups(self._ctx, ptrs[0], ptrs[1], sizes.pop() if sizes else 0))
+
     def set_tuning(self, block_len=0, warm_p=-1, warm_x=-1, warm_b=-1):
         L.check(self._lib.csr_set_tuning(self._ctx, int(block_len), int(warm_p), int(warm_x), int(warm_b)))
 

@@ -66,6 +66,26 @@ extern "C" int csr_batch_set_chain_q(csr_ctx *c, const double *q) {
     return 0;
 }
 
+// Scripted grouping of a pipelined step (step_pipelined; a test seam, off unless set): checked as a whole before anything changes
+extern "C" int csr_batch_set_step_groups(csr_ctx *c, const int32_t *tail_group, const int32_t *epilogue_group, int32_t n_chains) {
+    CHECK(need(c));
+    if (tail_group == nullptr && epilogue_group == nullptr) {
+        c->tailScript.clear();
+        c->epiScript.clear();
+        return 0;
+    }
+    const int nc = (int)c->chains.size();
+    if (n_chains != nc) return value_error("step groups: %d entries for a batch of %d chains", (int)n_chains, nc);
+    if (tail_group)
+        if (const char *e = script_error(tail_group, nc, MAX_EARLY_TAILS)) return value_error("step groups: tails (cap %d): %s", MAX_EARLY_TAILS, e);
+    if (epilogue_group)
+        if (const char *e = script_error(epilogue_group, nc, MAX_EARLY_EPILOGUES))
+            return value_error("step groups: epilogues (cap %d): %s", MAX_EARLY_EPILOGUES, e);
+    if (tail_group) c->tailScript.assign(tail_group, tail_group + nc); else c->tailScript.clear();
+    if (epilogue_group) c->epiScript.assign(epilogue_group, epilogue_group + nc); else c->epiScript.clear();
+    return 0;
+}
+
 extern "C" int csr_batch_configure(csr_ctx *c, const csr_model *mdl, int64_t m, int32_t n_chains,
                                    const int64_t *chain_len) {
     if (!c || !mdl || !chain_len) return fail("null argument");

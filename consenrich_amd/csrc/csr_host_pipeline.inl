@@ -1546,6 +1546,8 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     // timer slack and, around the moment the PREVIOUS launch of this context ended, it polls without sleeping)
     TimerSlack slack;
     std::vector<unsigned> done((size_t)nc, 0u);
+    const int32_t *const tailScript = c->tailScript.empty() ? nullptr : c->tailScript.data();
+    const int32_t *const epiScript = c->epiScript.empty() ? nullptr : c->epiScript.data();
     const auto tLoop = std::chrono::steady_clock::now();
     const double expectEnd = c->lastSbLoopUs;
     for (;;) {
@@ -1558,8 +1560,11 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
         if (!nearEnd) std::this_thread::sleep_for(std::chrono::microseconds(20));
         for (int i = 0; i < nc; ++i) done[(size_t)i] = __atomic_load_n(&c->hDone[i], __ATOMIC_ACQUIRE);
         // (an epilogue group is an upload and a launch: never inside the interval in which the end of the state chain is expected)
-        if (c->epiPct > 0 && !nearEnd && epis.pick(done.data(), c->epiPct, egrp)) CHECK(launch_epilogue());
-        if (tails.pick(done.data(), tails.handed() == 0 ? c->tailFirstPct : c->tailNextPct, grp)) {
+        // (a scripted grouping, csr_batch_set_step_groups: the next group goes out when all its chains are final, whatever the clock says)
+        if (epiScript ? epis.pick_scripted(done.data(), epiScript, egrp) : c->epiPct > 0 && !nearEnd && epis.pick(done.data(), c->epiPct, egrp))
+            CHECK(launch_epilogue());
+        if (tailScript ? tails.pick_scripted(done.data(), tailScript, grp)
+                       : tails.pick(done.data(), tails.handed() == 0 ? c->tailFirstPct : c->tailNextPct, grp)) {
             StreamScope onTail(c, c->tail);
             CHECK(launch_tail());
         }
@@ -1568,7 +1573,19 @@ static int step_pipelined(csr_ctx *c, uint32_t flags, uint32_t what, bool *handl
     // pass form rewrites the whole track from the cold prior: sb_finish waits for the groups already launched and everything is redone)
     const int64_t bail0 = c->rs.sb_bailouts;
     CHECK(sb_finish(c, false));
-    if (c->rs.sb_bailouts != bail0 && tails.handed() + epis.handed() > 0) { tails.clear(); epis.clear(); }
+    const bool bailed = c->rs.sb_bailouts != bail0;
+    if (bailed && tails.handed() + epis.handed() > 0) { tails.clear(); epis.clear(); }
+    // ---- a scripted grouping is the same whatever the timing: every chain is final now, and the scripted groups the watch loop
+    // did not reach go out one by one as it would have launched them (sb_finish waited for the main stream: nothing of the state
+    // chain is in flight).  After a bail-out everything is one remainder, scripted or not.
+    if (!bailed && (tailScript || epiScript)) {
+        std::fill(done.begin(), done.end(), 1u);
+        while (tailScript && tails.pick_scripted(done.data(), tailScript, grp)) {
+            StreamScope onTail(c, c->tail);
+            CHECK(launch_tail());
+        }
+        while (epiScript && epis.pick_scripted(done.data(), epiScript, egrp)) CHECK(launch_epilogue());
+    }
     // ---- the remaining chains: on the main stream, behind the state chain and beside whatever the tail stream still has to do
     if (tails.rest(grp)) CHECK(launch_tail());
     // ---- the epilogue of the chains that have none yet, on the side stream (the state chain has ended: nothing to wait for)

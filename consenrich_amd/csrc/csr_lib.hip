@@ -337,6 +337,9 @@ struct BatchState {
     GroupSlots<unsigned char, MAX_EARLY_TAILS + 1> tailMasks;
     GroupSlots<unsigned char, MAX_EARLY_EPILOGUES + 1> epiMasks;
     GroupSlots<ResidRun, MAX_EARLY_TAILS + 1> tailRuns;
+    // csr_batch_set_step_groups (a test seam): the group of every chain, -1 = the remainder; empty = the watch loop groups the
+    // chains by its thresholds as they become final
+    std::vector<int32_t> tailScript, epiScript;
     bool pfPending = false;
     // the reference-layout process-noise array holds the constant fill of THESE values in every row (k_fill_rows): a step with the
     // same constant process noise does not write it again (a 1/8-genome step: one side-stream launch and two stream waits less)

@@ -36,6 +36,20 @@ inline std::pair<int64_t, int64_t> group_span(const std::vector<ChainRun> &runs)
     return {g0, g1 - g0};
 }
 
+// What is wrong with a scripted grouping of n chains (ChainSet::pick_scripted), or nullptr: every entry is -1 (remainder) or a group
+// index below `cap`, and the indices in use are 0 .. k-1 without a hole
+inline const char *script_error(const int32_t *script, int64_t n, int cap) {
+    std::vector<unsigned char> used((size_t)cap, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        if (script[i] < -1) return "a group index below -1";
+        if (script[i] >= cap) return "a group index at or above the cap";
+        if (script[i] >= 0) used[(size_t)script[i]] = 1;
+    }
+    for (int g = 1; g < cap; ++g)
+        if (used[(size_t)g] && !used[(size_t)g - 1]) return "group indices with a hole";
+    return nullptr;
+}
+
 // The chains of a batch, handed out in disjoint groups: at most `cap` early ones (pick) while the state chain runs, then whatever
 // is left (rest).  The group just handed out owns mask / run-table slot handed() - 1.
 class ChainSet {
@@ -60,6 +74,20 @@ public:
         int64_t bins = 0;
         for (size_t i = 0; i < taken.size(); ++i) bins += (grp[i] = !taken[i] && done[i] != 0u) ? chains[i].n : 0;
         return bins > 0 && bins * 100 >= total * pct && take(grp);
+    }
+    // A SCRIPTED hand-out (csr_batch_set_step_groups, a test seam): script[i] is the group of chain i, -1 = the remainder.
+    // grp := the chains of group handed(); they are taken iff there is such a group and every one of them is final -- no
+    // threshold, no timing.  (The script is validated where it is set: groups 0 .. k-1 without a hole, k <= cap.  After clear()
+    // the count goes on, so the groups handed out before it are not handed out again.)
+    bool pick_scripted(const unsigned *done, const int32_t *script, std::vector<unsigned char> &grp) {
+        if (count >= cap) return false;
+        bool any = false, final = true;
+        for (size_t i = 0; i < taken.size(); ++i) {
+            grp[i] = script[i] == count && !taken[i];
+            any = any || grp[i];
+            final = final && (!grp[i] || done[i] != 0u);
+        }
+        return any && final && take(grp);
     }
     // grp := the chains not taken; they are taken as the final group (false: none is left)
     bool rest(std::vector<unsigned char> &grp) {

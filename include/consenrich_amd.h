@@ -186,6 +186,14 @@ int csr_batch_forward_backward(csr_ctx *ctx, uint32_t flags, double *sum_d, doub
  * noise, >= 2 chains) start the smoother / residuals of every chain as soon as THAT chain's filtered state stands, while the
  * state chain of slower chains is still running (csr_run_stats.tail_groups counts the groups). */
 int csr_batch_step(csr_ctx *ctx, uint32_t flags, uint32_t what, double *sum_d, double *sum_nll);
+/* A TEST SEAM, off unless set: which chains of such a step go out together.  By default the host groups the chains as they become
+ * final (by its clock); with a script the grouping is the same whatever the timing -- only whether a group overlaps the running
+ * state chain still depends on it.  tail_group / epilogue_group: n_chains entries each, the index of the chain's early group
+ * (tails: below 6; NIS / NLL epilogues: below 8; the indices in use are 0..k-1 without a hole) or -1 = the remainder, which follows
+ * the scripted groups.  A NULL array leaves that kind unscripted; both NULL clear the script.  The script belongs to the batch
+ * (csr_batch_configure drops it) and holds for every later step; a step that does not pipeline its tail ignores it.  Results do
+ * not depend on it.  A wrong n_chains or a bad index returns CSR_ERR_VALUE (csr_last_error says which) and changes nothing. */
+int csr_batch_set_step_groups(csr_ctx *ctx, const int32_t *tail_group, const int32_t *epilogue_group, int32_t n_chains);
 /* The FORWARD FILTER ALONE in one call (cforwardPass without cbackwardPass, pyx:6393-6632 -- BASELINE config 2): csr_batch_stats +
  * csr_batch_forward + csr_batch_export(what & CSR_EXPORT_FORWARD) + csr_batch_sums.  Same kernels and results as the separate
  * calls; no smoother, no residuals. */

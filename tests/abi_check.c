@@ -23,5 +23,6 @@ int main(void) {
     if (csr_solve_background(0, NULL, NULL, NULL, 1.0, 0.0, 0, 0, NULL, NULL, NULL) == 0) return 2;
     if (strlen(csr_last_error()) == 0) return 3;
     if (csr_format_bedgraph("chr1", 4, NULL, NULL, 0, 1, 0, NULL, 0, NULL, 0) >= 0) return 4;
+    if (csr_batch_set_step_groups(NULL, NULL, NULL, 0) == 0) return 5;     /* no context: refused, script or not */
     return 0;
 }

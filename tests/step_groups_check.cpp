@@ -128,6 +128,107 @@ int main() {
             for (size_t k = 0; k < t.size(); ++k) { REQUIRE(!(g[k] && all[k])); all[k] |= g[k]; bins += g[k] ? t[k].n : 0; }
         REQUIRE(all == (Mask{1, 1, 1, 1, 1, 1}) && bins == total && e.handed() == 3);     // {5}, {0, 3} ({0} alone is under 1 %), the rest
     }
+    // ---- ChainSet::pick_scripted (csr_batch_set_step_groups): the groups in the script's order, each when ALL its chains are final
+    {
+        // tails of the scattered script of tests/test_gpu_step_schedules.py on six chains: {0, 5}, {2, 3}, {1}; chain 4 remains
+        const int32_t script[6] = {0, 2, 1, 1, -1, 0};
+        REQUIRE(script_error(script, 6, MAX_EARLY_TAILS) == nullptr);
+        std::vector<unsigned> done(t.size(), 0u);
+        Mask g(t.size(), 7);
+        ChainSet s(t, MAX_EARLY_TAILS);
+        REQUIRE(!s.pick_scripted(done.data(), script, g) && s.handed() == 0);
+        // groups 1 and 2 are final, group 0 is not: nothing goes out (the order is the script's, not the clock's)
+        done[1] = done[2] = done[3] = done[4] = 1u;
+        REQUIRE(!s.pick_scripted(done.data(), script, g) && s.handed() == 0);
+        done[0] = 1u;                                               // one member of group 0 is final, the other is not
+        REQUIRE(!s.pick_scripted(done.data(), script, g) && s.handed() == 0 && g == (Mask{1, 0, 0, 0, 0, 1}));
+        done[5] = 1u;
+        REQUIRE(s.pick_scripted(done.data(), script, g) && s.handed() == 1 && g == (Mask{1, 0, 0, 0, 0, 1}));
+        {
+            // a scattered group: two runs, the span over the whole batch, the mask trims what lies between
+            const auto r = chain_runs(t, g);
+            REQUIRE(r.size() == 2 && same(r[0], 0, 64, 0, 1) && same(r[1], 448, 4160, 7, 72));
+            REQUIRE(group_span(r) == std::make_pair((int64_t)0, (int64_t)2));
+        }
+        REQUIRE(s.pick_scripted(done.data(), script, g) && s.handed() == 2 && g == (Mask{0, 0, 1, 1, 0, 0}));
+        {
+            const auto r = chain_runs(t, g);                        // two adjacent chains: one run
+            REQUIRE(r.size() == 1 && same(r[0], 128, 192, 2, 5));
+            REQUIRE(group_span(r) == std::make_pair((int64_t)0, (int64_t)1));
+        }
+        REQUIRE(s.pick_scripted(done.data(), script, g) && s.handed() == 3 && g == (Mask{0, 1, 0, 0, 0, 0}));
+        REQUIRE(!s.pick_scripted(done.data(), script, g) && s.handed() == 3 && g == (Mask{0, 0, 0, 0, 0, 0}));     // no group 3
+        REQUIRE(s.rest(g) && g == (Mask{0, 0, 0, 0, 1, 0}) && s.handed() == 4);
+        REQUIRE(!s.rest(g) && s.handed() == 4);
+    }
+    {
+        // a group whose runs lie in the second wavefront-group only, behind chains that are not in it
+        const std::vector<ChainInfo> far = table({4096, 64, 65, 1}, 64);    // blocks 0-63, 64, 65-66, 67
+        const int32_t script[4] = {-1, 0, -1, 0};
+        const unsigned done[4] = {0u, 1u, 0u, 1u};
+        Mask g(4, 0);
+        ChainSet s(far, MAX_EARLY_TAILS);
+        REQUIRE(s.pick_scripted(done, script, g) && g == (Mask{0, 1, 0, 1}));
+        const auto r = chain_runs(far, g);
+        REQUIRE(r.size() == 2 && same(r[0], 4096, 64, 64, 65) && same(r[1], 4288, 64, 67, 68));
+        REQUIRE(group_span(r) == std::make_pair((int64_t)1, (int64_t)1));
+        REQUIRE(s.rest(g) && g == (Mask{1, 0, 1, 0}));
+    }
+    {
+        // every chain in group 0: it goes out when the last chain is final, and no remainder is left
+        const int32_t script[6] = {0, 0, 0, 0, 0, 0};
+        std::vector<unsigned> done(t.size(), 1u);
+        Mask g(t.size(), 0);
+        ChainSet s(t, MAX_EARLY_EPILOGUES);
+        done[3] = 0u;
+        REQUIRE(!s.pick_scripted(done.data(), script, g) && s.handed() == 0);
+        done[3] = 1u;
+        REQUIRE(s.pick_scripted(done.data(), script, g) && g == (Mask{1, 1, 1, 1, 1, 1}) && s.handed() == 1);
+        REQUIRE(!s.pick_scripted(done.data(), script, g) && !s.rest(g) && s.handed() == 1);
+        // ... and none: all -1, everything is the remainder
+        const int32_t none[6] = {-1, -1, -1, -1, -1, -1};
+        ChainSet z(t, MAX_EARLY_EPILOGUES);
+        REQUIRE(script_error(none, 6, MAX_EARLY_EPILOGUES) == nullptr);
+        REQUIRE(!z.pick_scripted(done.data(), none, g) && z.handed() == 0);
+        REQUIRE(z.rest(g) && g == (Mask{1, 1, 1, 1, 1, 1}) && z.handed() == 1);
+    }
+    {
+        // the cap: six singleton groups of six chains is what a script may hold for tails; a ChainSet with a smaller cap stops there
+        const int32_t script[6] = {5, 4, 3, 2, 1, 0};
+        REQUIRE(script_error(script, 6, MAX_EARLY_TAILS) == nullptr && script_error(script, 6, MAX_EARLY_TAILS - 1) != nullptr);
+        std::vector<unsigned> done(t.size(), 1u);
+        Mask g(t.size(), 0);
+        ChainSet s(t, MAX_EARLY_TAILS);
+        for (int k = 0; k < 6; ++k) {
+            REQUIRE(s.pick_scripted(done.data(), script, g) && s.handed() == k + 1);
+            for (int i = 0; i < 6; ++i) REQUIRE(g[(size_t)i] == (i == 5 - k));
+        }
+        REQUIRE(!s.pick_scripted(done.data(), script, g) && !s.rest(g) && s.handed() == 6);
+        ChainSet small(t, 2);
+        REQUIRE(small.pick_scripted(done.data(), script, g) && small.pick_scripted(done.data(), script, g));
+        REQUIRE(!small.pick_scripted(done.data(), script, g) && small.handed() == 2);       // the cap, although group 2 is final
+        REQUIRE(small.rest(g) && g == (Mask{1, 1, 1, 1, 0, 0}) && small.handed() == 3);
+        // clear() after some groups (a bail-out): every chain is to be done again as ONE remainder; the count goes on, so the
+        // scripted pick does not hand the groups that went out a second time and no slot is used twice
+        ChainSet b(t, MAX_EARLY_TAILS);
+        REQUIRE(b.pick_scripted(done.data(), script, g) && b.pick_scripted(done.data(), script, g) && b.handed() == 2);
+        b.clear();
+        REQUIRE(b.rest(g) && g == (Mask{1, 1, 1, 1, 1, 1}) && b.handed() == 3);
+        ChainSet b2(t, MAX_EARLY_TAILS);
+        REQUIRE(b2.pick_scripted(done.data(), script, g) && b2.handed() == 1);
+        b2.clear();
+        REQUIRE(b2.pick_scripted(done.data(), script, g) && g == (Mask{0, 0, 0, 0, 1, 0}) && b2.handed() == 2);   // group 1, not group 0 again
+    }
+    // ---- script_error: what csr_batch_set_step_groups rejects
+    {
+        const int32_t below[3] = {0, -2, -1}, atCap[3] = {0, 1, MAX_EARLY_TAILS}, hole[3] = {0, 2, -1}, noZero[3] = {1, -1, -1};
+        const int32_t ok[3] = {1, 0, 1}, top[8] = {0, 1, 2, 3, 4, 5, 6, 7};
+        REQUIRE(script_error(below, 3, MAX_EARLY_TAILS) != nullptr && script_error(atCap, 3, MAX_EARLY_TAILS) != nullptr);
+        REQUIRE(script_error(hole, 3, MAX_EARLY_TAILS) != nullptr && script_error(noZero, 3, MAX_EARLY_TAILS) != nullptr);
+        REQUIRE(script_error(ok, 3, MAX_EARLY_TAILS) == nullptr && script_error(atCap, 3, MAX_EARLY_EPILOGUES) != nullptr);   // (a hole under the larger cap)
+        REQUIRE(script_error(top, 8, MAX_EARLY_EPILOGUES) == nullptr && script_error(top, 8, MAX_EARLY_TAILS) != nullptr);
+        REQUIRE(script_error(ok, 0, MAX_EARLY_TAILS) == nullptr);
+    }
     printf("step_groups_check ok\n");
     return 0;
 }

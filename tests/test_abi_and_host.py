@@ -219,8 +219,8 @@ def test_header_is_plain_c_and_library_links_from_c(tmp_path):
 
 def test_step_groups_header_hands_out_chains_as_the_pipelined_step_expects(tmp_path):
     """consenrich_amd/csrc/csr_step_groups.h is plain C++17: tests/step_groups_check.cpp (runs of chains, their span of
-    wavefront-groups, the thresholds / cap / remainder / bail-out of ChainSet) built stand-alone under the address and
-    undefined-behaviour sanitizers."""
+    wavefront-groups, the thresholds / cap / remainder / bail-out of ChainSet, its scripted pick and what a script may hold) built
+    stand-alone under the address and undefined-behaviour sanitizers."""
     import shutil
     import subprocess
 

@@ -18,14 +18,10 @@ import os
 import numpy as np
 import pytest
 
-import cases
 from conftest import gpu_available
+from tail_cases import N_LIST, OWN, assert_same as _assert_same, bits as _bits, make_inputs, pipelines as _pipelines, run as _run
 
 pytestmark = pytest.mark.gpu
-
-N_LIST = [1, 63, 64, 65, 127, 128, 129, 257, 4097, 8193, 20000]
-NAMES = ("D", "xf", "Pf", "pnoise", "xs", "Ps", "lag", "resid")
-OWN = ("CONSENRICH_AMD_TAIL_SPLIT", "CONSENRICH_AMD_TAIL_PCT", "CONSENRICH_AMD_SB_SPIN_LIMIT", "CONSENRICH_AMD_EPILOGUE_PCT")
 
 
 @pytest.fixture(scope="module")
@@ -37,82 +33,9 @@ def product():
     return cconsenrich
 
 
-def _pipelines():
-    """False when the suite runs under a mode switch (scripts/suite_variants.sh) that keeps a bit-exact step from pipelining at all:
-    the comparisons still hold, the counts of groups and bail-outs do not apply."""
-    e = os.environ.get
-    return (e("CONSENRICH_AMD_SB_ASYNC", "1") != "0" and e("CONSENRICH_AMD_SEQ_STATE", "0") == "0" and e("CONSENRICH_AMD_DEFER", "1") != "0"
-            and e("CONSENRICH_AMD_XTOL_ULPS", "0") == "0")
-
-
 @pytest.fixture(scope="module")
 def inputs():
-    """The chains' data (computed once, never changed): per m, per chain (data, munc); multipliers per chain."""
-    sets = {m: [cases.synth(n, m, 9100 + 10 * m + c, mask_frac=0.01, outlier_frac=0.01) for c, n in enumerate(N_LIST)] for m in (4, 5)}
-    mult = [cases.multipliers(n, 9300 + c) for c, n in enumerate(N_LIST)]
-    return sets, mult
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
-
-
-def _flags(variant):
-    from consenrich_amd import _lib as L
-
-    flags = L.RETURN_NLL
-    if variant == "multipliers":
-        flags |= L.USE_LAMBDA | L.USE_KAPPA | L.USE_QSCALE
-    if variant == "nll_in_d":
-        flags |= L.NLL_IN_D
-    return flags
-
-
-def _run(monkeypatch, inputs, env, m, block, variant, profile=False):
-    """Two steps of a fresh batch: every array of every chain after the first and after the second, both sums, the run counters."""
-    from consenrich_amd import _lib as L
-    from consenrich_amd.batch import DeviceBatch, ModelParams
-
-    sets, mult = inputs
-    for k in OWN:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("CONSENRICH_AMD_BLOCK", str(block))
-    monkeypatch.setenv("CONSENRICH_AMD_SB_BINS", "4096")
-    monkeypatch.setenv("CONSENRICH_AMD_WARM", "-1,-1,384")
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    what = L.EXPORT_FORWARD | L.EXPORT_SMOOTH | L.EXPORT_RESID
-    flags = _flags(variant)
-    out = {}
-    with DeviceBatch(0) as b:
-        b.configure(ModelParams(state_dim=2), m, N_LIST)
-        for c, (d_, v_) in enumerate(sets[m]):
-            b.upload(c, d_, v_)
-            if variant == "multipliers":
-                lam, kap, qs = mult[c]
-                b.upload_multipliers(c, lam, np.clip(kap, 0.25, 4.0), qs)
-        if variant == "per_chain_q":
-            b.set_chain_q([np.diag([1e-3 * (1 + c), 1e-4 * (1 + 0.5 * c)]).astype(np.float32) for c in range(len(N_LIST))])
-        if profile:
-            b.profile(True)
-        for step in range(2):
-            sd, sn = b.step(flags, what)
-            out[("sumD", step)], out[("sumNLL", step)] = np.array(sd), np.array(sn)
-            for c in range(len(N_LIST)):
-                for name in NAMES:
-                    out[(c, name, step)] = b.download(c, name)
-        if profile:
-            out["launches"] = {k: v[0] for k, v in b.kernel_times().items()}
-            b.profile(False)
-        out["stats"] = b.run_stats()
-    return out
-
-
-def _assert_same(got, ref, msg):
-    for key, val in ref.items():
-        if key in ("stats", "launches"):
-            continue
-        assert np.array_equal(_bits(val), _bits(got[key])), (msg, key)
+    return make_inputs()
 
 
 @pytest.mark.parametrize("variant", ["plain", "multipliers", "nll_in_d", "per_chain_q"])
