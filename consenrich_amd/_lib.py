@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libconsenrich_amd.so")
 
@@ -508,3 +510,31 @@ def fp(a):
 
 def dp(a):
     return None if a is None else a.ctypes.data_as(DP)
+
+
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _i32p(a):
+    return a.ctypes.data_as(I32P)
+
+
+def _i64p(a):
+    return a.ctypes.data_as(I64P)
+
+
+def _f64(x):
+    return np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1), dtype=np.float64)
+
+
+def _i64(x):
+    return np.ascontiguousarray(np.asarray(x, dtype=np.int64).reshape(-1), dtype=np.int64)
+
+
+def _c_int(v) -> int:
+    """A Cython `int` argument: truncated like C, OverflowError outside int32 (pyx:8850-8851, 8882)."""
+    v = int(v)
+    if not -(1 << 31) <= v < (1 << 31):
+        raise OverflowError("value too large to convert to int")
+    return v

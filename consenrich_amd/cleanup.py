@@ -24,6 +24,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._lib import _vp
 
 # the reference's constants (constants.py:541-552, peaks.py:120)
 CLEANUP_DEFAULT = True
@@ -55,10 +56,6 @@ NODE = np.dtype([("a", "<i8"), ("b", "<i8"), ("width", "<i8"), ("baseline", "<f8
                  ("gain", "<f8"), ("z", "<f8"), ("floor", "<f8"), ("found", "<i4"), ("mode", "<i4"), ("gap_bins", "<i4"),
                  ("reserved", "<i4")])
 COUNTERS = ("candidates", "splits", "segments_added", "evaluated", "contracts")
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _i32(v):

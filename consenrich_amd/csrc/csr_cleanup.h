@@ -25,10 +25,9 @@
 // the sign travels into a zero deficit and from there into `z` (a +-0.0) of a split that is refused anyway (gain <= 0).
 #pragma once
 #include "csr_export.h"
+#include "csr_np_order.h"
 
 namespace csr {
-
-#define CSR_HD __host__ __device__ __forceinline__
 
 #define CLEANUP_SORT_TILE 2048          // doubles of LDS per wavefront: 16 KiB, ten wavefronts' worth in a CU's 160 KiB
 // A leaf of the recursion holds at least minBins >= ceil(0.05 L) bins of a child of L bins, a split is accepted only if both
@@ -187,8 +186,8 @@ CSR_HD CleanupStats cleanup_node_stats(const T &tm, const double *x, double *w, 
     tm.sync();
     cleanup_sort(tm, w, n);
     double scale = 1.4826 * cleanup_sorted_median(w, n);
-    if (!nested_finite(scale) || scale <= 1.0e-12) scale = iqr / 1.349;
-    if (!nested_finite(scale) || scale <= 1.0e-12) scale = 1.0;
+    if (!np_finite(scale) || scale <= 1.0e-12) scale = iqr / 1.349;
+    if (!np_finite(scale) || scale <= 1.0e-12) scale = 1.0;
     r.scale = scale;
     tm.sync();
     return r;
@@ -258,7 +257,7 @@ CSR_HD CleanupCore cleanup_contract(const T &tm, const double *x, const CleanupC
     r.floor = 0.0;
     r.mode = CSR_CLEANUP_MODE_NONE;
     const int64_t original = co.width(s, s + n - 1);
-    if (!nested_finite(thr) || thr <= 0.0) return r;
+    if (!np_finite(thr) || thr <= 0.0) return r;
     // the maximum and its tolerance mask
     double mx = x[0];
     for (int64_t i = tm.lane(); i < n; i += tm.width()) mx = x[i] > mx ? x[i] : mx;
@@ -291,7 +290,7 @@ CSR_HD CleanupCore cleanup_contract(const T &tm, const double *x, const CleanupC
     const int64_t c0 = di < n ? di : 0;
     // the adaptive core: tried only if maxScore - low > 1e-12 and the centre bin is kept
     const double dynamic = mx - low;
-    if (nested_finite(dynamic) && dynamic > 1.0e-12) {
+    if (np_finite(dynamic) && dynamic > 1.0e-12) {
         const double floor = low + 0.5 * dynamic;
         if (x[c0] >= floor) {
             int64_t left = c0, right = c0;
@@ -403,7 +402,7 @@ CSR_HD void cleanup_plan_child(const T &tm, const CleanupArgs &a, int64_t c) {
     // a candidate with a non-finite score is the caller's (reachable only without the sub-peak split)
     {
         int64_t bad = 0;
-        for (int64_t i = tm.lane(); i < L; i += tm.width()) bad += nested_finite(x0[i]) ? 0 : 1;
+        for (int64_t i = tm.lane(); i < L; i += tm.width()) bad += np_finite(x0[i]) ? 0 : 1;
         if (tm.sum(bad) > 0) {
             cn.flags |= CSR_CLEANUP_NONFINITE;
             emit(root, kid.start, kid.end, false, false, CSR_CLEANUP_MODE_NONE, nullptr, nullptr);
@@ -566,5 +565,4 @@ __global__ __launch_bounds__(64) void k_cleanup_plan(CleanupArgs a) {
     else cleanup_piece(tm, a, c);
 }
 
-#undef CSR_HD
 }  // namespace csr

@@ -9,7 +9,7 @@
 //   k_depspan_rowdiff  per pair of rows an any-difference flag over all bins, on the 32-bit patterns (-0.0 != 0.0, NaN payloads
 //                      count): what SHA-256 plus array_equal(equal_nan=True) decides;
 //   k_depspan_scores   one workgroup per (window, row): the finite values' max(v, 0) compacted stably (ballot scan), then NumPy's
-//                      sum of one contiguous float64 array of any length (depspan_np_sum: the pairwise trees of chunks of 8192
+//                      sum of one contiguous float64 array of any length (np_sum_f: the pairwise trees of chunks of 8192
 //                      folded in ascending order), walked by one lane; windowBins / finiteCount * sum;
 //   k_depspan_center   one workgroup per (window, row): finite count, the four order statistics np.quantile(.., [0.005, 0.995])
 //                      reads (method "linear") by a bit-wise search on the ordered 32-bit keys, NumPy's lerp, the clip, np.mean in
@@ -25,6 +25,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -57,92 +58,6 @@ struct DepCfg {
     double thr, minCov;
 };
 
-__device__ __forceinline__ bool dep_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
-__device__ __forceinline__ bool dep_finite(double v) { return fabs(v) <= 1.7976931348623157e+308; }
-// ascending order of finite floats as unsigned keys, and back.  -0.0 sorts in front of +0.0 here and equal to it in NumPy: where
-// a quantile's rank falls among zeros of both signs a clip bound may be the zero of the other sign than the reference's.  A
-// clipped value, and so every centred value and every sum, is the same number either way; only a zero's sign can differ
-__device__ __forceinline__ uint32_t dep_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dep_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
-
-// np.add.reduce of one contiguous float64 array: blocks of up to 128 values through 8 accumulators, longer ones split at
-// n/2 - (n/2) % 8 (NumPy's pairwise_sum); n <= 8192 here
-__device__ inline double depspan_leaf(const double *x, int64_t n) {
-    if (n < 8) {
-        double res = 0.0;       // (NumPy starts from the first element; 0.0 + x is x but for -0.0, which cannot decide a score)
-        if (n > 0) res = x[0];
-        for (int64_t i = 1; i < n; ++i) res = res + x[i];
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = x[k];
-    int64_t i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = r[k] + x[i + k];
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res = res + x[i];
-    return res;
-}
-__device__ inline double depspan_chunk_sum(const double *x, int64_t n) {
-    int64_t lo[16], len[16];
-    int stage[16];
-    double left[16];
-    int sp = 0;
-    lo[0] = 0; len[0] = n; stage[0] = 0; left[0] = 0.0;
-    double ret = 0.0;
-    while (sp >= 0) {
-        if (stage[sp] == 0) {
-            if (len[sp] <= 128) {
-                ret = depspan_leaf(x + lo[sp], len[sp]);
-                --sp;
-                continue;
-            }
-            int64_t n2 = len[sp] / 2;
-            n2 -= n2 % 8;
-            stage[sp] = 1;
-            lo[sp + 1] = lo[sp]; len[sp + 1] = n2; stage[sp + 1] = 0;
-            ++sp;
-        } else if (stage[sp] == 1) {
-            int64_t n2 = len[sp] / 2;
-            n2 -= n2 % 8;
-            left[sp] = ret;
-            stage[sp] = 2;
-            lo[sp + 1] = lo[sp] + n2; len[sp + 1] = len[sp] - n2; stage[sp + 1] = 0;
-            ++sp;
-        } else {
-            ret = left[sp] + ret;
-            --sp;
-        }
-    }
-    return ret;
-}
-// np.sum of one contiguous float64 array: the ascending fold of the pairwise sums of chunks of 8192 (NumPy's reduction buffer; the
-// project's nested_np_sum states the same rule)
-__device__ inline double depspan_np_sum(const double *x, int64_t n) {
-    double total = 0.0;
-    for (int64_t c0 = 0; c0 < n; c0 += 8192) {
-        const double part = depspan_chunk_sum(x + c0, n - c0 < 8192 ? n - c0 : 8192);
-        total = c0 == 0 ? part : total + part;
-    }
-    return total;
-}
-// numpy.lib._function_base_impl._lerp
-__device__ __forceinline__ double dep_lerp(double a, double b, double t) {
-    const double d = b - a;
-    if (t >= 0.5) {
-        const double s = d * (1.0 - t);
-        return b - s;
-    }
-    const double s = d * t;
-    return a + s;
-}
-
 // grid (ceil(longest / DEP_CMP), pairs, matrices), 256 threads: diff[pair] |= rows (pi[pair], pj[pair]) differ somewhere
 __global__ __launch_bounds__(256) void k_depspan_rowdiff(const DepMat *__restrict__ mats, const int *__restrict__ pi,
                                                           const int *__restrict__ pj, unsigned int *__restrict__ diff) {
@@ -159,25 +74,6 @@ __global__ __launch_bounds__(256) void k_depspan_rowdiff(const DepMat *__restric
         if (i < mt.n) d = d || a[i] != b[i];
     }
     if (d) atomicOr(&diff[p], 1u);
-}
-
-// The stable compaction step of a workgroup of 256 (four wavefronts): where the calling thread's value goes (base + its rank
-// among the set flags of the workgroup); *total: how many flags are set.  sW: 4 ints of LDS.  Two barriers.
-__device__ __forceinline__ int dep_rank256(bool f, int *sW, int *total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(f);
-    const int pre = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();                    // (sW of the previous step has been read)
-    if (lane == 0) sW[wv] = __popcll(b);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        off += k < wv ? sW[k] : 0;
-        tot += sW[k];
-    }
-    *total = tot;
-    return off + pre;
 }
 
 struct DepScoreArgs {
@@ -200,16 +96,16 @@ __global__ __launch_bounds__(256) void k_depspan_scores(DepScoreArgs a) {
     for (int64_t t0 = 0; t0 < wb; t0 += 256) {
         const int64_t i = t0 + threadIdx.x;
         const float v = i < wb ? x[i] : __uint_as_float(0x7fc00000u);
-        const bool f = dep_finite(v);
+        const bool f = np_finite(v);
         int tot;
-        const int at = dep_rank256(f, sW, &tot);
+        const int at = wg_rank256(f, sW, &tot);
         if (f) comp[n + at] = fmax((double)v, 0.0);
         n += tot;
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
     double s = __longlong_as_double(0x7ff8000000000000ll);
-    if (n > 0 && (double)n / (double)wb >= a.rankMin) s = (double)wb / (double)n * depspan_np_sum(comp, n);
+    if (n > 0 && (double)n / (double)wb >= a.rankMin) s = (double)wb / (double)n * np_sum_f(comp, n, NpIdentity{});
     a.score[(a.w0 + blockIdx.x) * a.nRows + blockIdx.y] = s;
 }
 
@@ -256,7 +152,7 @@ __global__ __launch_bounds__(256) void k_depspan_center(DepAcfArgs a) {
         for (int j = 0; j < 4; ++j) c[j] = sC[0][j] + sC[1][j] + sC[2][j] + sC[3][j];
     };
     int c[4] = {0, 0, 0, 0};
-    for (int64_t i = threadIdx.x; i < wb; i += 256) c[0] += dep_finite(x[i]);
+    for (int64_t i = threadIdx.x; i < wb; i += 256) c[0] += np_finite(x[i]);
     total4(c);
     const int n = c[0];
     if (n < 2) {                // (uniform) the reference skips the row
@@ -279,7 +175,9 @@ __global__ __launch_bounds__(256) void k_depspan_center(DepAcfArgs a) {
         rk[2 * j] = lo;
         rk[2 * j + 1] = hi;
     }
-    // the key of rank k is the largest K with count(key < K) <= k: one bit per pass, four ranks at once
+    // the key of rank k is the largest K with count(key < K) <= k: one bit per pass, four ranks at once.  np_key puts -0.0 in front
+    // of +0.0, NumPy's sort holds them equal: where a quantile's rank falls among zeros of both signs a clip bound may be the zero of
+    // the other sign than the reference's.  A clipped value, and so every centred value and every sum, is the same number either way
     uint32_t cur[4] = {0u, 0u, 0u, 0u};
     for (int bit = 31; bit >= 0; --bit) {
         uint32_t cand[4];
@@ -290,8 +188,8 @@ __global__ __launch_bounds__(256) void k_depspan_center(DepAcfArgs a) {
         }
         for (int64_t i = threadIdx.x; i < wb; i += 256) {
             const float v = x[i];
-            const bool f = dep_finite(v);
-            const uint32_t k = dep_key(v);
+            const bool f = np_finite(v);
+            const uint32_t k = np_key(v);
 #pragma unroll
             for (int j = 0; j < 4; ++j) c[j] += f && k < cand[j];
         }
@@ -300,24 +198,24 @@ __global__ __launch_bounds__(256) void k_depspan_center(DepAcfArgs a) {
         for (int j = 0; j < 4; ++j)
             if ((int64_t)c[j] <= rk[j]) cur[j] = cand[j];
     }
-    const double lowerClip = dep_lerp((double)dep_unkey(cur[0]), (double)dep_unkey(cur[1]), g[0]);
-    const double upperClip = dep_lerp((double)dep_unkey(cur[2]), (double)dep_unkey(cur[3]), g[1]);
+    const double lowerClip = np_lerp((double)np_unkey(cur[0]), (double)np_unkey(cur[1]), g[0]);
+    const double upperClip = np_lerp((double)np_unkey(cur[2]), (double)np_unkey(cur[3]), g[1]);
     // np.clip = minimum(maximum(x, lower), upper), compacted for the mean and in place for the centring
     int64_t at0 = 0;
     for (int64_t t0 = 0; t0 < wb; t0 += 256) {
         const int64_t i = t0 + threadIdx.x;
         const float v = i < wb ? x[i] : __uint_as_float(0x7fc00000u);
-        const bool f = dep_finite(v);
+        const bool f = np_finite(v);
         const double cl = fmin(fmax((double)v, lowerClip), upperClip);
         int tot;
-        const int at = dep_rank256(f, sW, &tot);
+        const int at = wg_rank256(f, sW, &tot);
         if (f) comp[at0 + at] = cl;
         if (i < wb) cen[i] = f ? cl : nan;
         at0 += tot;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        sMean = depspan_np_sum(comp, n) / (double)n;
+        sMean = np_sum_f(comp, n, NpIdentity{}) / (double)n;
         a.nfin[slot] = n;
     }
     __syncthreads();
@@ -384,7 +282,7 @@ __global__ __launch_bounds__(256) void k_depspan_pool(DepAcfArgs a) {
             if (a.nfin[slot] >= 2) {
                 const double pc = (double)a.pairs[slot * L];
                 if (pc >= (double)cf.minPairs && pc / (double)wb >= cf.minCov) z = a.sums[slot * L] / pc;
-                if (!(dep_finite(z) && z > 0.0)) z = nan;
+                if (!(np_finite(z) && z > 0.0)) z = nan;
                 else if (z < 1.0e-290) flags |= 1;
             }
             sZero[r] = z;
@@ -410,7 +308,7 @@ __global__ __launch_bounds__(256) void k_depspan_pool(DepAcfArgs a) {
             const double cov = pc / (double)(wb - l);
             if (!(pc >= (double)cf.minPairs && cov >= cf.minCov)) continue;
             const double acf = (a.sums[slot * L + l] / pc) / z;
-            if (!dep_finite(acf)) continue;
+            if (!np_finite(acf)) continue;
             // insertion into the ascending list
             int k = m++;
             while (k > 0 && v[k - 1] > acf) {
@@ -470,7 +368,7 @@ __global__ __launch_bounds__(256) void k_depspan_pool(DepAcfArgs a) {
         bool found = true;
         for (int k = 0; k < cf.persist; ++k) {
             const double cv = smoothed(start + k);
-            if (!dep_finite(cv)) {
+            if (!np_finite(cv)) {
                 rc.margin = 0.0;
                 found = false;
                 break;

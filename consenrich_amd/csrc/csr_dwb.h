@@ -13,12 +13,13 @@
 //   k_dwb_select  the exact order statistics of a row at up to DWB_MAX_RANKS ranks: a byte-wise radix select like csr_gain.h's,
 //                 on a plain double array, one workgroup per row, eight passes inside one launch;
 //   k_dwb_tail    count(x > offset) and the sum of clip((x - offset) / scale, 0, inf) in NumPy's summation order: one thread per
-//                 (chunk of 8192, z) evaluates NumPy's pairwise tree of that chunk (dwb_chunk_sum_f, over any element
-//                 expression: csr_null.h sums with it too); k_dwb_tail_fold folds the chunk sums in ascending order and divides by n.
+//                 (chunk of 8192, z) evaluates NumPy's pairwise tree of that chunk (np_chunk_sum_f of csr_np_order.h over the
+//                 excess-and-count element); k_dwb_tail_fold folds the chunk sums in ascending order and divides by n.
 // Nothing here waits on another workgroup: every dependency is a kernel boundary, every loop bound is known at launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -28,7 +29,6 @@ constexpr int DWB_WT = 256;             // values per row and LDS tile of the wa
 constexpr int DWB_WR = 16;              // rows (draws) per wavefront of the walk
 constexpr int DWB_MAX_RANKS = 16;       // order statistics per row
 constexpr int DWB_MAX_Z = 16;           // (offset, scale) pairs per row
-constexpr int DWB_CHUNK = 8192;         // NumPy's reduction buffer: np.sum is the ascending fold of pairwise sums of such chunks
 
 struct DwbChain {
     int64_t off, n;         // bins [off, off + n) of a row of the concatenated layout (off is a multiple of 64)
@@ -191,15 +191,7 @@ __global__ __launch_bounds__(256) void k_dwb_centre(const DwbChain *__restrict__
     *p = *p - means[(int64_t)blockIdx.z * nRows + blockIdx.y];
 }
 
-// ---- exact order statistics of every row -----------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long dwb_key(double g) {       // monotone in g (-0.0 sorts before +0.0)
-    const unsigned long long b = (unsigned long long)__double_as_longlong(g);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dwb_unkey(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
+// ---- exact order statistics of every row (on np_key: -0.0 sorts before +0.0) --------------------------------------------------
 // grid (rows, chains); ranks[chain][nRanks] (-1 = unused, answered with NaN); out[(chain * outRows + d0 + row) * nRanks + q]
 __global__ __launch_bounds__(256) void k_dwb_select(const DwbChain *__restrict__ chains, const double *__restrict__ rows,
                                                     int64_t rowLen, const long long *__restrict__ ranks, int nRanks,
@@ -220,18 +212,11 @@ __global__ __launch_bounds__(256) void k_dwb_select(const DwbChain *__restrict__
     __syncthreads();
     for (int pass = 0; pass < 8; ++pass) {
         for (int i = t; i < DWB_MAX_RANKS * 256; i += 256) (&h[0][0])[i] = 0u;
-        if (t == 0)         // targets with equal prefixes share one histogram: grp[q] = the first target with q's prefix
-            for (int q = 0; q < DWB_MAX_RANKS; ++q) {
-                grp[q] = -1;
-                if (rk[q] < 0) continue;
-                grp[q] = q;
-                for (int u = 0; u < q; ++u)
-                    if (grp[u] == u && pre[u] == pre[q]) { grp[q] = u; break; }
-            }
+        if (t == 0) radix_groups(rk, pre, DWB_MAX_RANKS, grp);
         __syncthreads();
         const int shift = 56 - 8 * pass;
         for (int64_t k = t; k < ch.n; k += 256) {
-            const unsigned long long key = dwb_key(x[k]);
+            const unsigned long long key = np_key(x[k]);
             const unsigned long long hi = pass == 0 ? 0ull : key >> (shift + 8);
             const unsigned int digit = (unsigned int)(key >> shift) & 255u;
             for (int q = 0; q < nRanks; ++q)
@@ -241,16 +226,10 @@ __global__ __launch_bounds__(256) void k_dwb_select(const DwbChain *__restrict__
         long long newRank = -1;
         unsigned long long newPre = 0ull;
         if (t < DWB_MAX_RANKS && grp[t] >= 0) {
-            const unsigned int *hh = h[grp[t]];
-            long long cum = 0;
-            int digit = 255;
-            for (int d = 0; d < 256; ++d) {
-                const long long c = (long long)hh[d];
-                if (rk[t] < cum + c) { digit = d; break; }
-                cum += c;
-            }
+            long long before;
+            const int digit = radix_pick_digit(h[grp[t]], rk[t], &before);
             newPre = (pre[t] << 8) | (unsigned long long)digit;
-            newRank = rk[t] - cum;
+            newRank = rk[t] - before;
         }
         __syncthreads();
         if (t < DWB_MAX_RANKS && grp[t] >= 0) {
@@ -261,83 +240,19 @@ __global__ __launch_bounds__(256) void k_dwb_select(const DwbChain *__restrict__
     }
     if (t < nRanks)
         out[((int64_t)blockIdx.y * outRows + d0 + blockIdx.x) * nRanks + t] =
-            grp[t] >= 0 ? dwb_unkey(pre[t]) : __longlong_as_double(0x7ff8000000000000ll);
+            grp[t] >= 0 ? np_unkey(pre[t]) : __longlong_as_double(0x7ff8000000000000ll);
 }
 
 // ---- tail statistics -------------------------------------------------------------------------------------------------------
-// np.clip((x - off) / s, 0, None) of one element (np.maximum: a NaN stays, -0.0 becomes 0.0)
-__device__ __forceinline__ double dwb_excess(double x, double off, double s) {
-    const double v = __ddiv_rn(x - off, s);
-    return (v > 0.0 || v != v) ? v : 0.0;
-}
-// NumPy's pairwise sum of f(x[i]) over a block of 8 <= n <= 128 values (eight strided accumulators, then the remainder in order)
-// or of n < 8 values (in order); f is evaluated once per element, in the order NumPy adds them
-template <class F>
-__host__ __device__ __forceinline__ double dwb_leaf_f(const double *x, int n, F &f) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res = res + f(x[i]);
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = f(x[k]);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = r[k] + f(x[i + k]);
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res = res + f(x[i]);
-    return res;
-}
-// the pairwise tree of one chunk (n <= DWB_CHUNK): blocks above 128 values split at n/2 - (n/2) % 8
-template <class F>
-__host__ __device__ inline double dwb_chunk_sum_f(const double *x, int n, F &f) {
-    int lo[12], len[12], stage[12];
-    double left[12];
-    int sp = 0;
-    lo[0] = 0; len[0] = n; stage[0] = 0; left[0] = 0.0;
-    double ret = 0.0;
-    while (sp >= 0) {
-        if (stage[sp] == 0) {
-            if (len[sp] <= 128) {
-                ret = dwb_leaf_f(x + lo[sp], len[sp], f);
-                --sp;
-                continue;
-            }
-            int n2 = len[sp] / 2;
-            n2 -= n2 % 8;
-            stage[sp] = 1;
-            lo[sp + 1] = lo[sp]; len[sp + 1] = n2; stage[sp + 1] = 0;
-            ++sp;
-        } else if (stage[sp] == 1) {
-            int n2 = len[sp] / 2;
-            n2 -= n2 % 8;
-            left[sp] = ret;
-            stage[sp] = 2;
-            lo[sp + 1] = lo[sp] + n2; len[sp + 1] = len[sp] - n2; stage[sp + 1] = 0;
-            ++sp;
-        } else {
-            ret = left[sp] + ret;
-            --sp;
-        }
-    }
-    return ret;
-}
 // the element of the tail statistics: counts x > off on the way
 struct DwbExcess {
     double off, s;
     long long &cnt;
     __device__ __forceinline__ double operator()(double x) {
         cnt += x > off;
-        return dwb_excess(x, off, s);
+        return np_excess(x, off, s);
     }
 };
-__device__ __forceinline__ double dwb_chunk_sum(const double *x, int n, double off, double s, long long &cnt) {
-    DwbExcess f{off, s, cnt};
-    return dwb_chunk_sum_f(x, n, f);
-}
 struct DwbTailArgs {
     const DwbChain *chains;
     const double *rows;
@@ -358,13 +273,14 @@ __global__ __launch_bounds__(64) void k_dwb_tail(DwbTailArgs a) {
     const int64_t pair = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t chunk = pair / a.nZ;
     const int z = (int)(pair % a.nZ);
-    const int64_t nChunks = (ch.n + DWB_CHUNK - 1) / DWB_CHUNK;
+    const int64_t nChunks = (ch.n + NP_CHUNK - 1) / NP_CHUNK;
     if (chunk >= nChunks) return;
-    const double *x = a.rows + (int64_t)blockIdx.y * a.rowLen + ch.off + chunk * DWB_CHUNK;
-    const int64_t left = ch.n - chunk * DWB_CHUNK;
-    const int len = (int)(left < DWB_CHUNK ? left : DWB_CHUNK);
+    const double *x = a.rows + (int64_t)blockIdx.y * a.rowLen + ch.off + chunk * NP_CHUNK;
+    const int64_t left = ch.n - chunk * NP_CHUNK;
+    const int len = (int)(left < NP_CHUNK ? left : NP_CHUNK);
     long long cnt = 0;
-    const double s = dwb_chunk_sum(x, len, a.off[blockIdx.z * a.nZ + z], a.scale[blockIdx.z * a.nZ + z], cnt);
+    DwbExcess f{a.off[blockIdx.z * a.nZ + z], a.scale[blockIdx.z * a.nZ + z], cnt};
+    const double s = np_chunk_sum_f(x, len, f);
     const int64_t slot = ((((int64_t)blockIdx.z * a.nRows + blockIdx.y) * a.maxChunks) + chunk) * a.nZ + z;
     a.partSum[slot] = s;
     a.partCnt[slot] = cnt;
@@ -378,7 +294,7 @@ __global__ __launch_bounds__(64) void k_dwb_tail_fold(DwbTailArgs a, int nChains
     const int row = (int)((id / a.nZ) % a.nRows);
     const int c = (int)(id / ((int64_t)a.nZ * a.nRows));
     const DwbChain ch = a.chains[c];
-    const int64_t nChunks = (ch.n + DWB_CHUNK - 1) / DWB_CHUNK;
+    const int64_t nChunks = (ch.n + NP_CHUNK - 1) / NP_CHUNK;
     const int64_t slot0 = (((int64_t)c * a.nRows + row) * a.maxChunks) * a.nZ + z;
     double s = a.partSum[slot0];
     long long cnt = a.partCnt[slot0];

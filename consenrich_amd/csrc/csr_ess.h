@@ -19,7 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "csr_dwb.h"
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -27,7 +27,7 @@ constexpr int ESS_TILE = 512;               // values of i per LDS tile
 constexpr int ESS_WAVE = 64;                // lags per wavefront = threads per workgroup
 constexpr int ESS_A = ESS_TILE / ESS_WAVE;              // registers per lane that prefetch x[i ..)
 constexpr int ESS_B = ESS_TILE / ESS_WAVE + 1;          // ... and x[i + lag0 ..), one more row for the 63 further lags
-constexpr int ESS_MAX_Z = DWB_MAX_Z;
+constexpr int ESS_MAX_Z = 16;               // (threshold, scale) pairs of an integrated-excess series: the stage's own limit (ess.MAX_Z)
 
 enum : int { ESS_SERIES_GIVEN = 0, ESS_SERIES_OCCUPANCY = 1, ESS_SERIES_SOFT = 2, ESS_SERIES_INTEGRATED = 3 };
 
@@ -55,10 +55,10 @@ __global__ __launch_bounds__(256) void k_ess_series(const EssTrack *__restrict__
     const double x = tr.src[i];
     double v;
     if (tr.kind == ESS_SERIES_OCCUPANCY) v = x > tr.thr[0] ? 1.0 : 0.0;
-    else if (tr.kind == ESS_SERIES_SOFT) v = dwb_excess(x, tr.thr[0], tr.den[0]);
+    else if (tr.kind == ESS_SERIES_SOFT) v = np_excess(x, tr.thr[0], tr.den[0]);
     else if (tr.kind == ESS_SERIES_INTEGRATED) {        // np.mean(np.vstack(parts), axis=0): the rows added in order, then / nz
-        v = dwb_excess(x, tr.thr[0], tr.den[0]);
-        for (int k = 1; k < tr.nz; ++k) v = v + dwb_excess(x, tr.thr[k], tr.den[k]);
+        v = np_excess(x, tr.thr[0], tr.den[0]);
+        for (int k = 1; k < tr.nz; ++k) v = v + np_excess(x, tr.thr[k], tr.den[k]);
         v = __ddiv_rn(v, (double)tr.nz);
     } else v = x;
     tr.cen[i] = v;

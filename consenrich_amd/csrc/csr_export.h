@@ -28,10 +28,9 @@
 // with the SEGMENTS as parents that do not split: k_export_child finishes a segment exactly as it finishes a child.
 #pragma once
 #include "csr_nested.h"
+#include "csr_np_order.h"
 
 namespace csr {
-
-#define CSR_HD __host__ __device__ __forceinline__
 
 struct ExportTrack {
     const double *d;        // float64 values, or
@@ -94,8 +93,8 @@ CSR_HD void export_prep_parent(const ExportArgs &a, int j) {
     s.required = nested_argmax(x, jb.n);
     int flags = 0;
     for (int64_t i = 0; i < jb.n; ++i) {
-        if (!nested_finite(x[i])) flags |= EXPORT_BAD_SCORES;
-        if (!nested_finite(a.sig.at(jb.off + i))) flags |= EXPORT_BAD_SIGNAL;
+        if (!np_finite(x[i])) flags |= EXPORT_BAD_SCORES;
+        if (!np_finite(a.sig.at(jb.off + i))) flags |= EXPORT_BAD_SIGNAL;
     }
     a.na.st[j] = s;
     ExportParent r;
@@ -122,7 +121,7 @@ CSR_HD void export_finish_parent(const ExportArgs &a, int j) {
     // the final pick: max by (value, -count), the first of two equals
     const double last = s.vM - cost;
     const bool on = (last > s.v0) || (last == s.v0 && s.cM < s.c0);
-    if (!nested_finite(on ? last : s.v0)) {
+    if (!np_finite(on ? last : s.v0)) {
         r.flags |= EXPORT_INFEASIBLE;
         for (int64_t i = 0; i < n; ++i) m[i] = 0;
         a.par[j] = r;
@@ -153,7 +152,7 @@ CSR_HD void export_finish_parent(const ExportArgs &a, int j) {
         prev = cur;
     }
     if (prev) bp += cost;
-    const double selected = nested_np_sum(w, cnt, NestedIdentity{});
+    const double selected = np_sum_f(w, cnt, NpIdentity{});
     const double objective = (selected - bp) - 0.0 * (double)runs;
     r.penalized = objective - s.penalty * (double)cnt;
     r.boundary = bp;
@@ -238,7 +237,7 @@ CSR_HD void export_child(const ExportArgs &a, int64_t t) {
         int64_t cnt = 0;
         for (int64_t i = 0; i < len; ++i) {
             const double u = a.unc.at(jb.off + ts + i);
-            if (nested_finite(u)) w[cnt++] = u;
+            if (np_finite(u)) w[cnt++] = u;
         }
         if (cnt > 0) {
             p.local_median_p = export_median(w, cnt);
@@ -263,5 +262,4 @@ __global__ __launch_bounds__(64) void k_export_child(ExportArgs a) {
     if (t < a.nPeaks) export_child(a, t);
 }
 
-#undef CSR_HD
 }  // namespace csr

@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -41,14 +42,6 @@ __device__ __forceinline__ double gain_value(const GainArgs &a, int row, int64_t
     const double v = (double)a.munc[(int64_t)row * a.Npad + a.off + k] + a.pad;
     const double var = (v > 1.0e-12 || v != v) ? v : 1.0e-12;
     return (p00 * prec) / var;
-}
-__device__ __forceinline__ unsigned long long gain_key(double g) {     // monotone in g over all finite doubles
-    const unsigned long long b = (unsigned long long)__double_as_longlong(g);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double gain_unkey(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
 }
 
 // phase 0: count and sum of the finite gains; phase 1: sum of squared deviations from the mean (out[row][1])
@@ -107,17 +100,6 @@ __global__ __launch_bounds__(64) void k_gain_fold(GainArgs a, int phase) {
     }
 }
 
-// targets with equal prefixes share one histogram: grp[t] = the first target with t's prefix (or -1: unused)
-__device__ __forceinline__ void gain_groups(const GainArgs &a, int row, int *grp) {
-    for (int t = 0; t < GAIN_T; ++t) {
-        grp[t] = -1;
-        if (a.rank[row * GAIN_T + t] < 0) continue;
-        grp[t] = t;
-        for (int u = 0; u < t; ++u)
-            if (grp[u] == u && a.prefix[row * GAIN_T + u] == a.prefix[row * GAIN_T + t]) { grp[t] = u; break; }
-    }
-}
-
 // pass p (0 .. 7): histogram of byte 7 - p of the keys whose higher bytes equal a target's prefix
 __global__ __launch_bounds__(256) void k_gain_hist(GainArgs a, int pass) {
     __shared__ unsigned int h[GAIN_T][256];
@@ -126,7 +108,7 @@ __global__ __launch_bounds__(256) void k_gain_hist(GainArgs a, int pass) {
     const int row = blockIdx.y, w = blockIdx.x, t = threadIdx.x;
     for (int i = t; i < GAIN_T * 256; i += 256) (&h[0][0])[i] = 0u;
     if (t == 0) {
-        gain_groups(a, row, grp);
+        radix_groups(a.rank + row * GAIN_T, a.prefix + row * GAIN_T, GAIN_T, grp);
         for (int q = 0; q < GAIN_T; ++q) pre[q] = a.prefix[row * GAIN_T + q];
     }
     __syncthreads();
@@ -138,7 +120,7 @@ __global__ __launch_bounds__(256) void k_gain_hist(GainArgs a, int pass) {
         if (k >= a.len) continue;
         const double g = gain_value(a, row, k);
         if (!isfinite(g)) continue;
-        const unsigned long long key = gain_key(g);
+        const unsigned long long key = np_key(g);
         const unsigned long long hi = pass == 0 ? 0ull : key >> (shift + 8);
         const unsigned int digit = (unsigned int)(key >> shift) & 255u;
 #pragma unroll
@@ -156,7 +138,7 @@ __global__ __launch_bounds__(256) void k_gain_hist(GainArgs a, int pass) {
 __global__ __launch_bounds__(64) void k_gain_pick(GainArgs a, int pass) {
     __shared__ int grp[GAIN_T];
     const int row = blockIdx.x, lane = threadIdx.x;
-    if (lane == 0) gain_groups(a, row, grp);
+    if (lane == 0) radix_groups(a.rank + row * GAIN_T, a.prefix + row * GAIN_T, GAIN_T, grp);
     __syncthreads();
     unsigned long long newPre[GAIN_T];
     long long newRank[GAIN_T];
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(64) void k_gain_pick(GainArgs a, int pass) {
         for (int q = 0; q < GAIN_T; ++q) {
             a.prefix[row * GAIN_T + q] = newPre[q];
             if (grp[q] >= 0) a.rank[row * GAIN_T + q] = newRank[q];
-            if (pass == 7) a.out[row * GAIN_OUT + 3 + q] = grp[q] >= 0 ? gain_unkey(newPre[q]) : __longlong_as_double(0x7ff8000000000000ll);
+            if (pass == 7) a.out[row * GAIN_OUT + 3 + q] = grp[q] >= 0 ? np_unkey(newPre[q]) : __longlong_as_double(0x7ff8000000000000ll);
         }
     for (int i = lane; i < GAIN_T * 256; i += 64) a.hist[(int64_t)row * GAIN_T * 256 + i] = 0u;
 }

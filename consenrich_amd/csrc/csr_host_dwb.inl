@@ -82,7 +82,7 @@ static int dwb_setup(csr_ctx *c, int nChains, const int64_t *len, const int32_t 
         d.strideMax = std::max(d.strideMax, ch.stride);
     }
     d.rowLen = std::max<int64_t>(pad, 64);
-    d.maxChunks = std::max<int64_t>((d.longest + DWB_CHUNK - 1) / DWB_CHUNK, 1);
+    d.maxChunks = std::max<int64_t>((d.longest + NP_CHUNK - 1) / NP_CHUNK, 1);
     CHECK(d.chainBuf.reserve(sizeof(DwbChain) * (size_t)nChains));
     CHECK(d.wtsBuf.reserve(8 * w.size()));
     HIPOK(hipMemcpyAsync(d.chainBuf.ptr, d.chains.data(), sizeof(DwbChain) * (size_t)nChains, hipMemcpyHostToDevice, c->stream));
@@ -369,7 +369,7 @@ static int dwb_vector_tail(csr_ctx *c, const double *dx, int64_t n, int32_t n_z,
     HIPOK(hipMemcpyAsync(base + oOff, offsets, 8 * (size_t)n_z, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipMemcpyAsync(base + oScale, sc, 8 * (size_t)n_z, hipMemcpyHostToDevice, c->stream));
     HIPOK(hipStreamSynchronize(c->stream));     // (ch, sc leave scope)
-    CHECK(dwb_tail_rows(c, dx, n, (const DwbChain *)base, 1, std::max<int64_t>((n + DWB_CHUNK - 1) / DWB_CHUNK, 1), 1, n_z,
+    CHECK(dwb_tail_rows(c, dx, n, (const DwbChain *)base, 1, std::max<int64_t>((n + NP_CHUNK - 1) / NP_CHUNK, 1), 1, n_z,
                         (const double *)(base + oOff), (const double *)(base + oScale), (long long *)(base + oCnt),
                         (double *)(base + oSoft), 1, 0));
     HIPOK(hipMemcpyAsync(counts, base + oCnt, 8 * (size_t)n_z, hipMemcpyDeviceToHost, c->stream));

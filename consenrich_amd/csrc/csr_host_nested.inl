@@ -196,7 +196,7 @@ static int nested_sum_run(csr_ctx *c, const NestedLay &L, const std::vector<Nest
     csr_ctx::NestedWs &ws = c->nestedWs;
     int64_t most = 1, total = 0;
     for (const NestedSumJob &s : sums) { most = std::max(most, s.n); total += s.n; }
-    const int64_t maxChunks = (most + DWB_CHUNK - 1) / DWB_CHUNK;
+    const int64_t maxChunks = (most + NP_CHUNK - 1) / NP_CHUNK;
     const size_t oRun = 0, oSum = (runs.size() * sizeof(NestedRun) + 255) / 256 * 256,
                  oOut = oSum + (nc * sizeof(NestedSumJob) + 255) / 256 * 256, tabBytes = oOut + 8 * (size_t)nc;
     CHECK(ws.jobBuf.reserve(tabBytes));
@@ -209,9 +209,9 @@ static int nested_sum_run(csr_ctx *c, const NestedLay &L, const std::vector<Nest
         Scope sc(c, "nested_selected_sum");
         CHECK(launch(c, nullptr, "k_nested_gather", k_nested_gather, dim3((unsigned)runs.size()), dim3(256), 0, c->stream,
                      (const NestedRun *)(tab + oRun), L.scores, (double *)ws.work.ptr));
-        CHECK(launch(c, nullptr, "k_nested_sum", k_nested_sum, dim3((unsigned)((maxChunks + 63) / 64), (unsigned)nc), dim3(64), 0, c->stream,
+        CHECK(launch(c, nullptr, "k_nested_sum", k_np_chunk_sums<NestedSumJob>, dim3((unsigned)((maxChunks + 63) / 64), (unsigned)nc), dim3(64), 0, c->stream,
                      (const NestedSumJob *)(tab + oSum), (const double *)ws.work.ptr, (double *)ws.part.ptr, maxChunks));
-        CHECK(launch(c, nullptr, "k_nested_fold", k_nested_fold, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, c->stream,
+        CHECK(launch(c, nullptr, "k_nested_fold", k_np_fold<NestedSumJob>, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, c->stream,
                      (const NestedSumJob *)(tab + oSum), nc, (const double *)ws.part.ptr, maxChunks, (double *)(tab + oOut)));
     }
     HIPOK(hipMemcpyAsync(out, tab + oOut, 8 * (size_t)nc, hipMemcpyDeviceToHost, c->stream));

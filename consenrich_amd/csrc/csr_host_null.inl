@@ -154,14 +154,14 @@ struct NullEngine {
         CHECK(up(jobs, dev));
         int64_t most = 1;
         for (const NullJob &j : jobs) most = std::max(most, j.n);
-        const int64_t maxChunks = (most + DWB_CHUNK - 1) / DWB_CHUNK;
+        const int64_t maxChunks = (most + NP_CHUNK - 1) / NP_CHUNK;
         CHECK(ws().part.reserve(8 * (size_t)maxChunks * jobs.size()));
         CHECK(ws().outBuf.reserve(8 * jobs.size()));
         {
             Scope sc(c, "null_sum");
-            CHECK(launch(c, nullptr, "k_null_sum", k_null_sum, dim3((unsigned)((maxChunks + 63) / 64), (unsigned)jobs.size()), dim3(64), 0,
-                         c->stream, dev, (double *)ws().part.ptr, maxChunks));
-            CHECK(launch(c, nullptr, "k_null_fold", k_null_fold, dim3((unsigned)((jobs.size() + 63) / 64)), dim3(64), 0, c->stream, dev,
+            CHECK(launch(c, nullptr, "k_null_sum", k_np_chunk_sums<NullJob>, dim3((unsigned)((maxChunks + 63) / 64), (unsigned)jobs.size()),
+                         dim3(64), 0, c->stream, dev, (const double *)nullptr, (double *)ws().part.ptr, maxChunks));
+            CHECK(launch(c, nullptr, "k_null_fold", k_np_fold<NullJob>, dim3((unsigned)((jobs.size() + 63) / 64)), dim3(64), 0, c->stream, dev,
                          (int)jobs.size(), (const double *)ws().part.ptr, maxChunks, (double *)ws().outBuf.ptr));
         }
         return down(out, jobs.size());

@@ -20,7 +20,7 @@
 //   k_nested_dp_wide one workgroup per region, minRun up to NESTED_MAX_MIN_RUN: the states are the lanes, the shift goes
 //                    through double-buffered LDS, one barrier per bin.
 //   k_nested_finish  one lane per region: the final pick, the backtrace, the selected solver scores compacted into work space and
-//                    summed in NumPy's order (the chunk and leaf helpers of csr_dwb.h), the sequential boundary sum and run
+//                    summed in NumPy's order (np_sum_f of csr_np_order.h), the sequential boundary sum and run
 //                    count, the same for the all-ones mask, split gain, the gates and the decision; every candidate run with its
 //                    own required bin, raw maximum and NumPy-order score sum; and, when the region splits or shrinks, its bins
 //                    of the solution mask.
@@ -30,7 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include "csr_dwb.h"
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -82,9 +82,6 @@ struct NestedArgs {
     int64_t kidCap;
 };
 
-#define CSR_HD __host__ __device__ __forceinline__
-
-CSR_HD bool nested_finite(double x) { return x > -INFINITY && x < INFINITY; }
 CSR_HD bool nested_better(double v, int c, double bv, int bc) {
     return (v > bv + NESTED_EPS) || (fabs(v - bv) <= NESTED_EPS && c < bc);
 }
@@ -97,17 +94,6 @@ struct NestedShift {
     double floor;
     CSR_HD double operator()(double x) const { return x - floor; }
 };
-// np.sum of f(x[0 .. n)): the ascending fold of the pairwise sums of chunks of 8192
-template <class F>
-CSR_HD double nested_np_sum(const double *x, int64_t n, F f) {
-    double total = 0.0;
-    for (int64_t c0 = 0; c0 < n; c0 += DWB_CHUNK) {
-        const int len = (int)(n - c0 < DWB_CHUNK ? n - c0 : DWB_CHUNK);
-        const double part = dwb_chunk_sum_f(x + c0, len, f);
-        total = c0 == 0 ? part : total + part;
-    }
-    return total;
-}
 // np.quantile(v, q), method "linear", of the m values w[lo .. lo + m) - floor (w ascending); q is a multiple of 1/4
 CSR_HD double nested_quantile(const double *w, int64_t lo, int64_t m, double q, double floor) {
     const double vi = (double)m * q + (1.0 + q * -1.0) - 1.0;
@@ -115,8 +101,7 @@ CSR_HD double nested_quantile(const double *w, int64_t lo, int64_t m, double q, 
     const double fl = ::floor(vi);
     const int64_t k = (int64_t)fl;
     const double a = w[lo + k] - floor, b = w[lo + k + 1] - floor;
-    const double t = vi - fl, d = b - a;
-    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
+    return np_lerp(a, b, vi - fl);
 }
 CSR_HD void nested_heapsort(double *w, int64_t n) {
     auto sift = [&](int64_t root, int64_t end) {
@@ -147,9 +132,6 @@ CSR_HD int64_t nested_argmax(const double *r, int64_t n) {
         if (r[i] > m) { m = r[i]; k = i; }
     return k;
 }
-struct NestedIdentity {
-    CSR_HD double operator()(double x) const { return x; }
-};
 // what `_addNode` records of bins [off, off + n) whose first bin is `start` in its chain
 CSR_HD csr_nested_node nested_node(const double *scores, const double *raw, int64_t off, int64_t start, int64_t n) {
     csr_nested_node nd;
@@ -158,7 +140,7 @@ CSR_HD csr_nested_node nested_node(const double *scores, const double *raw, int6
     nd.end = start + n - 1;
     nd.required = start + k;
     nd.raw_score_max = raw[off + k];
-    nd.score_sum = nested_np_sum(scores + off, n, NestedIdentity{});
+    nd.score_sum = np_sum_f(scores + off, n, NpIdentity{});
     return nd;
 }
 
@@ -182,7 +164,7 @@ CSR_HD void nested_prep_region(const NestedArgs &a, int j) {
     const int64_t np = jb.n - lo;
     double spread = 0.0;
     if (np > 1) spread = nested_quantile(w, lo, np, 0.75, s.floor) - nested_quantile(w, lo, np, 0.25, s.floor);
-    if (!nested_finite(spread) || spread < 0.0) spread = 0.0;
+    if (!np_finite(spread) || spread < 0.0) spread = 0.0;
     const double scale = P.scale < 0.0 ? 0.0 : (P.scale > 1.0 ? 1.0 : P.scale);
     const double base = P.base > 0.0 ? P.base : 0.0;
     s.extra = (1.0 - scale) * spread;
@@ -224,8 +206,8 @@ CSR_HD void nested_dp_region(const NestedArgs &a, int j) {
         int n0c = big;
         unsigned long long b0 = 0ull, b1 = 0ull;
         if (i != s.required) {
-            if (nested_finite(p0)) { n0v = p0; n0c = c0; }
-            if (nested_finite(pM)) {
+            if (np_finite(p0)) { n0v = p0; n0c = c0; }
+            if (np_finite(pM)) {
                 const double cand = pM - tc;
                 if (nested_better(cand, cM, n0v, n0c)) { n0v = cand; n0c = cM; b0 = 1ull; }
             }
@@ -234,18 +216,18 @@ CSR_HD void nested_dp_region(const NestedArgs &a, int j) {
 #pragma unroll
         for (int k = S; k >= 2; --k)
             if (k <= M) {
-                const bool fin = nested_finite(v[k - 1]);
+                const bool fin = np_finite(v[k - 1]);
                 v[k] = fin ? v[k - 1] + adj : -INFINITY;
                 c[k] = fin ? c[k - 1] + 1 : big;
             }
         // state 1: a run that opens here
         {
-            const bool fin = nested_finite(p0);
+            const bool fin = np_finite(p0);
             v[1] = fin ? ((p0 - tc) - s.runPenalty) + adj : -INFINITY;
             c[1] = fin ? c0 + 1 : big;
         }
         // state M: the run that was already minRun long goes on
-        if (nested_finite(pM)) {
+        if (np_finite(pM)) {
             const double cand = pM + adj;
             const int cc = cM + 1;
 #pragma unroll
@@ -300,7 +282,7 @@ CSR_HD void nested_finish_region(const NestedArgs &a, int j) {
     // the final pick: max by (value, -count), the first of two equals
     const double last = s.vM - nested_cost(jb, P.internal, n);
     const bool on = (last > s.v0) || (last == s.v0 && s.cM < s.c0);
-    if (!nested_finite(on ? last : s.v0)) {
+    if (!np_finite(on ? last : s.v0)) {
         r.decision = CSR_NESTED_INFEASIBLE;
         r.selected_count = 0; r.n_runs = 0; r.widths_ok = 0;
         r.objective = r.penalized = r.boundary_penalty = r.run_penalty_total = r.parent_penalized = r.split_gain = 0.0;
@@ -338,7 +320,7 @@ CSR_HD void nested_finish_region(const NestedArgs &a, int j) {
         bp += nested_cost(jb, P.internal, n);
         if (run < M) ok = false;
     }
-    const double selected = nested_np_sum(w, cnt, NestedIdentity{});
+    const double selected = np_sum_f(w, cnt, NpIdentity{});
     const double rpt = s.runPenalty * (double)runs;
     r.objective = (selected - bp) - rpt;
     r.penalized = r.objective - s.penalty * (double)cnt;
@@ -349,7 +331,7 @@ CSR_HD void nested_finish_region(const NestedArgs &a, int j) {
     r.widths_ok = (runs >= 1 && ok) ? 1 : 0;
     // ... and of the whole region kept as it is
     {
-        const double all = nested_np_sum(x, n, NestedShift{s.floor});
+        const double all = np_sum_f(x, n, NestedShift{s.floor});
         double bpa = 0.0;
         bpa += nested_cost(jb, P.internal, 0);
         bpa += nested_cost(jb, P.internal, n);
@@ -435,19 +417,19 @@ __global__ __launch_bounds__(NESTED_WIDE_T) void k_nested_dp_wide(NestedArgs a, 
             double nv;
             int nc;
             if (k == 1) {
-                const bool fin = nested_finite(p0);
+                const bool fin = np_finite(p0);
                 nv = fin ? ((p0 - tc) - s.runPenalty) + adj : -INFINITY;
                 nc = fin ? c0 + 1 : big;
             } else {
                 const double pv = sV[b][k - 1];
                 const int pc = sC[b][k - 1];
-                const bool fin = nested_finite(pv);
+                const bool fin = np_finite(pv);
                 nv = fin ? pv + adj : -INFINITY;
                 nc = fin ? pc + 1 : big;
             }
             if (k == M) {
                 unsigned int b1 = 0u;
-                if (nested_finite(pM)) {
+                if (np_finite(pM)) {
                     const double cand = pM + adj;
                     if (nested_better(cand, cM + 1, nv, nc)) { nv = cand; nc = cM + 1; b1 = 1u; }
                 }
@@ -460,8 +442,8 @@ __global__ __launch_bounds__(NESTED_WIDE_T) void k_nested_dp_wide(NestedArgs a, 
             double n0v = -INFINITY;
             int n0c = big;
             if (i != s.required) {
-                if (nested_finite(p0)) { n0v = p0; n0c = c0; }
-                if (nested_finite(pM)) {
+                if (np_finite(p0)) { n0v = p0; n0c = c0; }
+                if (np_finite(pM)) {
                     const double cand = pM - tc;
                     if (nested_better(cand, cM, n0v, n0c)) { n0v = cand; n0c = cM; b0 = 1ull; }
                 }
@@ -496,30 +478,10 @@ __global__ __launch_bounds__(256) void k_nested_gather(const NestedRun *__restri
     const NestedRun r = runs[blockIdx.x];
     for (int64_t i = threadIdx.x; i < r.n; i += 256) comp[r.dst + i] = scores[r.src + i];
 }
-struct NestedSumJob {
+struct NestedSumJob {       // (a Job of k_np_chunk_sums / k_np_fold: "k_nested_sum", "k_nested_fold")
     int64_t src, n;         // comp[src .. src + n)
+    __device__ const double *data(const double *comp) const { return comp + src; }
+    __device__ NpIdentity elem() const { return NpIdentity{}; }
 };
-// grid (ceil(maxChunks / 64), jobs): part[job * maxChunks + chunk]
-__global__ __launch_bounds__(64) void k_nested_sum(const NestedSumJob *__restrict__ jobs, const double *__restrict__ comp,
-                                                   double *__restrict__ part, int64_t maxChunks) {
-    const NestedSumJob jb = jobs[blockIdx.y];
-    const int64_t chunk = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (chunk * DWB_CHUNK >= jb.n) return;
-    const int64_t left = jb.n - chunk * DWB_CHUNK;
-    NestedIdentity f;
-    part[(int64_t)blockIdx.y * maxChunks + chunk] =
-        dwb_chunk_sum_f(comp + jb.src + chunk * DWB_CHUNK, (int)(left < DWB_CHUNK ? left : DWB_CHUNK), f);
-}
-__global__ __launch_bounds__(64) void k_nested_fold(const NestedSumJob *__restrict__ jobs, int nJobs, const double *__restrict__ part,
-                                                    int64_t maxChunks, double *__restrict__ out) {
-    const int j = blockIdx.x * 64 + threadIdx.x;
-    if (j >= nJobs) return;
-    const int64_t nChunks = (jobs[j].n + DWB_CHUNK - 1) / DWB_CHUNK;
-    double s = 0.0;
-    if (nChunks > 0) s = part[(int64_t)j * maxChunks];
-    for (int64_t k = 1; k < nChunks; ++k) s = s + part[(int64_t)j * maxChunks + k];
-    out[j] = s;
-}
 
-#undef CSR_HD
 }  // namespace csr

@@ -4,7 +4,7 @@
 //
 // A TRACK is one float64 vector on the device (a chain's resident scores, an uploaded host vector, gathered templates); all
 // tracks of a call share one work-space layout in which track t owns the slots [slot, slot + padded n), padded to NULL_TILE.
-//   k_null_sort_tile   the monotone keys (dwb_key) of a tile of NULL_TILE values, sorted by a bitonic network in LDS; slots past n
+//   k_null_sort_tile   the monotone keys (np_key) of a tile of NULL_TILE values, sorted by a bitonic network in LDS; slots past n
 //                      hold the largest key, which no finite value has;
 //   k_null_merge       one merge-path pass: every thread finds its diagonal of a pair of sorted runs by bisection and merges
 //                      NULL_VT keys.  Keys only, so the output is a function of the values alone;
@@ -12,8 +12,8 @@
 //   k_null_hsm         the half-sample mode of a sorted prefix: one workgroup per track, one parallel arg-min per level (the plain
 //                      float64 subtraction, the LOWEST start among equal widths), until the window holds <= 3 values;
 //   k_null_eval        one elementwise pass dst[i] = e(src[i]) of a NullExpr: the template;
-//   k_null_sum         NumPy-order sums of e(src[i]): one thread per chunk of 8192 evaluates NumPy's pairwise tree
-//                      (dwb_chunk_sum_f); k_null_fold adds the chunk sums in ascending order;
+//   (csr_np_order.h)   NumPy-order sums of e(src[i]): k_np_chunk_sums<NullJob>, one thread per chunk of 8192, evaluates NumPy's
+//                      pairwise tree; k_np_fold<NullJob> adds the chunk sums in ascending order;
 //   k_null_flag_count, k_null_scan, k_null_scatter   the stable compaction of the support |x - centre| <= radius (count per
 //                      tile, exclusive scan over a track's tiles, scatter in track order);
 //   k_null_gather, k_null_search   single values of a sorted track, and how many of its values satisfy (x - a) < b or <= b (one
@@ -24,7 +24,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "csr_dwb.h"
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_null_sort_tile(const NullTrackDev *__re
     const int64_t i0 = (int64_t)blockIdx.x * NULL_TILE;
     if (i0 >= tr.padded) return;        // (uniform per workgroup)
     const int t = threadIdx.x;
-    for (int k = t; k < NULL_TILE; k += 256) s[k] = i0 + k < tr.n ? dwb_key(tr.src[i0 + k]) : ~0ull;
+    for (int k = t; k < NULL_TILE; k += 256) s[k] = i0 + k < tr.n ? np_key(tr.src[i0 + k]) : ~0ull;
     __syncthreads();
     for (int k = 2; k <= NULL_TILE; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void k_null_unkey(const NullTrackDev *__restri
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= tr.padded) return;
     double *d = reinterpret_cast<double *>(keys) + tr.slot + i;
-    *d = dwb_unkey(keys[tr.slot + i]);
+    *d = np_unkey(keys[tr.slot + i]);
 }
 
 // ---- the half-sample mode of sorted[slot .. slot + m[track]) --------------------------------------------------------------------
@@ -185,6 +185,8 @@ struct NullJob {
     double *dst;            // k_null_eval only
     int64_t n;
     NullExpr e;
+    __device__ const double *data(const double *) const { return src; }     // (a Job of k_np_chunk_sums / k_np_fold)
+    __device__ NullExpr elem() const { return e; }
 };
 // grid (ceil(longest / 256), jobs)
 __global__ __launch_bounds__(256) void k_null_eval(const NullJob *__restrict__ jobs) {
@@ -192,27 +194,6 @@ __global__ __launch_bounds__(256) void k_null_eval(const NullJob *__restrict__ j
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= jb.n) return;
     jb.dst[i] = jb.e(jb.src[i]);
-}
-// grid (ceil(maxChunks / 64), jobs): part[job * maxChunks + chunk]
-__global__ __launch_bounds__(64) void k_null_sum(const NullJob *__restrict__ jobs, double *__restrict__ part, int64_t maxChunks) {
-    const NullJob jb = jobs[blockIdx.y];
-    const int64_t chunk = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (chunk * DWB_CHUNK >= jb.n) return;
-    const int64_t left = jb.n - chunk * DWB_CHUNK;
-    const int len = (int)(left < DWB_CHUNK ? left : DWB_CHUNK);
-    const NullExpr e = jb.e;
-    part[(int64_t)blockIdx.y * maxChunks + chunk] = dwb_chunk_sum_f(jb.src + chunk * DWB_CHUNK, len, e);
-}
-// one thread per job: the chunk sums in ascending order
-__global__ __launch_bounds__(64) void k_null_fold(const NullJob *__restrict__ jobs, int nJobs, const double *__restrict__ part,
-                                                  int64_t maxChunks, double *__restrict__ out) {
-    const int j = blockIdx.x * 64 + threadIdx.x;
-    if (j >= nJobs) return;
-    const int64_t nChunks = (jobs[j].n + DWB_CHUNK - 1) / DWB_CHUNK;
-    double s = 0.0;
-    if (nChunks > 0) s = part[(int64_t)j * maxChunks];
-    for (int64_t k = 1; k < nChunks; ++k) s = s + part[(int64_t)j * maxChunks + k];
-    out[j] = s;
 }
 
 // ---- stable compaction of the support ------------------------------------------------------------------------------------------

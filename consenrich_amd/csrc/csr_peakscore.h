@@ -5,9 +5,9 @@
 // Segment scores.  A segment [a, b] of a float64 track against a view (threshold, null scale): the clipped excess
 // e[i] = clip((s[i] - thr) / scale, 0, inf), its np.sum, its np.max, sum / sqrt(len) and sum / len.
 //   k_peak_view_score  one wavefront per (segment, view).  np.sum is the ascending fold of the pairwise sums of chunks of
-//                      DWB_CHUNK values; the pairwise tree of a chunk ends in leaves of 64..128 values (dwb_leaf_f).  Lane 0 lists
-//                      the leaves of the chunk in order, the lanes sum one leaf each, lane 0 folds the leaf sums along the tree;
-//                      the maximum rides along and is reduced across the lanes at the end;
+//                      NP_CHUNK values; the pairwise tree of a chunk ends in leaves of 64..128 values (np_leaf_f).  Lane 0 walks
+//                      the tree (np_tree) to list the leaves of the chunk in order, the lanes sum one leaf each, lane 0 walks it
+//                      again with the leaf sums; the maximum rides along and is reduced across the lanes at the end;
 //   k_peak_view_pick   one thread per segment: score and mean of every view, the first view is the best and a later one replaces
 //                      it only if its score compares > (a NaN never replaces).
 // Empirical p and q values.  Both read the replay pool only through counts c(x) = #(pool >= x): the per-draw counts of
@@ -25,26 +25,23 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "csr_dwb.h"
+#include "csr_np_order.h"
 
 namespace csr {
 
 constexpr int PS_MAX_VIEWS = 16;        // views per call
 constexpr int PS_MAX_METRICS = 3;       // score, integrated excess, max excess
 constexpr int PS_LEAVES = 128;          // leaves of the pairwise tree of one chunk: a block above 128 values splits into parts of >= 64
-constexpr int PS_STACK = 16;            // depth of that tree (8192 -> <= 128 in 7 levels)
 // a block above 128 values splits at n / 2 - (n / 2) % 8 >= 64, so every leaf holds at least 64 values: a chunk has at most
-// DWB_CHUNK / 64 leaves, and its tree at most log2(DWB_CHUNK / 64) + 2 levels
-static_assert(PS_LEAVES * 64 >= DWB_CHUNK, "PS_LEAVES must hold the leaves of one chunk");
-static_assert((1 << (PS_STACK - 3)) * 64 >= DWB_CHUNK, "PS_STACK must hold the depth of one chunk's tree");
+// NP_CHUNK / 64 leaves
+static_assert(PS_LEAVES * 64 >= NP_CHUNK, "PS_LEAVES must hold the leaves of one chunk");
 
 // ---- segment scores ---------------------------------------------------------------------------------------------------------
-// np.max over values that are >= +0.0 or NaN: a NaN stays.  Which NaN, when a segment holds NaNs of DIFFERENT bit patterns (a score
-// track with several distinct NaNs), follows the lanes and not NumPy's index order; the sums add such NaNs in NumPy's order but take
+// np.max over values that are >= +0.0 or NaN (np_max_nan): a NaN stays.  Which NaN, when a segment holds NaNs of DIFFERENT bit
+// patterns (a score track with several distinct NaNs), follows the lanes and not NumPy's index order; the sums add such NaNs in NumPy's order but take
 // the hardware's choice of operand.  One NaN pattern per call -- a NaN threshold or null scale, np.nan in the track, an invalid
 // operation -- comes back bit for bit; that is what is supported and tested.
-__device__ __forceinline__ double ps_max(double a, double b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-// np.clip((x - off) / s, 0, None) of one element like dwb_excess, with every NaN bit for bit what the reference's host computes: a
+// np.clip((x - off) / s, 0, None) of one element like np_excess, with every NaN bit for bit what the reference's host computes: a
 // NaN operand comes through as it is, the first one if both are (here x - off is an add of the NEGATED threshold, which would flip
 // the sign of a NaN threshold), and an invalid operation (inf - inf, 0 / 0, inf / inf) gives the negative default NaN
 __device__ __forceinline__ double ps_excess(double x, double off, double s) {
@@ -72,7 +69,7 @@ struct PeakExcess {
     double &mx;
     __device__ __forceinline__ double operator()(double x) {
         const double v = ps_excess(x, off, s);
-        mx = ps_max(mx, v);
+        mx = np_max_nan(mx, v);
         return v;
     }
 };
@@ -90,8 +87,8 @@ struct PeakScoreArgs {
 __global__ __launch_bounds__(64) void k_peak_view_score(PeakScoreArgs a) {
     __shared__ int sLo[PS_LEAVES], sLen[PS_LEAVES];
     __shared__ double sSum[PS_LEAVES];
-    __shared__ int stLo[PS_STACK], stLen[PS_STACK], stStage[PS_STACK];
-    __shared__ double stLeft[PS_STACK];
+    __shared__ int stLen[NP_STACK];
+    __shared__ double stLeft[NP_STACK];
     __shared__ int sLeaves;
     const int seg = blockIdx.x, v = blockIdx.y, lane = threadIdx.x;
     int64_t s0 = a.starts[seg], e0 = a.ends[seg];
@@ -109,74 +106,32 @@ __global__ __launch_bounds__(64) void k_peak_view_score(PeakScoreArgs a) {
     const double *x = a.x + s0;
     double mx = 0.0, total = 0.0;
     PeakExcess f{a.thr[v], a.scale[v], mx};
-    for (int64_t c0 = 0; c0 < len; c0 += DWB_CHUNK) {
-        const int cl = (int)(len - c0 < DWB_CHUNK ? len - c0 : DWB_CHUNK);
+    for (int64_t c0 = 0; c0 < len; c0 += NP_CHUNK) {
+        const int cl = (int)(len - c0 < NP_CHUNK ? len - c0 : NP_CHUNK);
         if (lane == 0) {                // the leaves of the chunk's tree, left to right
-            int sp = 0, nl = 0;
-            stLo[0] = 0;
-            stLen[0] = cl;
-            while (sp >= 0) {
-                const int lo = stLo[sp], m = stLen[sp];
-                --sp;
-                if (m <= 128) {
-                    if (nl < PS_LEAVES) {
-                        sLo[nl] = lo;
-                        sLen[nl] = m;
-                    }
-                    ++nl;
-                    continue;
+            int nl = 0;
+            np_tree(cl, [&](int lo, int m) {
+                if (nl < PS_LEAVES) {
+                    sLo[nl] = lo;
+                    sLen[nl] = m;
                 }
-                int n2 = m / 2;
-                n2 -= n2 % 8;
-                ++sp;                   // the right part waits below the left one
-                stLo[sp] = lo + n2;
-                stLen[sp] = m - n2;
-                ++sp;
-                stLo[sp] = lo;
-                stLen[sp] = n2;
-            }
+                ++nl;
+                return 0.0;
+            }, stLen, stLeft);
             sLeaves = nl < PS_LEAVES ? nl : PS_LEAVES;
         }
         __syncthreads();
         const int nl = sLeaves;
-        for (int k = lane; k < nl; k += 64) sSum[k] = dwb_leaf_f(x + c0 + sLo[k], sLen[k], f);
+        for (int k = lane; k < nl; k += 64) sSum[k] = np_leaf_f(x + c0 + sLo[k], sLen[k], f);
         __syncthreads();
-        if (lane == 0) {                // dwb_chunk_sum_f's walk with the leaf sums taken in order
-            int sp = 0, next = 0;
-            stLen[0] = cl;
-            stStage[0] = 0;
-            double ret = 0.0;
-            while (sp >= 0) {
-                if (stStage[sp] == 0) {
-                    if (stLen[sp] <= 128) {
-                        ret = sSum[next++];
-                        --sp;
-                        continue;
-                    }
-                    int n2 = stLen[sp] / 2;
-                    n2 -= n2 % 8;
-                    stStage[sp] = 1;
-                    stLen[sp + 1] = n2;
-                    stStage[sp + 1] = 0;
-                    ++sp;
-                } else if (stStage[sp] == 1) {
-                    int n2 = stLen[sp] / 2;
-                    n2 -= n2 % 8;
-                    stLeft[sp] = ret;
-                    stStage[sp] = 2;
-                    stLen[sp + 1] = stLen[sp] - n2;
-                    stStage[sp + 1] = 0;
-                    ++sp;
-                } else {
-                    ret = stLeft[sp] + ret;
-                    --sp;
-                }
-            }
+        if (lane == 0) {                // the same walk with the leaf sums taken in order
+            int next = 0;
+            const double ret = np_tree(cl, [&](int, int) { return sSum[next++]; }, stLen, stLeft);
             total = c0 == 0 ? ret : total + ret;
         }
         __syncthreads();
     }
-    for (int d = 32; d > 0; d >>= 1) mx = ps_max(mx, __shfl_xor(mx, d, 64));
+    for (int d = 32; d > 0; d >>= 1) mx = np_max_nan(mx, __shfl_xor(mx, d, 64));
     if (lane == 0) {
         out[0] = total;
         out[1] = mx;
@@ -218,7 +173,7 @@ __global__ __launch_bounds__(256) void k_peak_nonfinite(const double *__restrict
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double v = x[i];
-    if (!(fabs(v) <= 1.7976931348623157e308)) atomicOr(flag, bit);
+    if (!np_finite(v)) atomicOr(flag, bit);
 }
 // np.searchsorted(sorted, x, side="left")
 __device__ __forceinline__ int64_t ps_lower_bound(const double *__restrict__ s, int64_t n, double x) {
@@ -307,7 +262,6 @@ struct PoolTrack {
     int64_t rowBase, rows, keep;        // rows of the track in the run's output; keep = min(rows, total cap)
     double *dst[3];                     // where its `keep` values of score / integrated / max go
 };
-__device__ __forceinline__ double ps_max_any(double a, double b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
 // grid (tracks); tracks without rows are not launched for
 __global__ __launch_bounds__(256) void k_pool_append(const PoolTrack *__restrict__ tracks, const double *__restrict__ score,
                                                      const double *__restrict__ integ, const double *__restrict__ mx,
@@ -323,14 +277,14 @@ __global__ __launch_bounds__(256) void k_pool_append(const PoolTrack *__restrict
     bool nan = false;
     for (int64_t i = th; i < t.rows; i += 256) {
         const double v = s[i];
-        best = ps_max_any(best, v);
+        best = np_max_nan(best, v);
         nan = nan || v != v;
     }
     if (nan) atomicOr(&sNan, 1);
     sM[th] = best;
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
-        if (th < h) sM[th] = ps_max_any(sM[th], sM[th + h]);
+        if (th < h) sM[th] = np_max_nan(sM[th], sM[th + h]);
         __syncthreads();
     }
     const bool over = t.rows > t.keep, undecided = over && sNan != 0;

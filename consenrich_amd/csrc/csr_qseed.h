@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -46,13 +47,12 @@ struct QsArgs {
 __device__ __forceinline__ int64_t qs_sample_index(int64_t i, int64_t items, int64_t samples) {   // pyx:1431-1438
     return (int64_t)floor((((double)i + 0.5) * (double)items) / (double)samples);
 }
-__device__ __forceinline__ bool qs_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN
 
 __device__ __forceinline__ bool qs_active(const QsArgs &a, int64_t j, int64_t k) {
     const int64_t i = j * a.stride + k;
     if (a.src64) return a.act[i] != 0;
     const double z = (double)a.data[i], v = (double)a.munc[i], o = v + a.pad;            // core.py:2998-3003
-    return qs_finite(z) && qs_finite(v) && v < a.maskedHalf && qs_finite(o) && o > 0.0;
+    return np_finite(z) && np_finite(v) && v < a.maskedHalf && np_finite(o) && o > 0.0;
 }
 __device__ __forceinline__ double qs_z(const QsArgs &a, int64_t j, int64_t k) {
     const int64_t i = j * a.stride + k;
@@ -79,14 +79,14 @@ __global__ __launch_bounds__(256) void k_qs_count(QsArgs a) {
         if (!(qs_active(a, j, k) && qs_active(a, j, k + 1))) continue;
         const double dl = qs_z(a, j, k), dr = qs_z(a, j, k + 1), ol = qs_obs(a, j, k), orr = qs_obs(a, j, k + 1);
         int code = 0;
-        if (!qs_finite(dl) || !qs_finite(dr)) code = 1;
-        else if (!qs_finite(ol) || !qs_finite(orr) || ol <= 0.0 || orr <= 0.0) code = 2;
+        if (!np_finite(dl) || !np_finite(dr)) code = 1;
+        else if (!np_finite(ol) || !np_finite(orr) || ol <= 0.0 || orr <= 0.0) code = 2;
         else {
             const double diff = dr - dl, rd = ol + orr;
-            if (!qs_finite(diff) || !qs_finite(rd) || rd <= 0.0) code = 3;
+            if (!np_finite(diff) || !np_finite(rd) || rd <= 0.0) code = 3;
             else {
                 const double rp = 1.0 / rd;
-                if (!qs_finite(rp) || rp <= 0.0) code = 4;
+                if (!np_finite(rp) || rp <= 0.0) code = 4;
             }
         }
         if (code) atomicMin(a.firstErr, ((unsigned long long)(si * a.m + j) << 8) | (unsigned long long)code);
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void k_qs_pooled(QsArgs a) {
     for (int64_t j = 0; j < a.m; ++j) {
         if (!qs_active(a, j, i)) continue;
         const double v = qs_z(a, j, i), o = qs_obs(a, j, i);
-        if (!qs_finite(v) || !qs_finite(o) || o <= 0.0) {
+        if (!np_finite(v) || !np_finite(o) || o <= 0.0) {
             atomicMin(a.firstErr, ((unsigned long long)i << 8) | 6ull);
             continue;
         }
@@ -268,11 +268,6 @@ __global__ __launch_bounds__(256) void k_qs_pooled(QsArgs a) {
     a.pooledVar[i] = wsum > 0.0 ? 1.0 / wsum : nan;
 }
 
-// order-preserving key of a float32
-__device__ __forceinline__ unsigned qs_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // one radix pass of the exact-median selection over the ACTIVE float32 variances of a chain: histogram of the digit at
 // `shift` among the keys whose higher digits equal `prefix` (mask = those digits)
 __global__ __launch_bounds__(256) void k_qs_hist(QsArgs a, int shift, unsigned mask, unsigned prefix,
@@ -284,7 +279,7 @@ __global__ __launch_bounds__(256) void k_qs_hist(QsArgs a, int shift, unsigned m
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
         const int64_t j = e / a.n, k = e - j * a.n;
         if (!qs_active(a, j, k)) continue;
-        const unsigned key = qs_key(a.munc[j * a.stride + k]);
+        const unsigned key = np_key(a.munc[j * a.stride + k]);
         if ((key & mask) == prefix) atomicAdd(&lh[(key >> shift) & 255u], 1u);
     }
     __syncthreads();

@@ -20,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -302,25 +303,12 @@ __device__ __forceinline__ unsigned long long rocco_run_flags(const RoccoRunArgs
     }
     return (st ? 1ull : 0ull) | (en ? (1ull << 32) : 0ull);
 }
-// inclusive scan of one value per thread over a 1024-thread workgroup
-__device__ __forceinline__ unsigned long long rocco_block_scan(unsigned long long v, unsigned long long *sh) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63) sh[wv] = v;
-    __syncthreads();
-    unsigned long long base = 0ull;
-    for (int k = 0; k < wv; ++k) base += sh[k];
-    __syncthreads();
-    return v + base;
-}
 __global__ __launch_bounds__(1024) void k_rocco_run_count(RoccoRunArgs a) {
     __shared__ unsigned long long sh[16];
     const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-    const unsigned long long inc = rocco_block_scan(rocco_run_flags(a, i), sh);
-    if (threadIdx.x == 1023) a.blockSum[blockIdx.x] = inc;
+    unsigned long long total;         // (one scan per launch: wg_scan's barrier in front of its LDS write has nothing to wait for)
+    wg_scan<1024>(rocco_run_flags(a, i), sh, total);
+    if (threadIdx.x == 1023) a.blockSum[blockIdx.x] = total;
 }
 __global__ __launch_bounds__(1024) void k_rocco_run_scan(RoccoRunArgs a, int64_t nb) {
     __shared__ unsigned long long sh[16];
@@ -330,11 +318,14 @@ __global__ __launch_bounds__(1024) void k_rocco_run_scan(RoccoRunArgs a, int64_t
     for (int64_t b0 = 0; b0 < nb; b0 += 1024) {
         const int64_t b = b0 + threadIdx.x;
         const unsigned long long v = b < nb ? a.blockSum[b] : 0ull;
-        const unsigned long long inc = rocco_block_scan(v, sh);
+        // wg_scan's barrier stands in front of its write of sh, so the next round's call waits for this round's reads of sh; no
+        // barrier is needed behind the scan.  carry keeps its own two: read by all, barrier, written by one, barrier
+        unsigned long long total;
+        const unsigned long long inc = wg_scan<1024>(v, sh, total);
         const unsigned long long c = carry;
         if (b < nb) a.blockSum[b] = c + inc - v;        // exclusive
         __syncthreads();
-        if (threadIdx.x == 1023) carry = c + inc;
+        if (threadIdx.x == 1023) carry = c + total;
         __syncthreads();
     }
     if (threadIdx.x == 0) a.blockSum[nb] = carry;
@@ -343,7 +334,8 @@ __global__ __launch_bounds__(1024) void k_rocco_run_write(RoccoRunArgs a) {
     __shared__ unsigned long long sh[16];
     const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
     const unsigned long long fl = rocco_run_flags(a, i);
-    const unsigned long long ex = rocco_block_scan(fl, sh) - fl + a.blockSum[blockIdx.x];
+    unsigned long long total;         // (one scan per launch, as in k_rocco_run_count)
+    const unsigned long long ex = wg_scan<1024>(fl, sh, total) - fl + a.blockSum[blockIdx.x];
     const int64_t ks = (int64_t)(ex & 0xffffffffull), ke = (int64_t)(ex >> 32);
     if ((fl & 1ull) && ks < a.capacity) a.starts[ks] = i;
     if ((fl >> 32) && ke < a.capacity) a.ends[ke] = i;

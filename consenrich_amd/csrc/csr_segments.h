@@ -26,7 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "csr_dwb.h"
+#include "csr_np_order.h"
 
 namespace csr {
 
@@ -155,29 +155,6 @@ __global__ __launch_bounds__(256) void k_seg_excess(SegArgs a) {
     a.excess[(int64_t)blockIdx.y * a.rowLen + ch.off + i] = e;
 }
 
-// exclusive scan of one int per thread over a workgroup of 256; sW: four ints of LDS
-__device__ __forceinline__ int seg_block_scan(int v, int *sW, int &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();            // (sW may still be read from the previous call)
-    if (lane == 63) sW[wv] = inc;
-    __syncthreads();
-    int pre = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int s = sW[k];
-        if (k < wv) pre += s;
-        total += s;
-    }
-    return pre + inc - v;
-}
-
 struct SegJob {
     int r, s, v;
     int64_t j;
@@ -229,7 +206,7 @@ __global__ __launch_bounds__(256) void k_seg_count(SegArgs a) {
             sum += f[k];
         }
         int total;
-        int run = carry + seg_block_scan(sum, sW, total);
+        int run = carry + wg_scan<256>(sum, sW, total) - sum;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (i0 + k < n) {
@@ -270,7 +247,7 @@ __global__ __launch_bounds__(256) void k_seg_runs(SegArgs a) {
             sum += st[k];
         }
         int total;
-        int run = carry + seg_block_scan(sum, sW, total);
+        int run = carry + wg_scan<256>(sum, sW, total) - sum;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (st[k]) rs[run] = (int)(i0 + k);
@@ -363,21 +340,16 @@ __global__ __launch_bounds__(256) void k_seg_select(SegArgs a) {
         const unsigned long long want = pre;
         for (int k = t; k < nr; k += 256)
             if (keep[k]) {
-                const unsigned long long key = dwb_key(score[k] + 0.0);
+                const unsigned long long key = np_key(score[k] + 0.0);
                 const unsigned long long hi = pass == 0 ? 0ull : key >> (shift + 8);
                 if (hi == want) atomicAdd(&h[(unsigned int)(key >> shift) & 255u], 1u);
             }
         __syncthreads();
         if (t == 0) {
-            long long cum = 0;
-            int digit = 255;
-            for (int d = 0; d < 256; ++d) {
-                const long long c = (long long)h[d];
-                if (rk < cum + c) { digit = d; break; }
-                cum += c;
-            }
+            long long before;
+            const int digit = radix_pick_digit(h, rk, &before);
             pre = (pre << 8) | (unsigned long long)digit;
-            rk -= cum;
+            rk -= before;
         }
         __syncthreads();
     }
@@ -385,7 +357,7 @@ __global__ __launch_bounds__(256) void k_seg_select(SegArgs a) {
     int g = 0, e = 0;
     for (int k = t; k < nr; k += 256)
         if (keep[k]) {
-            const unsigned long long key = dwb_key(score[k] + 0.0);
+            const unsigned long long key = np_key(score[k] + 0.0);
             g += key > T;
             e += key == T;
         }
@@ -395,7 +367,7 @@ __global__ __launch_bounds__(256) void k_seg_select(SegArgs a) {
     const bool flagged = sBad != 0 || sEqual > a.cap - sGreater;
     if (!flagged)
         for (int k = t; k < nr; k += 256)
-            if (keep[k] && dwb_key(score[k] + 0.0) >= T) keep[k] = 3;
+            if (keep[k] && np_key(score[k] + 0.0) >= T) keep[k] = 3;
     if (t == 0) a.meta[job] = SegMeta{nr, K, 1, flagged ? 1 : 0, flagged ? 0 : a.cap, 0};
 }
 
@@ -413,9 +385,9 @@ __global__ __launch_bounds__(256) void k_seg_emit(SegArgs a) {
     int carry = 0;
     for (int k0 = 0; k0 < m.nRuns; k0 += 256) {
         const int k = k0 + t;
-        const int f = (k < m.nRuns && a.keep[ro + k] == 3) ? 1 : 0;
+        const bool f = k < m.nRuns && a.keep[ro + k] == 3;
         int total;
-        const int pos = carry + seg_block_scan(f, sW, total);
+        const int pos = carry + wg_rank256(f, sW, &total);      // (a 0/1 flag: the ballot rank costs less than the scan)
         if (f && pos < m.emit) {
             const int64_t o = base + pos;
             a.oStart[o] = a.rStart[ro + k];

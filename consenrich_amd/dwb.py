@@ -19,21 +19,11 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._lib import _c_int, _f64
 
 TINY = float(np.finfo(np.float64).tiny)
 _QMETHOD = "interpolated_inverted_cdf"
 MAX_Z = 8       # two ranks per z, 16 ranks per draw on the device
-
-
-def _f64(x):
-    return np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1), dtype=np.float64)
-
-
-def _c_int(v) -> int:
-    v = int(v)
-    if not -(1 << 31) <= v < (1 << 31):
-        raise OverflowError("value too large to convert to int")
-    return v
 
 
 def kernel_code(kernel) -> int:

@@ -20,18 +20,12 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._lib import _c_int
 
 TINY = float(np.finfo(np.float64).tiny)         # peaks.py:73 `_TINY`
 BUDGET_MIN, BUDGET_MAX = 0.001, 0.25            # constants.py `ROCCO_BUDGET_MIN`, `ROCCO_BUDGET_MAX` (peaks.py:74-75)
 MAX_Z = 16
 KINDS = {"occupancy": L.ESS_OCCUPANCY, "soft": L.ESS_SOFT, "integrated": L.ESS_INTEGRATED}
-
-
-def _c_int(v) -> int:
-    v = int(v)
-    if not -(1 << 31) <= v < (1 << 31):
-        raise OverflowError("value too large to convert to int")
-    return v
 
 
 def cEstimateEffectiveSampleSize(values, maxLag, activeMask=None, logPositive=False, windowIntervals=0):

@@ -23,6 +23,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._lib import _vp
 
 MIN_PEAK_BP = 200
 MULTIPLIER = 2.0
@@ -36,10 +37,6 @@ PEAK = np.dtype([("start", "<i8"), ("end", "<i8"), ("untrimmed_start", "<i8"), (
                  ("chain", "<i4"), ("parent", "<i4"), ("num_subpeaks", "<i4"), ("flags", "<i4"), ("median_state", "<f8"),
                  ("local_median_p", "<f8"), ("max_state", "<f8"), ("max_score", "<f8"), ("subpeak_objective", "<f8"),
                  ("subpeak_boundary_penalty", "<f8")])
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def validate_multiplier(value):

@@ -15,6 +15,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._lib import _vp
 
 EDGE = 1.0e-12
 POLICY = "soft_selection_penalty"
@@ -29,10 +30,6 @@ REC = np.dtype([("required", "<i8"), ("selected_count", "<i8"), ("child_base", "
                 ("objective", "<f8"), ("penalized", "<f8"), ("boundary_penalty", "<f8"), ("run_penalty_total", "<f8"),
                 ("parent_penalized", "<f8"), ("split_gain", "<f8")])
 NODE = np.dtype([("start", "<i8"), ("end", "<i8"), ("required", "<i8"), ("raw_score_max", "<f8"), ("score_sum", "<f8")])
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _float_vector(name, values):

@@ -26,7 +26,8 @@ from collections.abc import Mapping
 import numpy as np
 
 from . import _lib as L
-from .segments import Views, _f64, _i64p, _i32p
+from ._lib import _f64, _i32p, _i64p
+from .segments import Views
 
 MAX_VIEWS = 16
 METRICS = ("score", "integrated_excess", "max_excess")      # the reference's width_adjusted_mass, integrated_excess, max_excess

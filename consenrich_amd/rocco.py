@@ -14,6 +14,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._lib import _c_int, _f64
 
 _I64_MAX = (1 << 63) - 1
 
@@ -22,18 +23,6 @@ def set_depth(depth: int) -> None:
     """Speculation depth D of the calibration for the calls of this module (1..8, 0 = default): 2^D - 1 penalties run side by
     side per round.  Changes speed only."""
     L.check(L.lib().csr_set_rocco_depth(None, int(depth)))
-
-
-def _f64(x):
-    return np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel(), dtype=np.float64)
-
-
-def _c_int(v) -> int:
-    """A Cython `int` argument: truncated like C, OverflowError outside int32 (pyx:8850-8851, 8882)."""
-    v = int(v)
-    if not -(1 << 31) <= v < (1 << 31):
-        raise OverflowError("value too large to convert to int")
-    return v
 
 
 def _clip_i64(v) -> int:

@@ -18,6 +18,7 @@ from collections.abc import Mapping
 import numpy as np
 
 from . import _lib as L
+from ._lib import _c_int, _f64, _i32p, _i64, _i64p
 
 TINY = float(np.finfo(np.float64).tiny)
 MAX_SEGMENTS = 20000            # peaks.py:122-123
@@ -30,29 +31,6 @@ _last = dict(capped_views=0, fallback_views=0)
 def last_run_stats() -> dict:
     """Of the last device run of this process: views that hit the cap, and how many of them NumPy decided on the host."""
     return dict(_last)
-
-
-def _f64(x):
-    return np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1), dtype=np.float64)
-
-
-def _i64(x):
-    return np.ascontiguousarray(np.asarray(x, dtype=np.int64).reshape(-1), dtype=np.int64)
-
-
-def _c_int(v) -> int:
-    v = int(v)
-    if not -(1 << 31) <= v < (1 << 31):
-        raise OverflowError("value too large to convert to int")
-    return v
-
-
-def _i32p(a):
-    return a.ctypes.data_as(L.I32P)
-
-
-def _i64p(a):
-    return a.ctypes.data_as(L.I64P)
 
 
 def collect(ctx, rows_per_track, counters, n_flagged, cap):

@@ -269,6 +269,105 @@ def test_chain_tracks_header_selects_chains_as_the_peak_stages_expect(tmp_path):
     assert r.returncode == 0 and "chain_tracks_check ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+NP_ORDER_LENS = [0, 1, 7, 8, 9, 15, 16, 17, 127, 128, 129, 135, 136, 137, 255, 256, 257, 8191, 8192, 8193, 16384, 16385, 24706]
+NP_ORDER_FUNCTOR_LENS = [129, 8193, 16385]
+
+
+def test_np_order_header_sums_keys_and_selects_as_numpy_does(tmp_path):
+    """consenrich_amd/csrc/csr_np_order.h is __host__ __device__: tests/native/np_order_host_check.hip runs it on the CPU under the
+    address and undefined-behaviour sanitizers.  np_sum_f against np.sum bit for bit at every length where the pairwise tree
+    changes shape (leaf, split, chunk fold), with the identity, a shift and the excess-and-count element; the tree walked twice
+    (leaves recorded, then leaf sums) against np_chunk_sum_f; the ordered keys and their inverse; the two serial steps of the
+    radix select on hand-made histograms."""
+    import shutil
+    import subprocess
+
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    exe = str(tmp_path / "np_order_host_check")
+    subprocess.check_call([hipcc, "-O1", "-g", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-Xarch_host",
+                           "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-o", exe,
+                           os.path.join(ROOT, "tests", "native", "np_order_host_check.hip")])
+    rng = np.random.default_rng(20261020)
+    n = max(NP_ORDER_LENS)
+    x = rng.standard_normal(n) * 10.0 ** rng.integers(-8, 8, n)
+    c, off, s = 0.37, -0.25, 1.75
+
+    def key_values(dtype, decades):
+        fi = np.finfo(dtype)
+        edges = [-np.inf, -fi.max, -1.0, -fi.smallest_subnormal, -0.0, 0.0, fi.smallest_subnormal, 1.0, fi.max, np.inf]
+        return np.asarray(edges + list(rng.standard_normal(1000) * 10.0 ** rng.integers(-decades, decades, 1000)), dtype)
+
+    kd, kf = key_values(np.float64, 300), key_values(np.float32, 30)
+
+    def hist(counts):
+        h = np.zeros(256, np.uint32)
+        for digit, cnt in counts.items():
+            h[digit] = cnt
+        return h
+
+    # (histogram, rank) -> (digit, count of the digits below it)
+    picks = [(hist({3: 5, 9: 2}), 0, (3, 0)),                   # the rank at the first count
+             (hist({3: 5, 9: 2}), 6, (9, 5)),                   # ... at the last
+             (hist({3: 5, 9: 2}), 4, (3, 0)),                   # on the boundary between two digits: the last of digit 3
+             (hist({3: 5, 9: 2}), 5, (9, 5)),                   # ... the first of digit 9
+             (hist({0: 1, 1: 1, 2: 1}), 1, (1, 1)),
+             (hist({255: 7}), 6, (255, 0)),                     # all mass in digit 255
+             (hist({255: 7}), 0, (255, 0)),
+             (hist({0: 4, 255: 4}), 4, (255, 4))]
+    # (ranks, prefixes) -> the first target with the same prefix, -1 for an unused target
+    groups = [([0, 5, 9], [0, 0, 0], [0, 0, 0]),
+              ([0, 5, 9], [1, 2, 1], [0, 1, 0]),
+              ([-1, 5, 9, 2], [7, 7, 7, 8], [-1, 1, 1, 3]),
+              ([4, -1, 4, 4, 6, 6], [3, 3, 5, 3, 5, 9], [0, -1, 2, 0, 2, 5]),
+              ([-1, -1], [0, 0], [-1, -1])]
+    src = tmp_path / "np_order.bin"
+    with open(src, "wb") as fh:
+        for arr in (x, np.asarray(NP_ORDER_LENS, np.int64), np.asarray(NP_ORDER_FUNCTOR_LENS, np.int64)):
+            fh.write(np.asarray([arr.size], np.int64).tobytes() + arr.tobytes())
+        fh.write(np.asarray([c, off, s], np.float64).tobytes())
+        for arr in (kd, kf):
+            fh.write(np.asarray([arr.size], np.int64).tobytes() + arr.tobytes())
+        fh.write(np.asarray([len(picks)], np.int64).tobytes())
+        for h, rank, _ in picks:
+            fh.write(h.tobytes() + np.asarray([rank], np.int64).tobytes())
+        fh.write(np.asarray([len(groups)], np.int64).tobytes())
+        for rank, prefix, _ in groups:
+            fh.write(np.asarray([len(rank)], np.int64).tobytes() + np.asarray(rank, np.int64).tobytes()
+                     + np.asarray(prefix, np.uint64).tobytes())
+    r = subprocess.run([exe, str(src)], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
+    out = {}
+    for line in r.stdout.splitlines():
+        out.setdefault(line.split()[0], []).append(line.split()[1:])
+
+    def b64(v):
+        return int(np.asarray([v], np.float64).view(np.uint64)[0])
+
+    assert [(int(a), int(b, 16)) for a, b in out["sum"]] == [(k, b64(np.sum(x[:k]))) for k in NP_ORDER_LENS]
+    capped = [min(k, 8192) for k in NP_ORDER_LENS]
+    assert [(int(a), int(b, 16), int(d, 16)) for a, b, d in out["tree"]] == [(k, b64(np.sum(x[:k])), b64(np.sum(x[:k]))) for k in capped]
+    assert [(int(a), int(b, 16)) for a, b in out["shift"]] == [(k, b64(np.sum(x[:k] - c))) for k in NP_ORDER_FUNCTOR_LENS]
+    assert [(int(a), int(b, 16), int(d)) for a, b, d in out["excess"]] == \
+        [(k, b64(np.sum(np.clip((x[:k] - off) / s, 0, None))), int((x[:k] > off).sum())) for k in NP_ORDER_FUNCTOR_LENS]
+    # sums of -0.0 alone.  Below 8 values the leaf starts from 0.0 and the sum is +0.0, as np.sum gives.  From 8 values on the
+    # eight accumulators start from the values themselves and the tree keeps -0.0, where np.sum (2.2.6) answers +0.0: the one
+    # known difference from NumPy, a zero's sign, in every stage since the first of them; pinned here as it is
+    zeros = [(int(a), int(b, 16)) for a, b in out["zeros"]]
+    assert zeros[:8] == [(k, b64(np.sum(np.full(k, -0.0)))) for k in range(8)] and all(b == 0 for _, b in zeros[:8])
+    assert zeros[8:] == [(k, b64(-0.0)) for k in (8, 9, 130)]
+    for name, vals, uint in (("keyd", kd, np.uint64), ("keyf", kf, np.uint32)):
+        keys = np.asarray([int(a, 16) for a, _ in out[name]], uint)
+        back = np.asarray([int(b, 16) for _, b in out[name]], uint)
+        assert np.array_equal(back, vals.view(uint)), name                       # np_unkey(np_key(v)) is v bit for bit
+        assert np.array_equal(vals[np.argsort(keys, kind="stable")], np.sort(vals)), name
+        assert keys[4] < keys[5] and vals[4] == 0 and np.signbit(vals[4]) and not np.signbit(vals[5]), name     # -0.0 before +0.0
+        assert np.unique(keys).size == np.unique(vals.view(uint)).size, name
+    assert [(int(a), int(b)) for a, b in out["pick"]] == [want for _, _, want in picks]
+    assert [[int(g) for g in row] for row in out["groups"]] == [want for _, _, want in groups]
+
+
 def test_qseed_posterior_fails_loudly_without_a_gpu():
     """The grid posterior of the Q0 seed (pyx:1905-2146) runs on the device since round 2 (csr_qseed_post.h; its golden
     vectors are checked under -m gpu, tests/test_gpu_qseed.py): without a GPU the call must raise, not compute on the host."""

@@ -68,7 +68,7 @@ def test_goldens_cover_the_outcomes():
 
 def test_long_window_sum_is_a_fold_of_pairwise_chunks():
     """np.sum of one contiguous float64 array longer than 8192 is the ascending fold of the pairwise sums of chunks of 8192 (one
-    pairwise tree over the whole array gives another last bit at 8193 values): the rule the device's depspan_np_sum states,
+    pairwise tree over the whole array gives another last bit at 8193 values): the rule the device's np_sum_f states,
     written out here and compared with np.sum itself."""
     def leaf(x):
         n = x.size
