@@ -255,6 +255,32 @@ class CleanupNode(C.Structure):
                [(k, C.c_int32) for k in ("found", "mode", "gap_bins", "reserved")]
 
 
+# broad mode (consenrich_amd/broad.py holds the records as NumPy structured arrays)
+BROAD_HAS_LOCAL_P, BROAD_DROPPED_MEDIAN, BROAD_NONFINITE = 1, 2, 4
+
+
+class BroadCfg(C.Structure):
+    _fields_ = [("multiplier", C.c_double), ("filter", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BroadParent(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("summit", C.c_int64), ("chain", C.c_int32), ("flags", C.c_int32)] + \
+               [(k, C.c_double) for k in ("median_state", "local_median_p", "max_state", "max_score", "mean_state", "mean_score")]
+
+
+class BroadRunCfg(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("selection_penalty", C.c_double), ("dip_fraction", C.c_double),
+                ("max_gap_bins", C.c_int64)]
+
+
+class BroadRunCounts(C.Structure):
+    _fields_ = [("support_runs", C.c_int64), ("touching_runs", C.c_int64), ("fallback", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BroadRun(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("gap_sum", C.c_double), ("chain", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DepspanCfg(C.Structure):
     _fields_ = [("window_bins", C.c_int64), ("max_lag_bins", C.c_int32), ("smoothing_bins", C.c_int32),
                 ("persistence_bins", C.c_int32), ("min_finite_pairs", C.c_int32), ("acf_threshold", C.c_double),
@@ -436,6 +462,15 @@ SYMBOLS = {
                                          C.c_void_p, I64P, C.c_void_p]),
     "csr_cleanup_plan": (C.c_int, [C.c_int32, C.c_int64, DP, I64P, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.c_void_p, I64P, C.c_void_p, C.c_void_p]),
+    "csr_broad_gap_sums": (C.c_int, [C.c_int64, DP, C.c_double, C.c_double, C.c_int64, I64P, I64P, DP]),
+    "csr_broad_rows": (C.c_int, [C.c_int32, I64P, DP, DP, DP, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_uint8), C.c_void_p]),
+    "csr_batch_rocco_weak": (C.c_int, [C.c_void_p, C.POINTER(RoccoCfg), C.c_char_p, C.POINTER(RoccoOut)]),
+    "csr_batch_rocco_weak_upload": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8)]),
+    "csr_batch_rocco_weak_download": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8)]),
+    "csr_batch_broad_parent_download": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8)]),
+    "csr_batch_broad_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, I64P, I64P, C.c_void_p, I64P]),
+    "csr_batch_broad_runs_fetch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "csr_batch_broad_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p]),
     # (mats: an array of pointers to float32 matrices; the window records are a NumPy structured array: consenrich_amd/depspan.py)
     "csr_depspan_unique_rows": (C.c_int, [C.c_int32, I64P, C.POINTER(C.c_void_p), C.c_int64, I32P, I32P]),
     "csr_depspan_window_scores": (C.c_int, [C.c_int32, I64P, C.POINTER(C.c_void_p), C.c_int64, C.c_int32, I32P, C.c_int64,

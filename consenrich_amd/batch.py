@@ -103,6 +103,8 @@ class DeviceBatch:
         self.d = 2
         self._comms = []
         self._rocco_count = {}      # selected bins per chain of the last rocco() (an upper bound of its runs)
+        self._broad_parents = {}    # merged runs per chain of the last broad_parents()
+        self.broad_stats = None
         self._null = {}             # chain -> (null centre, null scale) of the last rocco_null()
 
     def _attach_comm(self, comm):
@@ -144,6 +146,7 @@ class DeviceBatch:
         self.m, self.d = int(m), int(model.state_dim)
         self.model = model
         self._null = {}             # the templates died with the previous batch
+        self._broad_parents = {}    # ... and so did the masks the parents were made of
 
     def set_model(self, model: ModelParams):
         mdl = model.to_c()
@@ -495,6 +498,7 @@ class DeviceBatch:
             raise ValueError("`uncertaintyScoreMode` must be 'state' or 'lower_confidence'")
         # (a negative variance or a bad z comes back as the reference's ValueError)
         L.check_value(self._lib.csr_batch_rocco_scores(self._ctx, modes[mode], float(z)))
+        self._broad_parents.clear()     # (new scores drop the masks on the device: the parents made of the old ones go with them)
 
     def upload_scores(self, chain: int, scores):
         s = np.ascontiguousarray(np.asarray(scores, dtype=np.float64).ravel())
@@ -503,6 +507,7 @@ class DeviceBatch:
         if not np.all(np.isfinite(s)):
             raise ValueError("`scores` contains non-finite values")
         L.check(self._lib.csr_batch_upload_scores(self._ctx, int(chain), L.dp(s)))
+        self._broad_parents.pop(int(chain), None)
 
     def download_scores(self, chain: int) -> np.ndarray:
         out = np.empty(self.chain_lens[chain], np.float64)
@@ -516,6 +521,10 @@ class DeviceBatch:
         chains with False are not solved and keep their previous mask.  Returns one dict per chain (None where not solved)
         with the reference's tuple values: objective, penalized_objective, selected_count, selection_penalty; the mask stays
         on the device (rocco_solution / rocco_runs)."""
+        return self._rocco_into(False, budget, gamma, selection_penalty, max_iter, chains)
+
+    def _rocco_into(self, weak, budget, gamma, selection_penalty, max_iter, chains):
+        """The body of `rocco` and `rocco_weak`: the strong or the weak solution track as destination"""
         from . import rocco as R
 
         nc = len(self.chain_lens)
@@ -537,14 +546,73 @@ class DeviceBatch:
                 cfg[i] = R.chrom_config(self.chain_lens[i], b[i], g[i], p[i], int(it[i]))
         out = (L.RoccoOut * nc)()
         mask = None if chains is None else bytes(bytearray(int(t) for t in take))
-        L.check(self._lib.csr_batch_rocco(self._ctx, cfg, mask, out))
+        L.check((self._lib.csr_batch_rocco_weak if weak else self._lib.csr_batch_rocco)(self._ctx, cfg, mask, out))
         for i in range(nc):
-            if take[i]:
+            if take[i] and not weak:
                 self._rocco_count[i] = int(out[i].selected_count)
         return [None if not take[i] else
                 {"objective": float(out[i].objective), "penalized_objective": float(out[i].penalized_objective),
                  "selected_count": int(out[i].selected_count), "selection_penalty": float(out[i].selection_penalty)}
                 for i in range(nc)]
+
+    def rocco_weak(self, budget=None, gamma=0.5, selection_penalty=None, max_iter=60, chains=None):
+        """`rocco` with the WEAK solution track as destination (broad mode's second pass: the same scores, the weak budget, twice the
+        gamma): same arguments and return.  The strong mask, its run counts and everything else resident stay untouched; the mask
+        is read by `broad_parents` and served by `weak_solution`."""
+        return self._rocco_into(True, budget, gamma, selection_penalty, max_iter, chains)
+
+    def weak_solution(self, chain: int) -> np.ndarray:
+        """The uint8 weak selection mask of one chain."""
+        out = np.empty(self.chain_lens[chain], np.uint8)
+        L.check(self._lib.csr_batch_rocco_weak_download(self._ctx, int(chain), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def upload_weak_solution(self, chain: int, solution):
+        """Plants the weak selection mask of one chain (a host-decided one: `solveChromROCCO`'s fallback window)."""
+        s = np.ascontiguousarray(np.asarray(solution).astype(np.uint8).ravel())
+        if s.shape != (self.chain_lens[chain],):
+            raise ValueError("solution must have shape (chain_len,)")
+        L.check(self._lib.csr_batch_rocco_weak_upload(self._ctx, int(chain), s.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def broad_parents(self, thresholds, selection_penalties, boundary_costs, *, max_gap_bp, intervals=None, ends=None, interval_bp=None,
+                      chroms=None, blacklist=None, dip_penalty_fraction=0.5, run_penalty=0.0, chains=None):
+        """Broad mode's envelope and bridging (peaks.py:6884-6932 with `_mergeBroadRunsByObjective`, 1898-2005) of every chain's
+        RESIDENT scores, strong mask (`rocco` / `rocco_nested`) and weak mask (`rocco_weak`), in one device call for all chains:
+        the runs of scores >= threshold cut at coordinate breaks, those that touch weak | strong (where none does: the runs of
+        weak | strong), and per kept run the NumPy-order sum of the dip-weighted excess of the bins up to the next one.  The host
+        decides every gap on its own from the compact records: distance (max_gap_bp, a value or one per chain), blacklist (a
+        dict of per-chromosome (k, 2) arrays), and the gain gapScore + 2 boundary_cost + run_penalty > 0.  thresholds /
+        selection_penalties / boundary_costs: one value per chain or one for all (the weak pass's threshold, selection penalty
+        and gamma).  Returns per chain (None where not taken) a dict: starts, ends (the merged runs), merge_details (the reference's
+        dict, both forms), weak_support_threshold, weak_support_run_count, weak_support_touching_run_count, envelope_fallback,
+        broad_bridge_dip_penalty_fraction.  The merged runs wait for `broadpeak_rows`; nothing resident changes."""
+        from . import broad as B
+
+        return B.batch_parents(self, thresholds, selection_penalties, boundary_costs, max_gap_bp=max_gap_bp, intervals=intervals,
+                               ends=ends, interval_bp=interval_bp, chroms=chroms, blacklist=blacklist,
+                               dip_penalty_fraction=dip_penalty_fraction, run_penalty=run_penalty, chains=chains)
+
+    def broad_parent_solution(self, chain: int) -> np.ndarray:
+        """The uint8 mask of one chain's bridged parents, as the last `broadpeak_rows` filled it."""
+        out = np.empty(self.chain_lens[chain], np.uint8)
+        L.check(self._lib.csr_batch_broad_parent_download(self._ctx, int(chain), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def broadpeak_rows(self, *, intervals=None, ends=None, interval_bp=None, chroms=None, prefix="consenrich", multiplier=2.0,
+                       use_uncertainty=True, min_peak_bp=1000, chains=None):
+        """The reference's broadPeak and gappedPeak rows (`_solutionToChromBroadPeakRows`, peaks.py:5606-5818) of the parents
+        `broad_parents` left, with the chain's strong mask as child mask: one wavefront per parent makes np.median, the leftmost
+        arg-max, np.max and np.mean of the signal, np.max and np.mean of the scores, np.median of the finite uncertainty values
+        and the median filter's flag from the resident scores and the smoothed fit (signal float64 of xs[:,0], uncertainty the
+        float32 square root of Ps00), and fills the resident parent mask (`broad_parent_solution`).  The host does the coordinate
+        work from compact records (consenrich_amd/broad.py).  A chain with a non-finite signal or score value inside a parent has
+        its parent numbers redone with NumPy on its downloaded tracks (`decided_on_host`).  Returns per chain (None where not
+        taken) a dict: broad_rows, gapped_rows, peak_meta, export_details, decided_on_host; `broad_stats` holds the counts and
+        seconds of the last `broad_parents` and `broadpeak_rows`."""
+        from . import broad as B
+
+        return B.batch_rows(self, intervals=intervals, ends=ends, interval_bp=interval_bp, chroms=chroms, prefix=prefix,
+                            multiplier=multiplier, use_uncertainty=use_uncertainty, min_peak_bp=min_peak_bp, chains=chains)
 
     def rocco_solution(self, chain: int) -> np.ndarray:
         """The uint8 selection mask of one chain."""

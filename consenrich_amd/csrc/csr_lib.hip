@@ -19,6 +19,7 @@
 #include "csr_nested.h"
 #include "csr_export.h"
 #include "csr_cleanup.h"
+#include "csr_broad.h"
 #include "csr_depspan.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
@@ -350,6 +351,8 @@ struct BatchState {
     // invalidates which is scores_changed()
     ChainTrack<double> scores{"scores"}, tmpl{"null template"};
     ChainTrack<unsigned char> sol{"ROCCO solution"};
+    // broad mode (csr_host_broad.inl): the weak pass's mask and the mask of the bridged parents
+    ChainTrack<unsigned char> weak{"weak ROCCO solution"}, broadParent{"broad parent mask"};
     // ROCCO's work arrays without presence (csr_host_rocco.inl): backtrace words, per-chain maxima and flags; its growable work
     // space is csr_ctx::roccoWs
     struct Rocco {
@@ -469,6 +472,12 @@ struct csr_ctx : BatchState {
     struct CleanupWs {
         DevBuf arena, work, kids, seg, cnt, node;
     } cleanupWs;
+    // broad mode (csr_host_broad.inl): the staged arrays, one work double per bin, the job and chain tables (or the gaps), the parent
+    // mask and the records (or the gap sums)
+    struct BroadWs {
+        DevBuf arena, work, mask, jobs, rec, runs;
+        std::vector<csr_broad_run> kept;    // the records of the last csr_batch_broad_runs (compact: they wait on the host)
+    } broadWs;
     // stationary-null DWB panel (csr_host_dwb.inl): chain table, weights, templates, the seed's noise stream and the rows of one
     // group of draws; growable, the large ones given back by csr_dwb_panel_end
     struct Dwb {
@@ -628,7 +637,11 @@ int ChainTrack<T>::download(csr_ctx *c, int chain, T *host) const {
 }
 // New scores of a chain: the selection mask made of the previous ones is dropped.  The chain's null template is NOT: it stays
 // present although it came from the previous scores -- that is how the stages have behaved since they landed, kept as it is.
-static void scores_changed(csr_ctx *c, int chain) { c->sol.set(chain, false); }
+static void scores_changed(csr_ctx *c, int chain) {
+    c->sol.set(chain, false);
+    if (c->weak.d) c->weak.set(chain, false);
+    if (c->broadParent.d) c->broadParent.set(chain, false);
+}
 
 static int need(csr_ctx *c);    // csr_host_batch.inl
 static int check_chain(const csr_ctx *c, int chain) {
@@ -930,4 +943,5 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_nested.inl"
 #include "csr_host_export.inl"
 #include "csr_host_cleanup.inl"
+#include "csr_host_broad.inl"
 #include "csr_host_depspan.inl"

@@ -751,6 +751,108 @@ def cleanup_peaks_batch(batch: DeviceBatch, exported, *, interval_bp, intervals=
     return out, policy
 
 
+def validate_broad_weak_threshold_z(value) -> float:
+    z = float(value)
+    if not np.isfinite(z) or z < 0.0:
+        raise ValueError("`broadWeakThresholdZ` must be finite and non-negative")
+    return z
+
+
+def validate_broad_max_gap_bp(value):
+    if value is None:
+        return None
+    if isinstance(value, bool):
+        raise ValueError("`broadMaxGapBP` must be an integer or None")
+    gap = int(value)
+    if gap != value or gap < 0:
+        raise ValueError("`broadMaxGapBP` must be a non-negative integer or None")
+    return gap
+
+
+def broad_peaks_batch(batch: DeviceBatch, nested, *, dependence_spans, threshold_z, threshold_z_grid, num_bootstrap, random_seed,
+                      weak_threshold_z: float = 1.2816, max_gap_bp=None, selection_penalty=None, interval_bp=None, intervals=None,
+                      ends=None, chroms=None, prefix="consenrichROCCO", blacklist=None, multiplier: float = 2.0,
+                      use_uncertainty: bool = True, min_peak_bp: int = 1000, pooled_floors=None) -> List[dict]:
+    """The link between `nested_peaks_batch` and `score_peaks_batch` in broad mode (`solveRocco` with peakMode="broad":
+    peaks.py:6743-6778, 6874-6960 and `_solutionToChromBroadPeakRows`), without a track leaving the device.  The weak pass has the
+    strong pass's score track, null and template; its budget is `dwb_panel` and `rocco_budget` once more at weak_threshold_z (the
+    same seed and grid), its gamma 2.0 times the chain's.  `rocco_weak` solves into the weak slot; `solveChromROCCO`'s fallback
+    window is decided on the host as in `first_pass_peaks_batch` and uploaded there.  `broad_parents` then runs with the weak
+    pass's threshold, selection penalty and gamma (dip fraction 0.5, no run penalty; max_gap_bp None: 4 * the dependence span *
+    the chain's median bin width), `broadpeak_rows` with the refined strong mask as child mask.  nested: what nested_peaks_batch
+    returned (the strong mask is the resident one).  Returns a copy of every record with broad_rows, gapped_rows, peak_meta,
+    export_details, broad_parent (the reference's broadParentDetails with its keys -- `weak_solve_details` holds what `rocco`
+    returns -- plus three of its own: envelope_fallback, and parent_starts / parent_ends, the merged runs), decided_on_host
+    (how many of the two host decisions the chain took: the fallback window, a non-finite value inside a parent), and `starts` /
+    `ends` = the KEPT parents' start_idx / end_idx -- accepted by `score_peaks_batch` unchanged."""
+    from . import ess as E
+    from . import rocco as R
+
+    weak_z = validate_broad_weak_threshold_z(weak_threshold_z)
+    max_gap = validate_broad_max_gap_bp(max_gap_bp)
+    if weak_z > float(threshold_z):
+        raise ValueError("`broadWeakThresholdZ` cannot exceed `thresholdZ`")
+    nc = len(batch.chain_lens)
+    if len(nested) != nc:
+        raise ValueError("one record per chain")
+    spans = [max(int(s), 2) for s in (dependence_spans if np.ndim(dependence_spans) else [dependence_spans] * nc)]
+    if len(spans) != nc:
+        raise ValueError("one dependence span per chain")
+    if intervals is None:
+        if interval_bp is None:
+            raise ValueError("`interval_bp` is needed where no coordinates are given")
+        intervals = [np.arange(n, dtype=np.int64) * int(interval_bp) for n in batch.chain_lens]
+        ends = [iv + int(interval_bp) for iv in intervals]
+    grid = E.resolve_z_grid(weak_z, threshold_z_grid)
+    panel = batch.dwb_panel(threshold_z_grid=grid, bandwidths=spans, num_bootstrap=num_bootstrap, random_seed=random_seed,
+                            calibration_quantile=0.9, pooled_floors=pooled_floors)
+    budgets = batch.rocco_budget(panel, statistic="occupancy", threshold_z=weak_z, threshold_z_grid=grid, dependence_spans=spans)
+    gammas = [2.0 * float(r["gamma"]) for r in nested]
+    weak = batch.rocco_weak(budget=[b["budget"] for b in budgets], gamma=gammas, selection_penalty=selection_penalty)
+    windows = [False] * nc
+    for ch, r in enumerate(weak):
+        if selection_penalty is None:
+            target = R.budget_target_count(batch.chain_lens[ch], budgets[ch]["budget"])
+            if r["selected_count"] == 0 and target is not None and target > 0:
+                scores = batch.download_scores(ch)
+                mask, used = R.best_contiguous_budget_fallback_mask(scores, target, 0.0, gammas[ch], maxRelativeRange=0.05)
+                if used:
+                    solution = mask.astype(np.uint8)
+                    batch.upload_weak_solution(ch, solution)
+                    r["selected_count"] = int(np.sum(solution))
+                    r["objective"] = R.objective_for_solution(scores, solution, gammas[ch])
+                    r["penalized_objective"] = float(r["objective"]) - float(r["selection_penalty"]) * float(r["selected_count"])
+                    windows[ch] = True
+    gaps = [max_gap if max_gap is not None else
+            int(4 * int(budgets[ch]["dependence_span"]) * max(int(np.median(np.asarray(ends[ch]) - np.asarray(intervals[ch]))), 1))
+            for ch in range(nc)]
+    parents = batch.broad_parents([b["threshold"] for b in budgets], [r["selection_penalty"] for r in weak], gammas, max_gap_bp=gaps,
+                                  intervals=intervals, ends=ends, chroms=chroms, blacklist=blacklist, dip_penalty_fraction=0.5,
+                                  run_penalty=0.0)
+    rows = batch.broadpeak_rows(intervals=intervals, ends=ends, chroms=chroms, prefix=prefix, multiplier=multiplier,
+                                use_uncertainty=use_uncertainty, min_peak_bp=min_peak_bp)
+    out = []
+    for ch, (r, p, g) in enumerate(zip(nested, parents, rows)):
+        q = dict(r)
+        q.update(broad_rows=g["broad_rows"], gapped_rows=g["gapped_rows"], peak_meta=g["peak_meta"], export_details=g["export_details"],
+                 decided_on_host=int(g["decided_on_host"]) + int(windows[ch]))
+        q["broad_parent"] = {
+            "enabled": True, "weak_threshold_z": weak_z, "weak_budget": float(budgets[ch]["budget"]),
+            "weak_objective": float(weak[ch]["objective"]), "weak_solve_details": dict(weak[ch], budget_fallback_window=windows[ch]),
+            "weak_budget_details": budgets[ch], "weak_gamma": gammas[ch],
+            "weak_gamma_details": {"method": "child_gamma_multiplier", "child_gamma": float(r["gamma"]), "parent_gamma_multiplier": 2.0,
+                                   "gamma": gammas[ch]},
+            "strong_child_union_applied": True, "weak_support_threshold": float(p["weak_support_threshold"]),
+            "weak_support_run_count": p["weak_support_run_count"],
+            "weak_support_touching_run_count": p["weak_support_touching_run_count"], "envelope_fallback": p["envelope_fallback"],
+            "broad_bridge_dip_penalty_fraction": p["broad_bridge_dip_penalty_fraction"], "max_gap_bp": int(gaps[ch]),
+            "merge_details": p["merge_details"], "parent_starts": p["starts"], "parent_ends": p["ends"]}
+        q["starts"] = np.asarray([m["start_idx"] for m in g["peak_meta"]], np.int64)
+        q["ends"] = np.asarray([m["end_idx"] for m in g["peak_meta"]], np.int64)
+        out.append(q)
+    return out
+
+
 def score_peaks_batch(batch: DeviceBatch, first_pass, panel, *, dependence_spans, random_seed, min_run_bins: int = 1,
                       num_replay: int = 64, draws_per_group: int = 0) -> List[dict]:
     """The next link after `first_pass_peaks_batch`: the reference's DWB peak scoring (`_addDWBPeakScoringToPeakMeta`,

@@ -964,6 +964,85 @@ int csr_cleanup_plan(int32_t op, int64_t n, const double *scores, const int64_t 
                      int64_t n_children, const csr_cleanup_child *children, const csr_cleanup_policy *policy, int64_t capacity,
                      csr_cleanup_segment *segments, int64_t *n_segments, csr_cleanup_counts *counts, csr_cleanup_node *nodes);
 
+/* ---- broad mode: the per-bin arithmetic of `_mergeBroadRunsByObjective` (peaks.py:1898-2005) and of
+ * `_solutionToChromBroadPeakRows` (5606-5818), on host arrays (default context) ----------------------------------------------
+ * Every value equals the reference's bit for bit.
+ *   csr_broad_gap_sums   sums[g] = np.sum(np.where(ex < 0, f * ex, ex)), ex = scores[gap_start[g] .. + gap_len[g]) -
+ *                        selection_penalty, f = dip_fraction (the caller clips it to [0, 1]), in NumPy's order; 0.0 for a gap
+ *                        of no bin.  The gaps may be given in any order and may overlap.  Distance, blacklist and the gain
+ *                        decision are the caller's: they need coordinates, and each gap is decided on its own.
+ *   csr_broad_rows       A PARENT is bins [start, end] (inclusive) of one chain without a coordinate gap, ascending by (chain,
+ *                        start) and disjoint (csr_export_parent).  One wavefront takes one parent.  records[k]: np.median, the
+ *                        leftmost arg-max (summit, a bin of the chain), np.max and np.mean of the signal, np.max and np.mean of
+ *                        the scores, and with cfg.filter and an uncertainty array np.median of its finite values
+ *                        (CSR_BROAD_HAS_LOCAL_P if there is one) and the flag median < -multiplier * that median
+ *                        (CSR_BROAD_DROPPED_MEDIAN: the record still comes back, the caller counts it).
+ *                        CSR_BROAD_NONFINITE: the parent's signal or scores hold a non-finite value, NumPy's maxima, medians
+ *                        and means then propagate NaN in ways no order statistic does; the caller decides such a chain on the
+ *                        host.  parent_mask (all bins of all chains, may be NULL): 1 inside a parent, 0 elsewhere.
+ * A non-finite or negative multiplier returns CSR_ERR_VALUE with the reference's text; parents outside their chain or not
+ * disjoint and ascending, and gaps outside the scores, fail plainly; every check comes before a device is touched.  Medians up
+ * to CSR_CLEANUP_SORT_TILE values are sorted in LDS, longer ones in global memory.  A maximum or a median that is a zero may
+ * carry either sign where both zeros occur.  Additive to ABI 6. */
+enum { CSR_BROAD_HAS_LOCAL_P = 1, CSR_BROAD_DROPPED_MEDIAN = 2, CSR_BROAD_NONFINITE = 4 };
+typedef struct csr_broad_cfg {      /* per chain */
+    double multiplier;
+    int32_t filter, reserved;
+} csr_broad_cfg;
+typedef struct csr_broad_parent {
+    int64_t start, end, summit;     /* bins of the chain */
+    int32_t chain, flags;
+    double median_state, local_median_p, max_state, max_score, mean_state, mean_score;
+} csr_broad_parent;
+int csr_broad_gap_sums(int64_t n, const double *scores, double selection_penalty, double dip_fraction, int64_t n_gaps,
+                       const int64_t *gap_start, const int64_t *gap_len, double *sums);
+int csr_broad_rows(int32_t n_chains, const int64_t *chain_len, const double *state, const double *scores,
+                   const double *uncertainty, const csr_broad_cfg *cfg, int64_t n_parents, const csr_export_parent *parents,
+                   unsigned char *parent_mask, csr_broad_parent *records);
+
+/* The same on the RESIDENT data of a batch.  Two more per-chain tracks live next to the scores, the template and the (strong)
+ * solution mask: the WEAK solution and the BROAD PARENT mask; new scores of a chain drop both.  The fit's arrays, the scores, the
+ * template and the strong mask are only read by every call below.
+ *   csr_batch_rocco_weak        csr_batch_rocco with the weak track as destination (same arguments and results); the strong mask
+ *                               and its flags stay untouched.  _upload / _download move one chain's weak mask (the caller's
+ *                               fallback window), csr_batch_broad_parent_download one chain's parent mask.
+ *   csr_batch_broad_runs        per taken chain (it needs scores, a strong and a weak mask): the runs of scores >= threshold, cut
+ *                               after every bin of the chain's ascending `breaks` (n_breaks[chain] of them, the chains one after the
+ *                               other; the caller forms them as flatnonzero(ends[:-1] != intervals[1:])); counts[chain].support_runs
+ *                               of them.  Kept are the runs that hold a bin of weak | strong (touching_runs); where a chain keeps
+ *                               none, the same kernels run once more with weak | strong as the predicate (fallback = 1).  Per kept
+ *                               run one record, in order: its bins, and gap_sum = csr_broad_gap_sums of the bins between it and the
+ *                               chain's next kept run under the chain's selection_penalty and dip_fraction (0.0 behind the last
+ *                               one, and for a gap of more than max_gap_bins bins, which the caller's distance test blocks anyway:
+ *                               no lane walks a gap that long).  *n_records = the records of all chains; csr_batch_broad_runs_fetch hands them out until the
+ *                               next call.  Flag, scan and compaction, over bins and then over runs: no atomic counter, no sort.
+ *   csr_batch_broad_rows        csr_broad_rows with the resident scores, as signal (double) xs[:,0] and as uncertainty
+ *                               (double)(float) sqrt(Ps00) of the reference-layout copies of the smoothed fit (cfg.filter) -- the
+ *                               values and the side-effect rule of csr_batch_rocco_scores.  It fills the parent mask of every
+ *                               taken chain (0 outside the call's parents). */
+typedef struct csr_broad_run_cfg {  /* per chain */
+    double threshold, selection_penalty, dip_fraction;
+    int64_t max_gap_bins;           /* a gap of more bins is not summed (gap_sum 0.0): the caller's distance test blocks it; < 0: none */
+} csr_broad_run_cfg;
+typedef struct csr_broad_run_counts {
+    int64_t support_runs, touching_runs;
+    int32_t fallback, reserved;
+} csr_broad_run_counts;
+typedef struct csr_broad_run {
+    int64_t start, end;             /* bins of the chain */
+    double gap_sum;
+    int32_t chain, reserved;
+} csr_broad_run;
+int csr_batch_rocco_weak(csr_ctx *ctx, const csr_rocco_cfg *cfg, const unsigned char *chain_mask, csr_rocco_out *out);
+int csr_batch_rocco_weak_upload(csr_ctx *ctx, int32_t chain, const unsigned char *solution);
+int csr_batch_rocco_weak_download(csr_ctx *ctx, int32_t chain, uint8_t *solution);
+int csr_batch_broad_parent_download(csr_ctx *ctx, int32_t chain, uint8_t *mask);
+int csr_batch_broad_runs(csr_ctx *ctx, const csr_broad_run_cfg *cfg, const unsigned char *chain_mask, const int64_t *n_breaks,
+                         const int64_t *breaks, csr_broad_run_counts *counts, int64_t *n_records);
+int csr_batch_broad_runs_fetch(csr_ctx *ctx, int64_t capacity, csr_broad_run *records);
+int csr_batch_broad_rows(csr_ctx *ctx, const csr_broad_cfg *cfg, const unsigned char *chain_mask, int64_t n_parents,
+                         const csr_export_parent *parents, csr_broad_parent *records);
+
 /* ---- the dependence span: the device stages of pyx:3360-4120 `cchooseDependenceSpan` (helpers pyx:2645-3357) ------------------
  * Three stages, each on host arrays (default context; mats[k] = n_rows x n_bins[k] float32 in C order, staged one chromosome or one
  * window set at a time) and on the RESIDENT data of the listed chains of a batch (chains[k]: a chain index; a fold chain is left
