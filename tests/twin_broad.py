@@ -301,6 +301,14 @@ def _device_kept_runs(s, env, threshold, breaks, n, envelope):
         took("run_from_bin_0", int(t and a == 0))
         took("run_to_last_bin", int(t and b == n - 1))
         took("run_across_block_edge", int(t and a // 1024 != b // 1024))
+    # the second level of the launches and scans (tests/second_level_cases.py): a second workgroup of the passes over the runs, of the
+    # gap sums (64 kept runs each), a second round of the scan of the bins' block sums, a break list longer than a block of runs
+    kept = sum(touch)
+    took("support_runs_over_block", int(len(runs) > 1024))
+    took("kept_runs_over_wave", int(kept > 64))
+    took("kept_runs_over_block", int(kept > 1024))
+    took("bins_over_carry_round", int(n > 1024 * 1024))
+    took("breaks_over_block", int(len(breaks) > 1024))
     return runs, [r for r, t in zip(runs, touch) if t]
 
 
