@@ -171,6 +171,10 @@ ROCCO_SCORE_STATE, ROCCO_SCORE_LOWER_CONFIDENCE = 0, 1
 ERR_VALUE = 2       # CSR_ERR_VALUE: what the reference answers with ValueError (check_value); the stages' own names are aliases
 ROCCO_ERR_VALUE = DWB_ERR_VALUE = SEG_ERR_VALUE = NULL_ERR_VALUE = ESS_ERR_VALUE = ERR_VALUE
 ESS_OCCUPANCY, ESS_SOFT, ESS_INTEGRATED = 1, 2, 3
+SHRINK_TRACKS = {"shrunk": 0, "posterior_sd": 1, "spike_prop": 2, "slab_mean": 3, "slab_weight": 4, "variance": 5}
+SHRINK_MAX_SLABS = 96
+ARR_SHRINK_BASE = 64         # writers: ARR_SHRINK_BASE + SHRINK_TRACKS[name] as array id
+SIGNALS = {"state": 0, "shrunk": 1}
 PEAK_P, PEAK_Q, PEAK_Q_MAX_P = 1, 2, 4
 PEAK_BAD_OBSERVED, PEAK_BAD_POOL = 1, 2
 
@@ -481,6 +485,15 @@ SYMBOLS = {
     "csr_batch_depspan_window_scores": (C.c_int, [C.c_void_p, C.c_int32, I32P, C.c_int32, I32P, C.c_int64, C.c_double, DP, I64P]),
     "csr_batch_depspan_window_acf": (C.c_int, [C.c_void_p, C.c_int32, I32P, C.c_int32, I32P, C.POINTER(DepspanCfg), C.c_int64,
                                                I32P, I64P, C.c_void_p, DP]),
+    "csr_shrink_stage": (C.c_int, [C.c_int32, I64P, DP, DP, C.c_int64]),
+    "csr_batch_shrink_prepare": (C.c_int, [C.c_void_p, C.c_char_p, FP, C.c_int64]),
+    "csr_shrink_initial_sums": (C.c_int, [C.c_void_p, C.c_double, DP]),
+    "csr_shrink_em_step": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, DP, DP, DP]),
+    "csr_shrink_posterior": (C.c_int, [C.c_double, C.c_int32, DP, DP, FP]),
+    "csr_batch_shrink_posterior": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, DP, DP, C.c_int32]),
+    "csr_batch_shrink_download": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, FP]),
+    "csr_batch_shrink_medians": (C.c_int, [C.c_void_p, I64P, DP]),
+    "csr_batch_set_export_signal": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 _lib = None

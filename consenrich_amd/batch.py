@@ -46,6 +46,10 @@ _ARR = {"D": L.ARR_D, "xf": L.ARR_XF, "Pf": L.ARR_PF, "pnoise": L.ARR_PNOISE, "x
         "sumGain0": L.ARR_SUMGAIN0, "sumGain1": L.ARR_SUMGAIN1, "effectiveQLevel": L.ARR_EFFQ_LEVEL,
         "effectiveQTrend": L.ARR_EFFQ_TREND, "muncTrace": L.ARR_MUNCTRACE, "background": L.ARR_BACKGROUND,
         "background_next": L.ARR_BACKGROUND_NEXT}
+# what the writers take besides: the resident shrinkage tracks of a chain (shrink_apply), by these names
+_WRITER_ARR = dict(_ARR, shrunk=L.ARR_SHRINK_BASE + L.SHRINK_TRACKS["shrunk"],
+                   shrunk_posterior_sd=L.ARR_SHRINK_BASE + L.SHRINK_TRACKS["posterior_sd"],
+                   shrunk_spike_prop=L.ARR_SHRINK_BASE + L.SHRINK_TRACKS["spike_prop"])
 
 
 class _NestedBackend:
@@ -407,17 +411,19 @@ class DeviceBatch:
     def bedgraph_bytes(self, chain: int, name: str, chrom: str, start0: int, step: int, end_cap: int = 0, comp: int = 0,
                        transform=None) -> bytes:
         """bedGraph text (consenrich.py:9797-9805 format) of component `comp` of an exported array of one chain,
-        formatted on the device.  transform: None, "round4" (state track) or "sqrt" (uncertainty from a variance)."""
+        formatted on the device.  transform: None, "round4" (state track) or "sqrt" (uncertainty from a variance).  name may also
+        be "shrunk", "shrunk_posterior_sd" or "shrunk_spike_prop": the chain's resident shrinkage track (`shrink_apply`), so
+        that the reference's stateShrunk and stateShrunkUncertainty files are written without a download."""
         t = {None: 0, "none": 0, "round4": 1, "sqrt": 2}[transform]
         cn = str(chrom).encode("ascii")
         f = self._lib.csr_batch_format_bedgraph
-        size = f(self._ctx, chain, _ARR[name], comp, t, cn, int(start0), int(step), int(end_cap), None, 0)
+        size = f(self._ctx, chain, _WRITER_ARR[name], comp, t, cn, int(start0), int(step), int(end_cap), None, 0)
         if size < 0:
             raise L.ConsenrichAMDError(L.last_error())
         if size == 0:
             return b""
         buf = C.create_string_buffer(int(size))
-        if f(self._ctx, chain, _ARR[name], comp, t, cn, int(start0), int(step), int(end_cap), buf, int(size)) != size:
+        if f(self._ctx, chain, _WRITER_ARR[name], comp, t, cn, int(start0), int(step), int(end_cap), buf, int(size)) != size:
             raise L.ConsenrichAMDError(L.last_error() or "bedGraph writer size mismatch")
         return buf.raw
 
@@ -432,7 +438,7 @@ class DeviceBatch:
 
         t = {None: 0, "none": 0, "round4": 1, "sqrt": 2}[transform]
         f = self._lib.csr_batch_bigwig_sections
-        args = (self._ctx, int(chain), _ARR[name], int(comp), t, int(chrom_id), int(start0), int(step), int(end_cap))
+        args = (self._ctx, int(chain), _WRITER_ARR[name], int(comp), t, int(chrom_id), int(start0), int(step), int(end_cap))
         size = f(*args, BW.ITEMS_PER_SECTION, None, 0, None)
         if size < 0:
             raise L.ConsenrichAMDError(L.last_error())
@@ -599,7 +605,7 @@ class DeviceBatch:
         return out
 
     def broadpeak_rows(self, *, intervals=None, ends=None, interval_bp=None, chroms=None, prefix="consenrich", multiplier=2.0,
-                       use_uncertainty=True, min_peak_bp=1000, chains=None):
+                       use_uncertainty=True, min_peak_bp=1000, chains=None, signal="state"):
         """The reference's broadPeak and gappedPeak rows (`_solutionToChromBroadPeakRows`, peaks.py:5606-5818) of the parents
         `broad_parents` left, with the chain's strong mask as child mask: one wavefront per parent makes np.median, the leftmost
         arg-max, np.max and np.mean of the signal, np.max and np.mean of the scores, np.median of the finite uncertainty values
@@ -608,11 +614,14 @@ class DeviceBatch:
         work from compact records (consenrich_amd/broad.py).  A chain with a non-finite signal or score value inside a parent has
         its parent numbers redone with NumPy on its downloaded tracks (`decided_on_host`).  Returns per chain (None where not
         taken) a dict: broad_rows, gapped_rows, peak_meta, export_details, decided_on_host; `broad_stats` holds the counts and
-        seconds of the last `broad_parents` and `broadpeak_rows`."""
+        seconds of the last `broad_parents` and `broadpeak_rows`.  signal: "state" (default) or "shrunk", as in
+        `narrowpeak_rows`; the host fallback uses the same signal."""
         from . import broad as B
 
-        return B.batch_rows(self, intervals=intervals, ends=ends, interval_bp=interval_bp, chroms=chroms, prefix=prefix,
-                            multiplier=multiplier, use_uncertainty=use_uncertainty, min_peak_bp=min_peak_bp, chains=chains)
+        with self._export_signal(signal):
+            return B.batch_rows(self, intervals=intervals, ends=ends, interval_bp=interval_bp, chroms=chroms, prefix=prefix,
+                                multiplier=multiplier, use_uncertainty=use_uncertainty, min_peak_bp=min_peak_bp, chains=chains,
+                                signal=signal)
 
     def rocco_solution(self, chain: int) -> np.ndarray:
         """The uint8 selection mask of one chain."""
@@ -678,7 +687,7 @@ class DeviceBatch:
     def narrowpeak_rows(self, selection_penalties, gammas, *, intervals=None, ends=None, interval_bp=None, chroms=None,
                         prefix="consenrich", min_subpeak_bins=5, trim_score_floor=0.0, multiplier=2.0, use_uncertainty=True,
                         chains=None, split_subpeaks=True, width_policy=None, massive_subpeak_cleanup=True,
-                        split_quantile=0.25, split_z=2.0):
+                        split_quantile=0.25, split_z=2.0, signal="state"):
         """The reference's first-pass narrowPeak rows (`_solutionToChromNarrowPeakRows`, peaks.py:5202-5567, without a width policy
         and without a hierarchy) of every chain's RESIDENT mask, in one device call for all parents of all chains: sub-peaks of
         every run with the min-run dynamic programme (selection penalty = the chain's, boundary cost = 0.25 gamma,
@@ -697,7 +706,42 @@ class DeviceBatch:
         the policy is active and has a threshold; the coordinates travel as a step where `interval_bp` serves every chain,
         otherwise as the children's own edges), and the finishing step runs per SEGMENT -- `csr_batch_export_peaks` again with the
         segments as parents that do not split.  The meta keys and export details of the clean-up are filled as the reference fills
-        them, for an inactive policy too; `narrowpeak_stats` gains the five counters."""
+        them, for an inactive policy too; `narrowpeak_stats` gains the five counters.
+
+        signal: "state" (default: xs[:,0]) or "shrunk" -- the resident shrunk state `shrink_apply` left (float32, stride 1), which
+        is the reference's export signal in a default run; every taken chain then needs one.  The host fallback of a chain with
+        a non-finite signal value downloads and uses the same signal."""
+        with self._export_signal(signal):
+            return self._narrowpeak_rows(selection_penalties, gammas, intervals, ends, interval_bp, chroms, prefix, min_subpeak_bins,
+                                         trim_score_floor, multiplier, use_uncertainty, chains, split_subpeaks, width_policy,
+                                         massive_subpeak_cleanup, split_quantile, split_z, signal)
+
+    def _export_signal(self, signal):
+        """Points the export stages at `signal` for the duration of a with block, and back at the state afterwards."""
+        import contextlib
+
+        if signal not in L.SIGNALS:
+            raise ValueError(f"Unknown export signal: {signal!r}; supported values: state, shrunk")
+
+        @contextlib.contextmanager
+        def scope():
+            L.check(self._lib.csr_batch_set_export_signal(self._ctx, L.SIGNALS[signal]))
+            try:
+                yield
+            finally:
+                L.check(self._lib.csr_batch_set_export_signal(self._ctx, L.SIGNALS["state"]))
+
+        return scope()
+
+    def _signal_track(self, chain: int, signal: str) -> np.ndarray:
+        """The float64 signal of one chain as the export stages read it, downloaded."""
+        if signal == "shrunk":
+            return self.download_shrunk(chain, "shrunk").astype(np.float64)
+        return self.download(chain, "xs")[:, 0].astype(np.float64)
+
+    def _narrowpeak_rows(self, selection_penalties, gammas, intervals, ends, interval_bp, chroms, prefix, min_subpeak_bins,
+                         trim_score_floor, multiplier, use_uncertainty, chains, split_subpeaks, width_policy,
+                         massive_subpeak_cleanup, split_quantile, split_z, signal):
         import time
 
         from . import cleanup as K
@@ -813,7 +857,7 @@ class DeviceBatch:
             mine = peaks[first[a]:first[b]]
             host = bool(np.any(flags[a:b] & L.EXPORT_NONFINITE_SIGNAL))
             if host:
-                state = self.download(c, "xs")[:, 0].astype(np.float64)
+                state = self._signal_track(c, signal)
                 unc = np.sqrt(self.download(c, "Ps")[:, 0, 0]).astype(np.float64) if use_uncertainty else None
                 with np.errstate(invalid="ignore"):
                     P.redo_on_host(mine, state, self.download_scores(c), unc, cfg[c])
@@ -1174,6 +1218,92 @@ class DeviceBatch:
                 out.append(P.score_candidate_regions(observed[c], None, spans[c], scores[c], self.chain_lens[c],
                                                      num_bootstrap=num_bootstrap, scale_bins=pool.scales[c], min_run_bins=min_run_bins,
                                                      dependence_span=int(pool.bws[c]), random_seed=random_seed, pool=pool.chain(c)))
+        return out
+
+    # -- empirical-Bayes shrinkage of the state track (consenrich_amd/shrink.py) ------------------------------------------------
+    def _shrink_prepare(self, chains, variance, block_size):
+        take, mask = self._chain_mask(chains)
+        unc = None
+        if not (isinstance(variance, str) and variance == "fit"):
+            tracks = list(variance)
+            if len(tracks) != len(take):
+                raise ValueError("one uncertainty track (or None) per chain")
+            parts = []
+            for i, t in enumerate(tracks):
+                if not take[i]:
+                    continue
+                a = np.ascontiguousarray(np.asarray(t, dtype=np.float32).ravel())
+                if a.shape != (self.chain_lens[i],):
+                    raise ValueError("an uncertainty track must have shape (chain_len,)")
+                parts.append(a)
+            unc = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, np.float32)
+        L.check_value(self._lib.csr_batch_shrink_prepare(self._ctx, mask, L.fp(unc), int(max(1, int(block_size)))))
+        return take
+
+    def shrink_fit(self, *, chains=None, variance="fit", block_size, model=None, quadrature=None, **fit_arguments):
+        """`fitStateShrinkagePrior` (shrinkState.py:465-970) over the chains `chains` takes (per-chain booleans; None: all -- leave
+        the fold chains of a batch out of a genome-wide prior), from the RESIDENT smoothed fit: the state is float64 of xs[:,0],
+        the variance the float32 square root of Ps00 squared and floored at 1e-12 in float32 (variance="fit": the three float32
+        steps of the reference's CLI), or the same of per-chain float32 uncertainty tracks (an entry per chain; those of chains
+        not taken are not read).  Every pass is two kernels over the resident tracks; the EM control flow is
+        `shrink.fit_state_shrinkage_prior`'s, with its keyword arguments.  Returns the prior.  No array of the fit changes."""
+        from . import shrink as S
+
+        take = self._shrink_prepare(chains, variance, block_size)
+        batch, nc = self, len(self.chain_lens)
+        idx = [i for i in range(nc) if take[i]]
+
+        class _Passes:
+            lengths = tuple(batch.chain_lens[i] for i in idx)
+
+            def initial_sums(self, null_z):
+                rows = S._initial_rows(batch._ctx, nc, null_z)
+                return [S._initial_tuple(rows[i]) for i in idx]
+
+            def em_step(self, pi0, tau, log_prior):
+                tau, lsp = S._vec64(tau), S._vec64(log_prior)
+                rows = S._em_rows(batch._ctx, nc, pi0, tau, lsp)
+                return [S._em_tuple(rows[i], tau.shape[0]) for i in idx]
+
+        return S.fit_state_shrinkage_prior(passes=_Passes(), model=model, blockSize=int(max(1, int(block_size))),
+                                           quadrature=quadrature, **fit_arguments)
+
+    def shrink_apply(self, prior, *, spike_odds_multiplier=2.0, chains=None, variance="fit", want_slab=False):
+        """`applyStateShrinkagePrior` (shrinkState.py:992-1092) to the chains `chains` takes: their shrunk state, posterior sd and
+        spike probability (with want_slab the slab mean and weight too) become resident float32 tracks (`download_shrunk`; the
+        export stages' signal="shrunk"); a chain not taken keeps what it had, or stays without.  variance: as in `shrink_fit`.
+        Returns the reference's metadata per chain (None where not taken); its four medians are order statistics of the resident
+        tracks taken on the device, the two middle values combined as np.median combines float32 values."""
+        from . import shrink as S
+
+        multiplier = S.spike_odds_multiplier_value(spike_odds_multiplier)
+        effective = S.effective_spike_prop(prior, multiplier)
+        tau, weight = S.prior_slabs(prior)
+        if tau.shape[0] > L.SHRINK_MAX_SLABS:
+            raise ValueError(f"slab arrays must hold 1 to {L.SHRINK_MAX_SLABS} slabs")
+        lsp = S.log_slab_prior(effective, weight)
+        take = self._shrink_prepare(chains, variance, prior.blockSize)
+        nc = len(take)
+        L.check_value(self._lib.csr_batch_shrink_posterior(self._ctx, float(effective), int(tau.shape[0]), L.dp(tau), L.dp(lsp),
+                                                           int(bool(want_slab))))
+        count, mid = np.zeros(nc, np.int64), np.full((nc, 4, 2), np.nan, np.float64)
+        L.check(self._lib.csr_batch_shrink_medians(self._ctx, L._i64p(count), L.dp(mid)))
+        out = [None] * nc
+        for i in range(nc):
+            if not take[i]:
+                continue
+            medians = [float(np.mean(mid[i, r].astype(np.float32))) if count[i] > 0 else float("nan") for r in range(4)]
+            out[i] = S.apply_metadata(prior, interval_count=self.chain_lens[i], finite_count=int(count[i]), multiplier=multiplier,
+                                      effective=effective, tau=tau, weight=weight, medians=medians)
+        return out
+
+    def download_shrunk(self, chain: int, name: str = "shrunk") -> np.ndarray:
+        """One chain's resident shrinkage track: "shrunk", "posterior_sd", "spike_prop", "slab_mean", "slab_weight" or "variance"
+        (the float32 variance track the passes read).  A chain without it raises ("chain i has no shrunk track")."""
+        if name not in L.SHRINK_TRACKS:
+            raise ValueError(f"Unknown shrinkage track: {name!r}")
+        out = np.empty(self.chain_lens[chain], np.float32)
+        L.check(self._lib.csr_batch_shrink_download(self._ctx, int(chain), L.SHRINK_TRACKS[name], L.fp(out)))
         return out
 
     def export(self, what: int):

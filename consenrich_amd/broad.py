@@ -486,7 +486,7 @@ def batch_parents(batch, thresholds, selection_penalties, boundary_costs, *, max
 
 
 def batch_rows(batch, *, intervals=None, ends=None, interval_bp=None, chroms=None, prefix="consenrich", multiplier=MULTIPLIER,
-               use_uncertainty=True, min_peak_bp=MIN_PEAK_BP, chains=None):
+               use_uncertainty=True, min_peak_bp=MIN_PEAK_BP, chains=None, signal="state"):
     import time
 
     t_start = time.perf_counter()
@@ -522,7 +522,7 @@ def batch_rows(batch, *, intervals=None, ends=None, interval_bp=None, chroms=Non
         mine = rec[a:b]
         host = bool(np.any(mine["flags"] & NONFINITE))
         if host:
-            state = batch.download(c, "xs")[:, 0].astype(np.float64)
+            state = batch._signal_track(c, signal)
             unc = np.sqrt(batch.download(c, "Ps")[:, 0, 0]).astype(np.float64) if use_uncertainty else None
             with np.errstate(invalid="ignore"):
                 redo_on_host(mine, state, batch.download_scores(c), unc, mult)

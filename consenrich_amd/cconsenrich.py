@@ -32,6 +32,8 @@ __all__ = [
     "csolvePenalizedChainROCCO", "ccalibrateSelectionPenaltyROCCO", "csolveChromROCCOExact",
     "cGenerateDWBMultipliersFromNoise", "cApplyStationaryNullDWB", "cStationaryNullDWBDraw",
     "cEstimateEffectiveSampleSize", "cchooseDependenceSpan",
+    "cstateShrinkInitialSums", "cstateShrinkMixtureEMStep", "cstateShrinkMixtureEMStepPrepared", "cstateShrinkMixturePosterior",
+    "cstateShrinkMixturePosteriorPrepared",
 ]
 
 
@@ -640,3 +642,12 @@ from .ess import cEstimateEffectiveSampleSize  # noqa: E402,F401
 
 # dependence span from the per-chromosome matrices (pyx:3360-4120), implemented in consenrich_amd/depspan.py
 from .depspan import cchooseDependenceSpan  # noqa: E402,F401
+
+# post-fit empirical-Bayes state shrinkage (pyx:9783-10269), implemented in consenrich_amd/shrink.py
+from .shrink import (  # noqa: E402,F401
+    cstateShrinkInitialSums,
+    cstateShrinkMixtureEMStep,
+    cstateShrinkMixtureEMStepPrepared,
+    cstateShrinkMixturePosterior,
+    cstateShrinkMixturePosteriorPrepared,
+)

@@ -351,8 +351,7 @@ extern "C" int csr_batch_broad_rows(csr_ctx *c, const csr_broad_cfg *cfg, const 
         memset(&sig, 0, sizeof(sig));
         memset(&unc, 0, sizeof(unc));
         const int d = c->mdl.state_dim;
-        sig.f = c->nat[CSR_ARR_XS];
-        sig.stride = d;
+        CHECK(batch_export_signal(c, L.taken, sig));
         if (filter) {
             unc.f = c->nat[CSR_ARR_PS];
             unc.stride = (int64_t)d * d;

@@ -212,6 +212,30 @@ extern "C" int csr_export_peaks(int32_t n_chains, const int64_t *chain_len, cons
     return export_run(c, L, sig, unc, cfg, jobs, parent_flags, count);
 }
 
+// Which resident track the batch's export stages (narrowPeak, clean-up's second pass, broad rows) read as signal: the state
+// (double) xs[:,0] of the reference-layout fit (the default), or the shrunk state csr_batch_shrink_posterior left (float32, one
+// value per bin).  Belongs to the batch (csr_batch_configure puts it back to the state).
+extern "C" int csr_batch_set_export_signal(csr_ctx *c, int32_t signal) {
+    CHECK(need(c));
+    if (signal != CSR_SIGNAL_STATE && signal != CSR_SIGNAL_SHRUNK) return fail("bad export signal %d", signal);
+    c->exportSignal = signal;
+    return 0;
+}
+// sig := that track; a taken chain without a shrunk track fails before any launch
+template <class V>
+static int batch_export_signal(csr_ctx *c, const V &taken, ExportTrack &sig) {
+    if (c->exportSignal == CSR_SIGNAL_SHRUNK) {
+        for (size_t i = 0; i < taken.size(); ++i)
+            if (taken[i] && !c->shrunk.has((int)i)) return fail("chain %d has no %s", (int)i, c->shrunk.what);
+        sig.f = c->shrunk.d;
+        sig.stride = 1;
+    } else {
+        sig.f = c->nat[CSR_ARR_XS];
+        sig.stride = c->mdl.state_dim;
+    }
+    return 0;
+}
+
 // batch context: the resident score tracks and the reference-layout copies of the smoothed fit are read; nothing resident changes
 extern "C" int csr_batch_export_peaks(csr_ctx *c, const csr_export_cfg *cfg, const unsigned char *chain_mask, int64_t n_parents,
                                       const csr_export_parent *parents, int32_t *parent_flags, int64_t *count) {
@@ -235,8 +259,7 @@ extern "C" int csr_batch_export_peaks(csr_ctx *c, const csr_export_cfg *cfg, con
     memset(&sig, 0, sizeof(sig));
     memset(&unc, 0, sizeof(unc));
     const int d = c->mdl.state_dim;
-    sig.f = c->nat[CSR_ARR_XS];
-    sig.stride = d;
+    CHECK(batch_export_signal(c, L.taken, sig));
     bool filter = false;
     for (size_t i = 0; i < L.len.size(); ++i) filter = filter || (L.taken[i] && cfg[i].filter);
     if (filter) {

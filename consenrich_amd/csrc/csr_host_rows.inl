@@ -607,21 +607,39 @@ extern "C" int64_t csr_format_bedgraph(const char *chrom, int64_t n, const int64
     return bedgraph_impl(c, a, starts, ends, values, chrom, out, out_capacity);
 }
 
+// What a writer of the batch reads of one chain (the chain index is checked): component `comp` of an exported array, or -- array_id
+// CSR_ARR_SHRINK_BASE + CSR_SHRINK_* -- a resident track of the state shrinkage (one float per bin; the chain must hold it)
+static int writer_values(csr_ctx *c, int32_t chain, int32_t array_id, int32_t comp, const float **values, int *stride) {
+    const ChainInfo &ci = c->chains[chain];
+    if (array_id >= CSR_ARR_SHRINK_BASE && array_id <= CSR_ARR_SHRINK_BASE + CSR_SHRINK_VARIANCE) {
+        const ChainTrack<float> &t = shrink_track(c, array_id - CSR_ARR_SHRINK_BASE);
+        if (!t.has(chain)) return fail("chain %d has no %s", chain, t.what);
+        if (comp != 0) return fail("component out of range");
+        *values = t.at(c, chain);
+        *stride = 1;
+        return 0;
+    }
+    if (array_id < 0 || array_id >= CSR_ARR_COUNT || array_id == CSR_ARR_RESID) return fail("bad array id");
+    if (!c->nat[array_id]) return fail("array %d was not exported", array_id);
+    const int64_t per = arr_comps(c, array_id);
+    if (comp < 0 || comp >= per) return fail("component out of range");
+    *values = c->nat[array_id] + ci.off * per;
+    *stride = (int)per;
+    return 0;
+}
+
 extern "C" int64_t csr_batch_format_bedgraph(csr_ctx *c, int32_t chain, int32_t array_id, int32_t comp,
                                              int32_t transform, const char *chrom, int64_t start0, int64_t step,
                                              int64_t end_cap, char *out, int64_t out_capacity) {
     if (need(c) != 0 || settle(c) != 0) return -1;
     if (chain < 0 || chain >= (int)c->chains.size()) { fail("chain index out of range"); return -1; }
-    if (array_id < 0 || array_id >= CSR_ARR_COUNT || array_id == CSR_ARR_RESID) { fail("bad array id"); return -1; }
-    if (!c->nat[array_id]) { fail("array %d was not exported", array_id); return -1; }
-    const int64_t per = arr_comps(c, array_id);
-    if (comp < 0 || comp >= per) { fail("component out of range"); return -1; }
-    if (transform < 0 || transform > 2) { fail("bad transform"); return -1; }
-    const ChainInfo &ci = c->chains[chain];
     BgwArgs a;
     memset(&a, 0, sizeof(a));
+    if (writer_values(c, chain, array_id, comp, &a.values, &a.stride) != 0) return -1;
+    if (transform < 0 || transform > 2) { fail("bad transform"); return -1; }
+    const ChainInfo &ci = c->chains[chain];
     a.n = ci.n; a.transform = transform; a.start0 = start0; a.step = step; a.endCap = end_cap;
-    a.values = c->nat[array_id] + ci.off * per; a.stride = (int)per; a.comp = comp;
+    a.comp = comp;
     return bedgraph_impl(c, a, nullptr, nullptr, nullptr, chrom, out, out_capacity);
 }
 
@@ -631,10 +649,9 @@ extern "C" int64_t csr_batch_format_bedgraph(csr_ctx *c, int32_t chain, int32_t 
 static int bw_args(csr_ctx *c, int32_t chain, int32_t array_id, int32_t comp, int32_t transform, int64_t start0, int64_t step,
                    int64_t end_cap, BwArgs &a) {
     if (chain < 0 || chain >= (int)c->chains.size()) return fail("chain index out of range");
-    if (array_id < 0 || array_id >= CSR_ARR_COUNT || array_id == CSR_ARR_RESID) return fail("bad array id");
-    if (!c->nat[array_id]) return fail("array %d was not exported", array_id);
-    const int64_t per = arr_comps(c, array_id);
-    if (comp < 0 || comp >= per) return fail("component out of range");
+    const float *values = nullptr;
+    int stride = 1;
+    CHECK(writer_values(c, chain, array_id, comp, &values, &stride));
     if (transform < 0 || transform > 2) return fail("bad transform");
     if (step <= 0 || start0 < 0) return fail("bigWig intervals need start0 >= 0 and step > 0");
     const ChainInfo &ci = c->chains[chain];
@@ -643,7 +660,7 @@ static int bw_args(csr_ctx *c, int32_t chain, int32_t array_id, int32_t comp, in
     if (end_cap > 0 && end_cap <= start0 + (ci.n - 1) * step) return fail("end_cap leaves an empty last interval");
     memset(&a, 0, sizeof(a));
     a.g.n = ci.n; a.g.transform = transform; a.g.start0 = start0; a.g.step = step; a.g.endCap = end_cap;
-    a.g.values = c->nat[array_id] + ci.off * per; a.g.stride = (int)per; a.g.comp = comp;
+    a.g.values = values; a.g.stride = stride; a.g.comp = comp;
     return 0;
 }
 

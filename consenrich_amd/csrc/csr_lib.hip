@@ -21,6 +21,7 @@
 #include "csr_cleanup.h"
 #include "csr_broad.h"
 #include "csr_depspan.h"
+#include "csr_shrink.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
 
@@ -353,6 +354,12 @@ struct BatchState {
     ChainTrack<unsigned char> sol{"ROCCO solution"};
     // broad mode (csr_host_broad.inl): the weak pass's mask and the mask of the bridged parents
     ChainTrack<unsigned char> weak{"weak ROCCO solution"}, broadParent{"broad parent mask"};
+    // empirical-Bayes state shrinkage (csr_host_shrink.inl): the float32 variance track csr_batch_shrink_prepare makes and the
+    // posterior tracks csr_batch_shrink_posterior leaves
+    ChainTrack<float> shrinkVar{"shrinkage variance track"}, shrunk{"shrunk track"}, shrunkSd{"shrunk posterior sd track"},
+        shrunkSpike{"shrunk spike probability track"}, shrunkSlabMean{"shrunk slab mean track"},
+        shrunkSlabWeight{"shrunk slab weight track"};
+    int exportSignal = 0;       // CSR_SIGNAL_*: what the export stages read as signal (csr_batch_set_export_signal)
     // ROCCO's work arrays without presence (csr_host_rocco.inl): backtrace words, per-chain maxima and flags; its growable work
     // space is csr_ctx::roccoWs
     struct Rocco {
@@ -522,6 +529,18 @@ struct csr_ctx : BatchState {
     struct DepWs {
         DevBuf stageBuf, matBuf, winBuf, rowBuf, pairTab, diffBuf, compBuf, cenBuf, nfinBuf, sumBuf, pairBuf, lagBuf, medBuf, recBuf;
     } depWs;
+    // empirical-Bayes state shrinkage (csr_host_shrink.inl): the prepared input -- staged host arrays (default context) or the chains
+    // of the batch a mask took (fromBatch: it dies with the batch) -- with its chain table and per-block valid counts, and the work
+    // space of a pass: tile partials, folded sums, the parameter set, posterior tracks of host arrays, median keys
+    struct ShrinkWs {
+        bool ready = false, fromBatch = false;
+        std::vector<ShrinkChain> chains;
+        std::vector<int> idx;               // where chain k's sums go in the caller's output
+        ShrinkTrack tr{};
+        int64_t block = 1, total = 0, longest = 0, nTiles = 0, nBlocks = 0;
+        size_t nOut = 0;
+        DevBuf xBuf, vBuf, chainBuf, cntBuf, partBuf, outBuf, priorBuf, postBuf, keyBuf;
+    } shrinkWs;
     // DWB peak scoring (csr_host_peakscore.inl): growable work space of a call -- an uploaded host track, the segments, views and
     // results of a scoring call, the observed and pooled statistics with their p / q values (sorted through nullWs)
     struct PeakWs {
@@ -556,6 +575,7 @@ struct csr_ctx : BatchState {
 static int settle(csr_ctx *c);
 static void peak_pool_release(csr_ctx *c);      // csr_host_peakscore.inl
 static int export_impl(csr_ctx *c, uint32_t what);
+static ChainTrack<float> &shrink_track(csr_ctx *c, int which);     // csr_host_shrink.inl
 
 // The pass that just ran wrote these arrays in the given copies (and not in the other)
 enum : unsigned { W_BLOCKED = 1u, W_NAT = 2u };
@@ -679,6 +699,7 @@ static void free_batch(csr_ctx *c) {
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (void *q : c->allocs) (void)hipFree(q);
     static_cast<BatchState &>(*c) = BatchState{};
+    if (c->shrinkWs.fromBatch) c->shrinkWs.ready = false;       // (its tracks were the batch's)
 }
 
 // Warm-up windows that gave zero re-runs on the bench workload with margin (hg38 x 32 synthetic: the state chain needs
@@ -945,3 +966,4 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_cleanup.inl"
 #include "csr_host_broad.inl"
 #include "csr_host_depspan.inl"
+#include "csr_host_shrink.inl"

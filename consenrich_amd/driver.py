@@ -689,7 +689,7 @@ def nested_peaks_batch(batch: DeviceBatch, first_pass, *, interval_bp, intervals
 
 
 def export_peaks_batch(batch: DeviceBatch, nested, *, interval_bp, intervals=None, ends=None, chroms=None, prefix="consenrich",
-                       multiplier: float = 2.0, use_uncertainty: bool = True) -> List[dict]:
+                       multiplier: float = 2.0, use_uncertainty: bool = True, signal: str = "state") -> List[dict]:
     """The link between `nested_peaks_batch` and `score_peaks_batch`: what the reference exports and then scores is not the refined
     mask's runs but what `_solutionToChromNarrowPeakRows` makes of them (`solveRocco`, peaks.py:6987-7006): runs broken at coordinate
     gaps, split into sub-peaks, trimmed around their summits, filtered by the median test and the 200 bp minimum.  On the device
@@ -697,13 +697,14 @@ def export_peaks_batch(batch: DeviceBatch, nested, *, interval_bp, intervals=Non
     subpeakSelectionPenalty = the chain's selection_penalty, subpeakBoundaryCost = 0.25 gamma, minSubpeakBins 5, trimScoreFloor 0.
     nested: what nested_peaks_batch (or first_pass_peaks_batch) returned.  intervals / ends: per chain the bins' coordinates (None:
     bins of interval_bp starting at 0).  Returns a copy of every record with `rows`, `peak_meta`, `export_details`,
-    `decided_on_host`, and `starts` / `ends` = the KEPT peaks' start_idx / end_idx -- accepted by `score_peaks_batch` unchanged."""
+    `decided_on_host`, and `starts` / `ends` = the KEPT peaks' start_idx / end_idx -- accepted by `score_peaks_batch` unchanged.
+    signal: "state", or "shrunk" after `shrink_state_batch` (the reference's export signal in a default run)."""
     nc = len(batch.chain_lens)
     if len(nested) != nc:
         raise ValueError("one record per chain")
     got = batch.narrowpeak_rows([r["selection_penalty"] for r in nested], [r["gamma"] for r in nested], intervals=intervals, ends=ends,
                                 interval_bp=interval_bp, chroms=chroms, prefix=prefix, min_subpeak_bins=5, trim_score_floor=0.0,
-                                multiplier=multiplier, use_uncertainty=use_uncertainty)
+                                multiplier=multiplier, use_uncertainty=use_uncertainty, signal=signal)
     out = []
     for r, g in zip(nested, got):
         q = dict(r)
@@ -715,13 +716,14 @@ def export_peaks_batch(batch: DeviceBatch, nested, *, interval_bp, intervals=Non
 
 
 def cleanup_peaks_batch(batch: DeviceBatch, exported, *, interval_bp, intervals=None, ends=None, chroms=None, prefix="consenrichROCCO",
-                        multiplier: float = 2.0, use_uncertainty: bool = True, enabled: bool = True):
+                        multiplier: float = 2.0, use_uncertainty: bool = True, enabled: bool = True, signal: str = "state"):
     """The link between `export_peaks_batch` and `score_peaks_batch`: `solveRocco`'s massive sub-peak clean-up (peaks.py:7008-7096).
     The width policy is learned on the host from the kept widths of ALL chains (`meta["end"] - meta["start"]`) with the reference's
     constants.  If it is not active, the records come back with `export_details["massive_subpeak_width_policy"]` set and nothing
     else changed.  If it is active, every chain is exported once more under the policy, from resident data in one more round of
     device calls (`DeviceBatch.narrowpeak_rows(width_policy=...)`), and `rows`, `peak_meta`, `export_details`, `starts` / `ends`
-    become those of the cleaned peak set.  exported: what export_peaks_batch returned.  Returns (records, policy)."""
+    become those of the cleaned peak set.  exported: what export_peaks_batch returned; signal: the one it was given.  Returns
+    (records, policy)."""
     from . import cleanup as K
 
     nc = len(batch.chain_lens)
@@ -741,7 +743,7 @@ def cleanup_peaks_batch(batch: DeviceBatch, exported, *, interval_bp, intervals=
     got = batch.narrowpeak_rows([r["selection_penalty"] for r in exported], [r["gamma"] for r in exported], intervals=intervals, ends=ends,
                                 interval_bp=interval_bp, chroms=chroms, prefix=prefix, min_subpeak_bins=5, trim_score_floor=0.0,
                                 multiplier=multiplier, use_uncertainty=use_uncertainty, width_policy=policy, massive_subpeak_cleanup=True,
-                                split_quantile=K.SPLIT_QUANTILE, split_z=K.SPLIT_Z)
+                                split_quantile=K.SPLIT_QUANTILE, split_z=K.SPLIT_Z, signal=signal)
     for r, g in zip(exported, got):
         q = dict(r)
         q.update(rows=g["rows"], peak_meta=g["peak_meta"], export_details=g["export_details"], decided_on_host=g["decided_on_host"])
@@ -772,7 +774,7 @@ def validate_broad_max_gap_bp(value):
 def broad_peaks_batch(batch: DeviceBatch, nested, *, dependence_spans, threshold_z, threshold_z_grid, num_bootstrap, random_seed,
                       weak_threshold_z: float = 1.2816, max_gap_bp=None, selection_penalty=None, interval_bp=None, intervals=None,
                       ends=None, chroms=None, prefix="consenrichROCCO", blacklist=None, multiplier: float = 2.0,
-                      use_uncertainty: bool = True, min_peak_bp: int = 1000, pooled_floors=None) -> List[dict]:
+                      use_uncertainty: bool = True, min_peak_bp: int = 1000, pooled_floors=None, signal: str = "state") -> List[dict]:
     """The link between `nested_peaks_batch` and `score_peaks_batch` in broad mode (`solveRocco` with peakMode="broad":
     peaks.py:6743-6778, 6874-6960 and `_solutionToChromBroadPeakRows`), without a track leaving the device.  The weak pass has the
     strong pass's score track, null and template; its budget is `dwb_panel` and `rocco_budget` once more at weak_threshold_z (the
@@ -784,7 +786,8 @@ def broad_peaks_batch(batch: DeviceBatch, nested, *, dependence_spans, threshold
     export_details, broad_parent (the reference's broadParentDetails with its keys -- `weak_solve_details` holds what `rocco`
     returns -- plus three of its own: envelope_fallback, and parent_starts / parent_ends, the merged runs), decided_on_host
     (how many of the two host decisions the chain took: the fallback window, a non-finite value inside a parent), and `starts` /
-    `ends` = the KEPT parents' start_idx / end_idx -- accepted by `score_peaks_batch` unchanged."""
+    `ends` = the KEPT parents' start_idx / end_idx -- accepted by `score_peaks_batch` unchanged.  signal: what `broadpeak_rows`
+    reads as signal ("state", or "shrunk" after `shrink_state_batch`)."""
     from . import ess as E
     from . import rocco as R
 
@@ -830,7 +833,7 @@ def broad_peaks_batch(batch: DeviceBatch, nested, *, dependence_spans, threshold
                                   intervals=intervals, ends=ends, chroms=chroms, blacklist=blacklist, dip_penalty_fraction=0.5,
                                   run_penalty=0.0)
     rows = batch.broadpeak_rows(intervals=intervals, ends=ends, chroms=chroms, prefix=prefix, multiplier=multiplier,
-                                use_uncertainty=use_uncertainty, min_peak_bp=min_peak_bp)
+                                use_uncertainty=use_uncertainty, min_peak_bp=min_peak_bp, signal=signal)
     out = []
     for ch, (r, p, g) in enumerate(zip(nested, parents, rows)):
         q = dict(r)
@@ -868,3 +871,18 @@ def score_peaks_batch(batch: DeviceBatch, first_pass, panel, *, dependence_spans
     peaks = [(r["starts"], r["ends"]) for r in first_pass]
     return batch.dwb_peak_scoring(panel, bandwidths=spans, peaks=peaks, num_replay=min(int(num_replay), 64), random_seed=random_seed,
                                   min_run_bins=min_run_bins, draws_per_group=draws_per_group)
+
+
+def shrink_state_batch(batch: DeviceBatch, *, block_size, chains=None, variance="fit", model=None, spike_odds_multiplier: float = 2.0,
+                       want_slab: bool = False, **fit_arguments):
+    """The reference's default-on state shrinkage (`fitStateShrinkagePrior` over all chromosomes, then `applyStateShrinkagePrior`
+    per chromosome; consenrich.py:9977-10086) from the resident fit.  Where it sits: AFTER `run_consenrich_batch` (it reads the
+    smoothed fit and changes none of its arrays) and BEFORE the export stages, which then take `signal="shrunk"`
+    (`export_peaks_batch`, `cleanup_peaks_batch`, `broad_peaks_batch`) -- the score tracks and masks do not depend on it.
+    block_size: `diagnostics.resolveUncertaintyBlockSizeIntervals(...)` of the run.  chains: per-chain booleans -- fold chains of
+    a batch must not enter a genome-wide prior, so leave them out; they get no shrunk track.  variance: "fit", or per-chain float32
+    uncertainty tracks (the calibrated ones).  fit_arguments: those of `shrink.fit_state_shrinkage_prior` (studentTQuadratureOrder
+    is 16 in the reference's CLI, 12 in its function).  Returns (prior, per-chain apply metadata)."""
+    prior = batch.shrink_fit(chains=chains, variance=variance, block_size=block_size, model=model, **fit_arguments)
+    return prior, batch.shrink_apply(prior, spike_odds_multiplier=spike_odds_multiplier, chains=chains, variance=variance,
+                                     want_slab=want_slab)

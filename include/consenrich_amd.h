@@ -1089,6 +1089,53 @@ int csr_batch_depspan_window_acf(csr_ctx *ctx, int32_t n_listed, const int32_t *
                                  const csr_depspan_cfg *cfg, int64_t n_windows, const int32_t *win_chain, const int64_t *win_start,
                                  csr_depspan_window *rec, double *pooled);
 
+/* ---- post-fit empirical-Bayes state shrinkage ------------------------------------------------------------ */
+/* The per-bin passes of the reference's spike-and-slab state shrinkage (pyx:9791-10269 `cstateShrinkInitialSums`,
+ * `cstateShrinkMixtureEMStepPrepared`, `cstateShrinkMixturePosteriorPrepared`).  The EM control flow around them is scalar work
+ * of the caller (consenrich_amd/shrink.py); a call here evaluates one pass for one parameter set.
+ *
+ * An input is prepared once per (input, block size): csr_shrink_stage takes host arrays (float64 state and variance, the chunks
+ * one after the other, n_chunks lengths) into the default context; csr_batch_shrink_prepare takes the chains chain_mask selects
+ * (NULL: all) of a resident smoothed fit -- the state is (double) xs[:,0] of the reference-layout copy (the conversion and the
+ * side-effect rule of csr_batch_rocco_scores: no array of the fit changes), the float32 variance track is made on the device from
+ * (float) sqrt(Ps00) squared and floored at 1e-12 in float32, or the same way from `uncertainty`: the float32 uncertainty tracks
+ * of the taken chains one after the other.  Blocks of `block` bins restart at every chunk / chain.
+ *
+ * The sum passes (ctx NULL: the staged host arrays) return one record per chunk / chain, which the caller adds in order as the
+ * reference adds its chunks; records of chains the prepared input does not hold stay untouched.
+ *   initial sums   out[chain][5]: totalWeight, centralWeight, excessMomentSum, varianceSum, finiteCount;
+ *   EM step        out[chain][4 + 2 K]: totalWeight, nullMass, logLikelihood, finiteCount, slabMass[K], slabSecond[K];
+ * finiteCount is an exact integer.  The sums are float64 trees of a fixed shape (csr_shrink.h): two identical calls return
+ * identical bits; against the reference's sequential sums they agree to rounding, not bit for bit.
+ * The posterior pass writes five float32 tracks: for the staged host arrays into out[5][total bins] (shrunk, posterior sd, spike
+ * probability, slab mean, slab weight); for a batch into resident per-chain tracks (the two slab tracks with want_slab), which
+ * csr_batch_shrink_download hands out (which: CSR_SHRINK_*; a chain without the track: "chain i has no shrunk track").
+ * csr_batch_shrink_medians: count[chain] = the valid bins, mid[chain][4][2] = the lower and upper middle value over the valid
+ * bins of |state|, |shrunk|, spike probability and posterior sd (equal for an odd count, untouched for none).
+ * Checked before any launch: K in 1..96, finite positive tau (CSR_ERR_VALUE with the reference's text), 0 < pi0 < 1 (the same),
+ * block >= 1.  Additive to ABI 6. */
+enum { CSR_SHRINK_SHRUNK = 0, CSR_SHRINK_POSTERIOR_SD = 1, CSR_SHRINK_SPIKE_PROP = 2, CSR_SHRINK_SLAB_MEAN = 3,
+       CSR_SHRINK_SLAB_WEIGHT = 4, CSR_SHRINK_VARIANCE = 5 };
+#define CSR_SHRINK_MAX_SLABS 96
+/* csr_batch_format_bedgraph, csr_batch_bigwig_sections and csr_batch_bigwig_zoom take CSR_ARR_SHRINK_BASE + CSR_SHRINK_* as
+ * array_id (component 0): the chain's resident shrinkage track, written without a download. */
+#define CSR_ARR_SHRINK_BASE 64
+int csr_shrink_stage(int32_t n_chunks, const int64_t *lens, const double *state, const double *variance, int64_t block);
+int csr_batch_shrink_prepare(csr_ctx *ctx, const unsigned char *chain_mask, const float *uncertainty, int64_t block);
+int csr_shrink_initial_sums(csr_ctx *ctx, double null_z, double *out);
+int csr_shrink_em_step(csr_ctx *ctx, double pi0, int32_t n_slabs, const double *tau, const double *log_slab_prior, double *out);
+int csr_shrink_posterior(double pi0, int32_t n_slabs, const double *tau, const double *log_slab_prior, float *out);
+int csr_batch_shrink_posterior(csr_ctx *ctx, double pi0, int32_t n_slabs, const double *tau, const double *log_slab_prior,
+                               int32_t want_slab);
+int csr_batch_shrink_download(csr_ctx *ctx, int32_t chain, int32_t which, float *host_dst);
+int csr_batch_shrink_medians(csr_ctx *ctx, int64_t *count, double *mid);
+/* Which resident track csr_batch_export_peaks and csr_batch_broad_rows read as signal from now on: CSR_SIGNAL_STATE, the
+ * (double) xs[:,0] of the smoothed fit (the default; csr_batch_configure puts it back), or CSR_SIGNAL_SHRUNK, the shrunk state
+ * track (float32 -- it carries a NaN / Inf of the state through).  With the shrunk signal a taken chain without the track fails
+ * with "chain i has no shrunk track" before any launch.  Scores, masks and uncertainty are read as before. */
+enum { CSR_SIGNAL_STATE = 0, CSR_SIGNAL_SHRUNK = 1 };
+int csr_batch_set_export_signal(csr_ctx *ctx, int32_t signal);
+
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
     int64_t fix_launches;       /* validation/fix-up kernel launches so far */
