@@ -24,7 +24,7 @@ USE_LAMBDA, USE_KAPPA, USE_QSCALE, USE_APN, RETURN_NLL, NLL_IN_D = (1 << i for i
  ARR_SUMGAIN0, ARR_SUMGAIN1, ARR_EFFQ_LEVEL, ARR_EFFQ_TREND, ARR_MUNCTRACE, ARR_BACKGROUND, ARR_BACKGROUND_NEXT,
  ARR_COUNT) = range(19)
 BG_OK, BG_NO_SUPPORT, BG_BAD_PIVOT, BG_UNRELIABLE, BG_NONFINITE = range(5)
-BG_INIT_FROM_CURRENT, BG_ZERO_STATE = 1, 2
+BG_INIT_FROM_CURRENT, BG_ZERO_STATE, BG_SEED_WEIGHTS = 1, 2, 4
 EXPORT_FORWARD, EXPORT_SMOOTH, EXPORT_RESID, EXPORT_MULT = 1, 2, 4, 8
 
 
@@ -162,6 +162,16 @@ class NullOut(C.Structure):
                 ("center_method", C.c_int32), ("null_method", C.c_int32), ("host_fallback", C.c_int32)]
 
 
+class MuncSeedCfg(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("pad", "student_t_df", "d_omega", "omega_min", "omega_max", "variance_floor",
+                                          "variance_cap")] + \
+               [(k, C.c_int32) for k in ("use_weights", "student_t", "update_weights", "reserved_")]
+
+
+class MuncSeedStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("passes", "rolls", "roll_rows", "roll_fallback_rows", "last_roll_fallback_rows")]
+
+
 class EssOut(C.Structure):
     _fields_ = [("n_eff", C.c_double), ("tau", C.c_double), ("lags_used", C.c_int64)]
 
@@ -173,6 +183,15 @@ ROCCO_ERR_VALUE = DWB_ERR_VALUE = SEG_ERR_VALUE = NULL_ERR_VALUE = ESS_ERR_VALUE
 ESS_OCCUPANCY, ESS_SOFT, ESS_INTEGRATED = 1, 2, 3
 SHRINK_TRACKS = {"shrunk": 0, "posterior_sd": 1, "spike_prop": 2, "slab_mean": 3, "slab_weight": 4, "variance": 5}
 SHRINK_MAX_SLABS = 96
+# the resident arrays of the dense observation-variance seed loop (CSR_MUNC_SEED_*): name -> (id, per cell?, dtype)
+MUNC_SEED_ARRAYS = {"seed_total": (0, True, "float32"), "seed_local": (1, True, "float32"), "seed_rho": (2, True, "float32"),
+                    "seed_omega": (3, False, "float32"), "seed_g": (4, False, "float32"), "seed_gvar": (5, False, "float32"),
+                    "seed_weight": (6, True, "float32"), "seed_count_floor": (7, True, "float32"),
+                    "seed_exclude": (8, False, "uint8"), "seed_smooth": (9, True, "float32"),
+                    "seed_total_next": (10, True, "float32"), "seed_rho_next": (11, True, "float32"),
+                    "seed_omega_next": (12, False, "float32")}
+MUNC_ROLL_BLOCK = 128        # csr_munc.h: intervals per speculative block of the rolling mean
+MUNC_REG_TRACKS = 16         # ... and up to how many tracks the seed pass keeps its float32 pair in registers
 ARR_SHRINK_BASE = 64         # writers: ARR_SHRINK_BASE + SHRINK_TRACKS[name] as array id
 SIGNALS = {"state": 0, "shrunk": 1}
 PEAK_P, PEAK_Q, PEAK_Q_MAX_P = 1, 2, 4
@@ -494,6 +513,19 @@ SYMBOLS = {
     "csr_batch_shrink_download": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, FP]),
     "csr_batch_shrink_medians": (C.c_int, [C.c_void_p, I64P, DP]),
     "csr_batch_set_export_signal": (C.c_int, [C.c_void_p, C.c_int32]),
+    "csr_munc_seed_pass": (C.c_int, [C.c_int64, C.c_int64, FP, FP, FP, FP, FP, FP, FP, FP, FP, C.POINTER(C.c_uint8), C.c_int32,
+                                     C.POINTER(MuncSeedCfg), FP, FP, FP, FP, FP, FP]),
+    "csr_munc_smooth_local": (C.c_int, [C.c_int64, C.c_int64, FP, C.c_int64, C.POINTER(C.c_uint8), C.c_int32, C.c_double, FP, I64P]),
+    "csr_batch_munc_seed_begin": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32]),
+    "csr_batch_munc_seed_upload": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "csr_batch_munc_seed_download": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "csr_batch_munc_seed_working": (C.c_int, [C.c_void_p, C.c_double, C.c_int32]),
+    "csr_batch_munc_seed_pass": (C.c_int, [C.c_void_p, C.POINTER(MuncSeedCfg)]),
+    "csr_batch_munc_seed_swap": (C.c_int, [C.c_void_p, C.c_int32]),
+    "csr_batch_munc_seed_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32]),
+    "csr_batch_munc_seed_stats": (C.c_int, [C.c_void_p, C.POINTER(MuncSeedStats)]),
+    "csr_batch_munc_seed_background": (C.c_int, [C.c_void_p, C.POINTER(BgCfg), C.c_double, C.c_int32, C.c_int32, C.POINTER(BgOut)]),
+    "csr_batch_munc_seed_background_tracks": (C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP]),
 }
 
 _lib = None

@@ -386,16 +386,22 @@ class DeviceBatch:
         L.check(self._lib.csr_batch_background_update(self._ctx, C.byref(cfg), outs))
         res = [{k: getattr(o, k) for k, _ in L.BgOut._fields_} for o in outs]
         if raise_on_error:
-            for c, o in enumerate(res):
-                if o["status"] == L.BG_BAD_PIVOT:
-                    raise RuntimeError("roughness-penalized LDL factorization required pivot modification at index "
-                                       f"{o['bad_index']} (pivot={o['bad_value']:.6g}, floor={1.0e-12:.6g}). [chain {c}]")
-                if o["status"] == L.BG_UNRELIABLE:
-                    raise RuntimeError("roughness-penalized LDL system exceeds float64 reliability: "
-                                       f"roundoffIndex={o['roundoff_index']:.6g} threshold=1 [chain {c}]")
-                if o["status"] == L.BG_NONFINITE:
-                    raise RuntimeError(f"solver returned non-finite values [chain {c}]")
+            self._raise_background_errors(res)
         return res
+
+    @staticmethod
+    def _raise_background_errors(res, take=None):
+        for c, o in enumerate(res):
+            if take is not None and not take[c]:
+                continue
+            if o["status"] == L.BG_BAD_PIVOT:
+                raise RuntimeError("roughness-penalized LDL factorization required pivot modification at index "
+                                   f"{o['bad_index']} (pivot={o['bad_value']:.6g}, floor={1.0e-12:.6g}). [chain {c}]")
+            if o["status"] == L.BG_UNRELIABLE:
+                raise RuntimeError("roughness-penalized LDL system exceeds float64 reliability: "
+                                   f"roundoffIndex={o['roundoff_index']:.6g} threshold=1 [chain {c}]")
+            if o["status"] == L.BG_NONFINITE:
+                raise RuntimeError(f"solver returned non-finite values [chain {c}]")
 
     def background_apply(self, take=None):
         """current background := last proposal (for the chains with take[c] true; default all)."""
@@ -1305,6 +1311,150 @@ class DeviceBatch:
         out = np.empty(self.chain_lens[chain], np.float32)
         L.check(self._lib.csr_batch_shrink_download(self._ctx, int(chain), L.SHRINK_TRACKS[name], L.fp(out)))
         return out
+
+    # -- dense observation-variance seed loop (consenrich_amd/munc.py, csrc/csr_munc.h) -------------------------------------------
+    def _seed_put(self, chain: int, name: str, arr):
+        ident, per_cell, dtype = L.MUNC_SEED_ARRAYS[name]
+        n = self.chain_lens[chain]
+        arr = np.ascontiguousarray(arr, dtype=dtype)
+        if arr.shape != ((self.m, n) if per_cell else (n,)):
+            raise ValueError(f"{name}: expected shape {(self.m, n) if per_cell else (n,)}, got {arr.shape}")
+        L.check(self._lib.csr_batch_munc_seed_upload(self._ctx, int(chain), ident, arr.ctypes.data_as(C.c_void_p)))
+
+    def munc_seed_begin(self, seed_munc=None, count_floor=None, exclude=None, chains=None):
+        """Opens the seed loop of consenrich.py:7784-7945 on the chains `chains` takes (per-chain booleans; None: all): its arrays
+        stay on the device until the batch is configured again.  total starts from the batch's resident munc, or from
+        seed_munc[chain] ((m, n) each; a dict or a list with one entry per chain, None entries keep the resident munc); omega and
+        rho are 1, the seed background g and its variance G are 0.  count_floor[chain]: (m, n) count-model variance floors, NaN
+        meaning none (consenrich.py:7354-7359, with the reference's two RuntimeErrors); exclude[chain]: (n,) bytes, nonzero =
+        excluded from the rolling mean of `munc_seed_finish`."""
+        nc = len(self.chain_lens)
+        take = [True] * nc if chains is None else [bool(t) for t in chains]
+        if len(take) != nc:
+            raise ValueError("one entry per chain")
+
+        def entries(x):
+            if x is None:
+                return {}
+            items = x.items() if isinstance(x, dict) else enumerate(x)
+            return {int(i): v for i, v in items if v is not None and take[int(i)]}
+
+        seed_munc, count_floor, exclude = entries(seed_munc), entries(count_floor), entries(exclude)
+        floors = {}
+        for i, f in count_floor.items():
+            work = np.asarray(f, dtype=np.float32).copy()
+            if work.shape != (self.m, self.chain_lens[i]):
+                raise RuntimeError("count-model floor matrix must align with MUNC evidence")
+            finite = np.isfinite(work)
+            if np.any(finite & (work < 0.0)):
+                raise RuntimeError("count-model floor must be nonnegative")
+            if np.any((~finite) & (~np.isnan(work))):
+                raise RuntimeError("count-model floor must be finite or NaN")
+            work[~finite] = 0.0
+            floors[i] = work
+        mask = bytes(bytearray(int(t) for t in take))
+        self._seed_take = take
+        L.check(self._lib.csr_batch_munc_seed_begin(self._ctx, mask, int(bool(floors)), int(bool(exclude))))
+        for i, a in seed_munc.items():
+            self._seed_put(i, "seed_total", a)
+        for i, a in floors.items():
+            self._seed_put(i, "seed_count_floor", a)
+        for i, a in exclude.items():
+            self._seed_put(i, "seed_exclude", a)
+
+    def munc_seed_upload(self, chain: int, name: str, arr):
+        """One chain's part of a resident seed array (`L.MUNC_SEED_ARRAYS`): planted inputs of a stage (a test's).  A planted
+        "seed_g" is read by the seed pass only: the smoother subtracts the batch's own background (`set_background`)."""
+        if name not in L.MUNC_SEED_ARRAYS:
+            raise ValueError(f"Unknown seed array: {name!r}")
+        self._seed_put(chain, name, arr)
+
+    def munc_seed_working(self, pad: float, use_weights: bool = True):
+        """`_seedWorkingMunc` (consenrich.py:7482-7503) of the current total, omega, rho and G INTO THE BATCH'S OWN munc: the next
+        `forward_backward` runs on it, and the fit's resident results are dropped."""
+        L.check(self._lib.csr_batch_munc_seed_working(self._ctx, float(pad), int(bool(use_weights))))
+
+    def munc_seed_pass(self, pad: float, update_weights: bool, student_t_df: float = 8.0, omega_min: float = 0.01,
+                       omega_max: float = 100.0, use_weights: bool = True, cap=None, student_t: bool = True):
+        """`cMuncObservationMomentSeedPass` as the loop calls it (consenrich.py:7505-7541) on the resident arrays: the batch's data,
+        the current total as matrixMunc, xs[:,0] and max(Ps[:,0,0], 0) of the resident smoothed fit, g, G, the count floor, the
+        current omega and rho.  The new rho, omega and total go to the "next" copies (`munc_seed_swap`), the pointwise local
+        evidence to "seed_local".  cap: the reference's maxR (None or <= 0: float32 max).  use_weights is the native's
+        `enabled and useSeedWeights`, student_t its `studentT` (the loop passes seedWeightEnabled and seedWeightStudentT combined
+        as use_weights and leaves studentT at True; Gaussian weights are use_weights=True, student_t=False: no reweighting).
+        The log-only moment and omegaRaw are never written.  Raises the reference's ValueErrors."""
+        from . import munc as M
+        cap = M.F32_MAX if cap is None or not cap > 0.0 else M._f32(cap)
+        cfg = M.seed_cfg(M._f32(pad), M._f32(student_t_df), 8.0, M._f32(omega_min), M._f32(omega_max), M._f32(1.0e-12), cap,
+                         bool(use_weights), bool(student_t), bool(update_weights))
+        L.check_value(self._lib.csr_batch_munc_seed_pass(self._ctx, C.byref(cfg)))
+
+    def munc_seed_background(self, lam_first: float, lam: float, zero_center=False, use_nonnegative=True,
+                             negative_penalty_multiplier=1.0, max_passes=5, block_len=0, *, pad: float, use_weights: bool = True,
+                             g_uncertainty: str = "proxy"):
+        """`_updateSeedBackground` (consenrich.py:7688-7777) after `munc_seed_pass` and before `munc_seed_swap`, with
+        `background_update`'s arguments: the per-cell inverse variance omega * rho / max(total + pad, 1e-12) (float64, cast to
+        float32; without weights 1 / max(total + pad, 1e-12)) of the CURRENT total, omega and rho, and the float32 residual data -
+        level of the resident fit feed the weighted statistics, the pentadiagonal solve and its asymmetric IRLS unchanged.
+        g_uncertainty "disabled": G = 0; "proxy": G = clip(float32(1 / max(sum of the float64 weights +
+        `_backgroundPenaltyDiagonal` + multiplier * max(median of the positive sums, 1e-12) where g < 0, 1e-12)), 0, q99 of the
+        chain's total).  "seed_g" / "seed_gvar" then hold the new pair and the batch's current background -- what the next
+        smoother subtracts from the data -- is the new g.  The solver's errors on a chain of the loop raise RuntimeError as in
+        `background_update`, and then no seed array has changed; the statistics and the solve also run over the chains the loop
+        left out, whose records come back but whose errors do not raise.  Returns one dict per chain."""
+        modes = {"disabled": 0, "proxy": 1}
+        if g_uncertainty not in modes:
+            raise RuntimeError(f"unsupported MUNC EB prior g uncertainty mode {g_uncertainty}")
+        nc = len(self.chain_lens)
+        cfg = L.BgCfg(float(lam_first), float(lam),
+                      float("nan") if negative_penalty_multiplier is None else float(negative_penalty_multiplier),
+                      int(bool(zero_center)), int(bool(use_nonnegative)), 0, 0, int(max_passes), int(block_len))
+        outs = (L.BgOut * nc)()
+        L.check(self._lib.csr_batch_munc_seed_background(self._ctx, C.byref(cfg), float(pad), int(bool(use_weights)),
+                                                         modes[g_uncertainty], outs))
+        res = [{k: getattr(o, k) for k, _ in L.BgOut._fields_} for o in outs]
+        self._raise_background_errors(res, getattr(self, "_seed_take", None))      # (a chain the loop left out is not its error)
+        return res
+
+    def munc_seed_background_tracks(self, chain: int):
+        """(weight, rhs, float64 weight sums) of one chain from the last `munc_seed_background`, float64 each."""
+        n = self.chain_lens[chain]
+        w, r, w64 = np.empty(n), np.empty(n), np.empty(n)
+        L.check(self._lib.csr_batch_munc_seed_background_tracks(self._ctx, int(chain), L.dp(w), L.dp(r), L.dp(w64)))
+        return w, r, w64
+
+    def munc_seed_swap(self, use_weights: bool = True):
+        """The end of a round (consenrich.py:7821-7827): the last pass's total, rho and omega become current; with weights disabled
+        omega and rho are refilled with 1."""
+        L.check(self._lib.csr_batch_munc_seed_swap(self._ctx, int(not use_weights)))
+
+    def munc_seed_finish(self, window: int, eps: float = 1.0e-12, cap=None, use_weights: bool = True):
+        """consenrich.py:7936-7945 after the pointwise pass: "seed_smooth" = `cMuncSmoothDenseLocalEvidence` of "seed_local" under
+        the exclude mask, "seed_total" = `_localEvidenceToTotalVariance` of it, "seed_weight" = rho * omega of the pointwise pass
+        (ones without weights)."""
+        from . import munc as M
+        L.check_value(self._lib.csr_batch_munc_seed_finish(self._ctx, int(window), M._f32(eps),
+                                                           0.0 if cap is None or not cap > 0.0 else float(cap),
+                                                           int(bool(use_weights))))
+
+    def download_munc_seed(self, chain: int, name: str) -> np.ndarray:
+        """One chain's part of a resident seed array: "seed_total", "seed_local" (pointwise), "seed_smooth" (local evidence),
+        "seed_rho", "seed_omega", "seed_g", "seed_gvar", "seed_weight", "seed_count_floor", "seed_exclude", or the "_next" copies
+        of total / rho / omega a pass wrote."""
+        if name not in L.MUNC_SEED_ARRAYS:
+            raise ValueError(f"Unknown seed array: {name!r}")
+        ident, per_cell, dtype = L.MUNC_SEED_ARRAYS[name]
+        n = self.chain_lens[chain]
+        out = np.empty((self.m, n) if per_cell else (n,), dtype)
+        L.check(self._lib.csr_batch_munc_seed_download(self._ctx, int(chain), ident, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def munc_seed_stats(self) -> dict:
+        """Counters since `munc_seed_begin`: passes, rolling means, the rows they smoothed and how many of those were redone
+        whole, a wavefront per row, after an inexact running-sum operation (in all, and in the last rolling mean)."""
+        st = L.MuncSeedStats()
+        L.check(self._lib.csr_batch_munc_seed_stats(self._ctx, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in L.MuncSeedStats._fields_}
 
     def export(self, what: int):
         L.check(self._lib.csr_batch_export(self._ctx, int(what)))

@@ -34,6 +34,7 @@ __all__ = [
     "cEstimateEffectiveSampleSize", "cchooseDependenceSpan",
     "cstateShrinkInitialSums", "cstateShrinkMixtureEMStep", "cstateShrinkMixtureEMStepPrepared", "cstateShrinkMixturePosterior",
     "cstateShrinkMixturePosteriorPrepared",
+    "cMuncObservationMomentSeedPass", "cMuncSmoothDenseLocalEvidence",
 ]
 
 
@@ -639,6 +640,9 @@ from .segments import cMultiscaleCandidateSegmentStats  # noqa: E402,F401
 
 # effective sample size scan behind the ROCCO budget (pyx:9160-9279), implemented in consenrich_amd/ess.py
 from .ess import cEstimateEffectiveSampleSize  # noqa: E402,F401
+
+# dense observation-variance seed natives (pyx:4843-5351, 5577-5741), implemented in consenrich_amd/munc.py
+from .munc import cMuncObservationMomentSeedPass, cMuncSmoothDenseLocalEvidence  # noqa: E402,F401
 
 # dependence span from the per-chromosome matrices (pyx:3360-4120), implemented in consenrich_amd/depspan.py
 from .depspan import cchooseDependenceSpan  # noqa: E402,F401

@@ -490,6 +490,13 @@ struct BgBatch {
     int NW, pad_;
     double *part;                       // NW x 4 partial records
     double *chainSum;                   // per chain: [sumW, support, sum w d^2, sum w next^2, sum w cur^2]
+    // CSR_BG_SEED_WEIGHTS (the seed loop's `_updateSeedBackground`, consenrich.py:7699-7711): the inverse variance of a cell is
+    // float32 of the float64 omega * rho / max(total + pad, 1e-12) (seedMode 1) or 1 / max(total + pad, 1e-12) (seedMode 2) of
+    // the seed arrays instead of 1 / (munc + pad); seedW64: the float64 sum over the tracks of the float64 values (the G proxy's)
+    int seedMode, pad2_;
+    double seedPad;
+    const float *seedTotal, *seedRho, *seedOmega;
+    double *seedW64;
 };
 
 // weight / rhs per bin exactly as the reference forms them (core.py:5064-5083): float32 invVar = 1/max(munc+pad,1e-8)
@@ -503,13 +510,24 @@ __global__ __launch_bounds__(256) void k_bg_batch_stats(Prm p, BgBatch a) {
         float lam = 1.f;
         if (a.useLambda) lam = fminf(fmaxf(a.lamNat[g], a.wMinf), a.wMaxf);
         const float xs0 = a.xsNat ? a.xsNat[g * a.xsStride] : 0.0f;      // null: background warm start (core.py:2857)
+        double w64 = 0.0;
         for (int j = 0; j < p.m; ++j) {
-            float iv = __fdiv_rn(1.0f, fmaxf(p.munc[(int64_t)j * p.Npad + g] + a.padf, 1.0e-8f));
-            if (a.useLambda) iv *= lam;
+            float iv;
+            if (a.seedMode) {
+                double base = (double)a.seedTotal[(int64_t)j * p.Npad + g] + a.seedPad;
+                base = base < 1.0e-12 ? 1.0e-12 : base;
+                const double iv64 = a.seedMode == 1 ? (double)a.seedOmega[g] * (double)a.seedRho[(int64_t)j * p.Npad + g] / base : 1.0 / base;
+                w64 += iv64;
+                iv = (float)iv64;
+            } else {
+                iv = __fdiv_rn(1.0f, fmaxf(p.munc[(int64_t)j * p.Npad + g] + a.padf, 1.0e-8f));
+                if (a.useLambda) iv *= lam;
+            }
             const float res = p.data[(int64_t)j * p.Npad + g] - xs0;
             ws += (double)iv;
             rs += (double)iv * (double)res;
         }
+        if (a.seedMode) a.seedW64[g] = w64;
     }
     a.w[g] = ws;
     a.rhs[g] = rs;

@@ -352,6 +352,15 @@ extern "C" int csr_batch_background_update(csr_ctx *c, const csr_bg_cfg *cfg, cs
     a.lamNat = cfg->use_lambda ? c->nat[CSR_ARR_LAMBDA] : nullptr;
     a.padf = (float)c->mdl.pad; a.wMinf = (float)c->mdl.w_min; a.wMaxf = (float)c->mdl.w_max;
     a.bgCur = S.haveCur ? c->nat[CSR_ARR_BACKGROUND] : nullptr;
+    // use_initial bit 2 (CSR_BG_SEED_WEIGHTS): the per-cell weights of the seed loop (csr_batch_munc_seed_background set them up)
+    a.seedMode = 0;
+    if (cfg->use_initial & CSR_BG_SEED_WEIGHTS) {
+        if (!c->seed.ready || !c->seed.w64) return fail("CSR_BG_SEED_WEIGHTS: call csr_batch_munc_seed_background");
+        a.seedMode = c->seed.bgUseWeights ? 1 : 2;
+        a.seedPad = c->seed.bgPad;
+        a.seedTotal = c->seed.total[c->seed.cur]; a.seedRho = c->seed.rho[c->seed.cur]; a.seedOmega = c->seed.omega[c->seed.cur];
+        a.seedW64 = c->seed.w64;
+    }
     Prm p = c->p;
     CHECK(launch(c, "bg_batch_stats", "k_bg_batch_stats", k_bg_batch_stats, dim3(gridN), dim3(256), 0, c->stream, p, a));
     const int gridW = (a.NW + 3) / 4;

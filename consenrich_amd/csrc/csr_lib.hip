@@ -22,6 +22,7 @@
 #include "csr_broad.h"
 #include "csr_depspan.h"
 #include "csr_shrink.h"
+#include "csr_munc.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
 
@@ -359,6 +360,26 @@ struct BatchState {
     ChainTrack<float> shrinkVar{"shrinkage variance track"}, shrunk{"shrunk track"}, shrunkSd{"shrunk posterior sd track"},
         shrunkSpike{"shrunk spike probability track"}, shrunkSlabMean{"shrunk slab mean track"},
         shrunkSlabWeight{"shrunk slab weight track"};
+    // the dense observation-variance seed loop (csr_host_munc.inl): its arrays in the batch's own layout ((m, Npad) per cell, Npad per
+    // interval), from dalloc at the first csr_batch_munc_seed_begin.  total / rho / omega are double-buffered: a pass reads [cur] and
+    // writes [1 - cur].  idx / dOff / dLen: the chains the loop takes; work: the invalid flag, the fallback count and one word per row
+    struct MuncSeed {
+        bool ready = false, useCountFloor = false, useExclude = false;
+        int cur = 0;
+        std::vector<int> idx;
+        int64_t longest = 0;
+        int64_t *dOff = nullptr, *dLen = nullptr;
+        float *total[2] = {nullptr, nullptr}, *rho[2] = {nullptr, nullptr}, *omega[2] = {nullptr, nullptr};
+        float *local = nullptr, *smooth = nullptr, *weight = nullptr, *g = nullptr, *gvar = nullptr, *countFloor = nullptr;
+        unsigned char *exclude = nullptr;
+        unsigned int *work = nullptr;
+        double *w64 = nullptr, *gSel = nullptr;     // seed background: float64 weight track; per-chain penalty and clip of the G proxy
+        unsigned long long *rankCount = nullptr;
+        unsigned int *rankTrial = nullptr;
+        double bgPad = 0.0;
+        bool bgUseWeights = true;
+        csr_munc_seed_stats stats{};
+    } seed;
     int exportSignal = 0;       // CSR_SIGNAL_*: what the export stages read as signal (csr_batch_set_export_signal)
     // ROCCO's work arrays without presence (csr_host_rocco.inl): backtrace words, per-chain maxima and flags; its growable work
     // space is csr_ctx::roccoWs
@@ -541,6 +562,10 @@ struct csr_ctx : BatchState {
         size_t nOut = 0;
         DevBuf xBuf, vBuf, chainBuf, cntBuf, partBuf, outBuf, priorBuf, postBuf, keyBuf;
     } shrinkWs;
+    // dense observation-variance seed natives on host arrays (csr_host_munc.inl): the staged inputs, the outputs, flags and row words
+    struct MuncWs {
+        DevBuf in, out, flag;
+    } muncWs;
     // DWB peak scoring (csr_host_peakscore.inl): growable work space of a call -- an uploaded host track, the segments, views and
     // results of a scoring call, the observed and pooled statistics with their p / q values (sorted through nullWs)
     struct PeakWs {
@@ -967,3 +992,4 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_broad.inl"
 #include "csr_host_depspan.inl"
 #include "csr_host_shrink.inl"
+#include "csr_host_munc.inl"

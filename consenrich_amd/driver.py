@@ -886,3 +886,81 @@ def shrink_state_batch(batch: DeviceBatch, *, block_size, chains=None, variance=
     prior = batch.shrink_fit(chains=chains, variance=variance, block_size=block_size, model=model, **fit_arguments)
     return prior, batch.shrink_apply(prior, spike_odds_multiplier=spike_odds_multiplier, chains=chains, variance=variance,
                                      want_slab=want_slab)
+
+
+def munc_seed_batch(batch: DeviceBatch, *, pad: float, window: int, passes: int = 3, state_model: str = "levelTrend",
+                    count_floor=None, exclude=None, chains=None, weights: str = "student_t", student_t_df: float = 8.0,
+                    omega_min: float = 0.01, omega_max: float = 100.0, cap=None, fit_background: bool = True, background=None,
+                    g_uncertainty: str = "proxy", q=None, min_q: float = 1.0e-6, max_q: float = 1000.0, robust_t_nu=8.0,
+                    eps: float = 1.0e-12, fetch=("local_evidence", "seed_munc", "response_weight")) -> List[dict]:
+    """The dense observation-variance seed loop of `_collectPooledMuncBlocks` (consenrich.py:7784-7945) for the chains of a batch
+    at once, chains of unequal length included.  The batch holds the data and the SEED munc of every chain (`upload`).  Per round:
+    working munc (`munc_seed_working`), forward / backward without multipliers with the Q0 seed of the resident data and seed munc
+    (`qseed` with min_q / max_q / robust_t_nu, once, or the per-chain matrices `q`), the seed pass with updated weights, the seed
+    background (`munc_seed_background`), swap.  Then the final smoother, the pointwise pass, the rolling mean over `window`
+    intervals, the total variance and the response weights (`munc_seed_finish`).  No (m, n) array crosses the bus between the begin
+    and the downloads `fetch` asks for.
+
+    weights: "student_t" (seedWeightEnabled and seedWeightStudentT), "gaussian" (enabled, Student-t off) or "disabled".  As in
+    the reference, the last two run the same arithmetic -- no reweighting, omega and rho refilled with 1 after every round
+    (consenrich.py:7825-7827) -- and differ in the label of its log line only.
+    fit_background (the reference's `fitBackground`): True needs `background`, a dict of `munc_seed_background`'s arguments
+    (lam_first, lam, and optionally zero_center, use_nonnegative, negative_penalty_multiplier, max_passes, block_len); False keeps
+    g = G = 0.  g_uncertainty: "proxy" or "disabled".
+
+    Returns one dict per chain (None for a chain `chains` leaves out) with the entries `fetch` names: "local_evidence" (the
+    smoothed local evidence), "seed_munc" (total variance), "response_weight", "seed_mean" (float64 of the level of the final
+    smoother), "omega", "rho" (of the pointwise pass), "background", "g_variance", "pointwise" (the local evidence before the
+    rolling mean: what the Nu_L effective-sample-size scan reads).
+
+    ON EXIT THE BATCH'S OWN munc HOLDS THE LAST WORKING munc, not what was uploaded, its current background is the seed
+    background g (zero without the fit), its per-chain Q0 is the seed's, and the resident fit is the final seed smoother's.  A
+    chain `chains` leaves out keeps its munc, its background and its seed arrays; its Q0 is set like the others' and the
+    smoothers run over it too (its resident fit changes)."""
+    if weights not in ("student_t", "gaussian", "disabled"):
+        raise ValueError(f"Unknown weights: {weights!r}")
+    use_weights = weights == "student_t"
+    if fit_background and background is None:
+        raise ValueError("fit_background needs `background`: the arguments of munc_seed_background (lam_first, lam, ...)")
+    if int(passes) < 0:
+        raise ValueError("passes must be nonnegative")
+    names = {"local_evidence": "seed_smooth", "seed_munc": "seed_total", "response_weight": "seed_weight", "omega": "seed_omega_next",
+             "rho": "seed_rho_next", "background": "seed_g", "g_variance": "seed_gvar", "pointwise": "seed_local"}
+    for f in fetch:
+        if f not in names and f != "seed_mean":
+            raise ValueError(f"Unknown output: {f!r}")
+    nc = len(batch.chain_lens)
+    take = [True] * nc if chains is None else [bool(t) for t in chains]
+    if q is None:
+        q = [s[0] for s in batch.qseed(pad=pad, stateModel=state_model, minQ=min_q, maxQ=max_q, robustTNu=robust_t_nu)]
+    d = batch.d
+    batch.set_chain_q([np.asarray(x, np.float32)[:d, :d] for x in q])
+    batch.munc_seed_begin(count_floor=count_floor, exclude=exclude, chains=chains)
+    for i in range(nc):
+        if take[i]:
+            batch.set_background(i, None)
+
+    def seed_pass(update):
+        batch.munc_seed_working(pad, use_weights)
+        batch.stats()
+        batch.forward_backward(want_sums=False)
+        batch.munc_seed_pass(pad, update, student_t_df, omega_min, omega_max, weights != "disabled", cap,
+                             student_t=weights == "student_t")
+
+    for _ in range(int(passes)):
+        seed_pass(True)
+        if fit_background:
+            batch.munc_seed_background(pad=pad, use_weights=use_weights, g_uncertainty=g_uncertainty, **background)
+        batch.munc_seed_swap(use_weights)
+    seed_pass(False)
+    batch.munc_seed_finish(window, eps, cap, use_weights)
+    out: List[Optional[dict]] = []
+    for i in range(nc):
+        if not take[i]:
+            out.append(None)
+            continue
+        rec = {f: batch.download_munc_seed(i, names[f]) for f in fetch if f in names}
+        if "seed_mean" in fetch:
+            rec["seed_mean"] = batch.download(i, "xs")[:, 0].astype(np.float64)
+        out.append(rec)
+    return out

@@ -305,7 +305,8 @@ typedef struct csr_bg_cfg {
     int32_t max_passes;                 /* reference: 5 */
     int32_t block_len;                  /* partition size of the solver, 0 = default */
 } csr_bg_cfg;
-enum { CSR_BG_INIT_FROM_CURRENT = 1, CSR_BG_ZERO_STATE = 2 };
+enum { CSR_BG_INIT_FROM_CURRENT = 1, CSR_BG_ZERO_STATE = 2,
+       CSR_BG_SEED_WEIGHTS = 4 /* the seed loop's per-cell weights: set by csr_batch_munc_seed_background only */ };
 enum { CSR_BG_OK = 0, CSR_BG_NO_SUPPORT = 1, CSR_BG_BAD_PIVOT = 2, CSR_BG_UNRELIABLE = 3, CSR_BG_NONFINITE = 4 };
 typedef struct csr_bg_out {
     int64_t support;                    /* bins with positive weight */
@@ -1135,6 +1136,70 @@ int csr_batch_shrink_medians(csr_ctx *ctx, int64_t *count, double *mid);
  * with "chain i has no shrunk track" before any launch.  Scores, masks and uncertainty are read as before. */
 enum { CSR_SIGNAL_STATE = 0, CSR_SIGNAL_SHRUNK = 1 };
 int csr_batch_set_export_signal(csr_ctx *ctx, int32_t signal);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Dense observation-variance ("munc") seed natives: `cMuncObservationMomentSeedPass` (pyx:4843-5351) and
+ * `cMuncSmoothDenseLocalEvidence` (pyx:5577-5741), and the per-cell glue of the seed loop (consenrich.py:7482-7576, 7938-7945),
+ * on host arrays (default context) and on arrays that stay resident with a batch between the loop's rounds.  Every output
+ * element equals the reference's bit for bit.  Invalid cells and parameters return CSR_ERR_VALUE with the reference's text.
+ * use_weights is the reference's `enabled and useSeedWeights`.  Masks: mode 0 none, 1 per interval (n bytes), 2 per cell
+ * ((m, n) bytes); a nonzero byte means ACTIVE in the seed pass and EXCLUDED in the rolling mean, as in the reference.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct csr_munc_seed_cfg {
+    double pad, student_t_df, d_omega, omega_min, omega_max, variance_floor, variance_cap;
+    int32_t use_weights, student_t, update_weights, reserved_;
+} csr_munc_seed_cfg;
+typedef struct csr_munc_seed_stats {
+    int64_t passes;                     /* resident seed passes since csr_batch_munc_seed_begin */
+    int64_t rolls;                      /* rolling means since then ... */
+    int64_t roll_rows;                  /* ... the rows they smoothed ... */
+    int64_t roll_fallback_rows;         /* ... and those of them redone whole (one wavefront per row) after an inexact running-sum operation */
+    int64_t last_roll_fallback_rows;    /* the same count of the last rolling mean alone */
+} csr_munc_seed_stats;
+/* (m, n) float32 arrays; background / g_variance / count_floor / omega_in / rho_in / active may be NULL (rho_in NULL = ones).
+ * All six outputs are written: moment, rho_out, local, variance (m, n); omega_raw, omega_out (n). */
+int csr_munc_seed_pass(int64_t m, int64_t n, const float *data, const float *munc, const float *state_mean,
+                       const float *state_variance, const float *background, const float *g_variance, const float *count_floor,
+                       const float *omega_in, const float *rho_in, const unsigned char *active, int32_t active_mode,
+                       const csr_munc_seed_cfg *cfg, float *moment, float *rho_out, float *omega_raw, float *omega_out, float *local,
+                       float *variance);
+/* out (m, n); fallback_rows (may be NULL): rows redone whole, a wavefront per row, because an add or subtract of their running sum was inexact */
+int csr_munc_smooth_local(int64_t m, int64_t n, const float *local, int64_t window, const unsigned char *exclude,
+                          int32_t exclude_mode, double eps, float *out, int64_t *fallback_rows);
+/* The arrays of the seed loop, resident in the batch's layout and freed with the batch.  total / rho / omega have a current and
+ * a "next" copy: csr_batch_munc_seed_pass reads the current ones and writes the next ones, csr_batch_munc_seed_swap makes the
+ * next ones current.  LOCAL is the pointwise local evidence a pass leaves, SMOOTH its rolling mean, WEIGHT the response weight
+ * (both from csr_batch_munc_seed_finish).  G / GVAR: the seed background and its variance (zero unless uploaded). */
+enum {
+    CSR_MUNC_SEED_TOTAL = 0, CSR_MUNC_SEED_LOCAL, CSR_MUNC_SEED_RHO, CSR_MUNC_SEED_OMEGA, CSR_MUNC_SEED_G, CSR_MUNC_SEED_GVAR,
+    CSR_MUNC_SEED_WEIGHT, CSR_MUNC_SEED_COUNT_FLOOR, CSR_MUNC_SEED_EXCLUDE, CSR_MUNC_SEED_SMOOTH, CSR_MUNC_SEED_TOTAL_NEXT,
+    CSR_MUNC_SEED_RHO_NEXT, CSR_MUNC_SEED_OMEGA_NEXT
+};
+/* total := the batch's resident munc, omega = rho = 1, everything else 0; chain_mask (n_chains bytes or NULL = all): the chains
+ * the loop takes.  use_count_floor / use_exclude: the pass reads COUNT_FLOOR, the rolling mean reads EXCLUDE (per interval). */
+int csr_batch_munc_seed_begin(csr_ctx *ctx, const unsigned char *chain_mask, int32_t use_count_floor, int32_t use_exclude);
+/* one chain's part of a seed array: (m, n) float32, (n) float32 for OMEGA* / G / GVAR, (n) bytes for EXCLUDE */
+int csr_batch_munc_seed_upload(csr_ctx *ctx, int32_t chain, int32_t array_id, const void *host_src);
+int csr_batch_munc_seed_download(csr_ctx *ctx, int32_t chain, int32_t array_id, void *host_dst);
+/* `_seedWorkingMunc` of the current total / omega / rho / GVAR into the batch's own munc (the next pass of the fit reads it) */
+int csr_batch_munc_seed_working(csr_ctx *ctx, double pad, int32_t use_weights);
+/* the seed pass on the batch's data, the current total as munc and the resident smoothed fit (xs[:,0], max(Ps[:,0,0], 0)) */
+int csr_batch_munc_seed_pass(csr_ctx *ctx, const csr_munc_seed_cfg *cfg);    /* (moment and omegaRaw, log-only in the loop, are never written: no switches are offered) */
+int csr_batch_munc_seed_swap(csr_ctx *ctx, int32_t refill_weights);
+/* SMOOTH := rolling mean of LOCAL; TOTAL := min(SMOOTH + COUNT_FLOOR, cap) floored at 1e-12 in float32 (cap <= 0: none);
+ * WEIGHT := RHO_NEXT * OMEGA_NEXT (use_weights 0: ones) */
+int csr_batch_munc_seed_finish(csr_ctx *ctx, int64_t window, double eps, double cap, int32_t use_weights);
+int csr_batch_munc_seed_stats(csr_ctx *ctx, csr_munc_seed_stats *out);
+/* `_updateSeedBackground` (consenrich.py:7688-7777) after a seed pass and before the swap: csr_batch_background_update with the
+ * seed's per-cell weights (float32 of omega * rho / max(total + pad, 1e-12) of the CURRENT total / omega / rho; use_weights 0:
+ * 1 / max(total + pad, 1e-12)) and the residual data - level of the resident fit; cfg->use_initial and use_lambda are ignored.
+ * g_mode 0 ("disabled"): G = 0; 1 ("proxy"): the diagonal proxy clipped to [0, q99 of the chain's total] (the total's cells ordered
+ * like their values, negative ones and infinities included; NaN cells are not NumPy's quantile).  out: n_chains records;
+ * a status of 2..4 on a chain of the loop leaves every seed array as it was.  On success G / GVAR hold the new pair and the
+ * batch's current background (what the next forward / backward pass subtracts) is the new g for the loop's chains. */
+int csr_batch_munc_seed_background(csr_ctx *ctx, const csr_bg_cfg *cfg, double pad, int32_t use_weights, int32_t g_mode, csr_bg_out *out);
+/* the last update's float64 weight / rhs tracks of one chain and the float64 sums of the float64 weights (any may be NULL) */
+int csr_batch_munc_seed_background_tracks(csr_ctx *ctx, int32_t chain, double *weight, double *rhs, double *weight64);
 
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
