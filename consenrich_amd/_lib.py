@@ -172,6 +172,22 @@ class MuncSeedStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("passes", "rolls", "roll_rows", "roll_fallback_rows", "last_roll_fallback_rows")]
 
 
+class MuncTrackPrm(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("nu_local", "nu_prior", "posterior", "factor")] + \
+               [("scale", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class MuncTrackOut(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("invalid_local", "invalid_prior", "invalid_count_floor", "support", "floor_finite",
+                                         "floor_added", "floor_missing")] + [("blacklist_floor", C.c_double)]
+
+
+# csr_munc_block_rec as a NumPy record
+MUNC_BLOCK_REC = [("valid", "<i8"), ("q", "<f8"), ("qp", "<f8"), ("qe", "<f8"), ("qq", "<f8")]
+MUNC_BLOCK_MAX = 2048        # csr_munc_track.h: intervals per block at most
+MUNC_TRACK_MAX_DEGREE, MUNC_TRACK_MAX_BASIS = 5, 512
+
+
 class EssOut(C.Structure):
     _fields_ = [("n_eff", C.c_double), ("tau", C.c_double), ("lags_used", C.c_int64)]
 
@@ -189,7 +205,8 @@ MUNC_SEED_ARRAYS = {"seed_total": (0, True, "float32"), "seed_local": (1, True, 
                     "seed_weight": (6, True, "float32"), "seed_count_floor": (7, True, "float32"),
                     "seed_exclude": (8, False, "uint8"), "seed_smooth": (9, True, "float32"),
                     "seed_total_next": (10, True, "float32"), "seed_rho_next": (11, True, "float32"),
-                    "seed_omega_next": (12, False, "float32")}
+                    "seed_omega_next": (12, False, "float32"), "seed_prior": (13, False, "float32"),
+                    "seed_track_floor": (14, True, "float32")}
 MUNC_ROLL_BLOCK = 128        # csr_munc.h: intervals per speculative block of the rolling mean
 MUNC_REG_TRACKS = 16         # ... and up to how many tracks the seed pass keeps its float32 pair in registers
 ARR_SHRINK_BASE = 64         # writers: ARR_SHRINK_BASE + SHRINK_TRACKS[name] as array id
@@ -526,6 +543,18 @@ SYMBOLS = {
     "csr_batch_munc_seed_stats": (C.c_int, [C.c_void_p, C.POINTER(MuncSeedStats)]),
     "csr_batch_munc_seed_background": (C.c_int, [C.c_void_p, C.POINTER(BgCfg), C.c_double, C.c_int32, C.c_int32, C.POINTER(BgOut)]),
     "csr_batch_munc_seed_background_tracks": (C.c_int, [C.c_void_p, C.c_int32, DP, DP, DP]),
+    "csr_munc_block_sums": (C.c_int, [C.c_int64, C.c_int64, FP, FP, C.POINTER(C.c_uint8), DP, C.c_int64, C.c_void_p, I64P]),
+    "csr_munc_eval_pspline": (C.c_int, [C.c_int64, DP, DP, C.c_int64, DP, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, FP]),
+    "csr_munc_finalize_track": (C.c_int, [C.c_int64, FP, FP, FP, C.POINTER(MuncTrackPrm), C.c_double, C.c_double, C.c_int32, FP,
+                                          C.POINTER(MuncTrackOut)]),
+    "csr_munc_blacklist_floor": (C.c_int, [C.c_int64, C.c_int64, FP, C.POINTER(C.c_uint8), C.c_double, C.c_double, DP]),
+    "csr_batch_munc_block_sums": (C.c_int, [C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_int64, I64P, C.c_int64]),
+    "csr_batch_munc_prior_track": (C.c_int, [C.c_void_p, C.c_char_p, DP, C.c_int64, DP, C.c_int64, C.c_int32, C.c_double,
+                                             C.c_double, C.c_double, C.c_double]),
+    "csr_batch_munc_track_finish": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(MuncTrackPrm), C.c_double, C.c_double, C.c_int32,
+                                              C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(MuncTrackOut),
+                                              I64P]),
 }
 
 _lib = None

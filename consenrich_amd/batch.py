@@ -1456,6 +1456,161 @@ class DeviceBatch:
         L.check(self._lib.csr_batch_munc_seed_stats(self._ctx, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in L.MuncSeedStats._fields_}
 
+    # -- finished observation-variance tracks (consenrich_amd/munc_track.py, csrc/csr_munc_track.h) ----------------------------
+    def _track_take(self, chains):
+        """The chains a stage after the seed loop takes: `chains`, or those of the seed loop."""
+        seed = getattr(self, "_seed_take", None)
+        if seed is None:
+            raise L.ConsenrichAMDError("no seed arrays: call munc_seed_begin first")
+        nc = len(self.chain_lens)
+        take = list(seed) if chains is None else [bool(t) for t in chains]
+        if len(take) != nc:
+            raise ValueError("one entry per chain")
+        return take, bytes(bytearray(int(t) for t in take))
+
+    def munc_block_sums(self, block_intervals: int, chains=None):
+        """The deterministic block summaries of consenrich.py:7981-8040 from the resident "seed_smooth" (local evidence),
+        "seed_weight" (zero where "seed_exclude" is set) and the predictor sign(x) log1p(|x|) of xs[:,0] of the resident smoothed
+        fit: blocks of max(2, block_intervals) intervals (at most 2048), a last block shorter than 2 dropped.  Returns one dict
+        per chain (None where not taken): "valid" (int64), "q", "qp", "qe", "qq" (float64 np.sum of q, q * predictor,
+        q * evidence, q * q over the valid cells), each (m, blocks); "included" (non-excluded intervals per block), "starts",
+        "ends".  A chain without a block raises the reference's RuntimeError; a fit that is no longer resident is an error
+        before any launch.  `munc_track.pooled_block_rows` turns the records into the pooled rows of the trend fit."""
+        from . import munc_track as MT
+
+        if max(2, int(block_intervals)) > L.MUNC_BLOCK_MAX:
+            raise ValueError(f"block_intervals {int(block_intervals)}: the device stages blocks of up to {L.MUNC_BLOCK_MAX} intervals")
+        take, mask = self._track_take(chains)
+        layout = [MT.block_layout(n, block_intervals) if t else None for n, t in zip(self.chain_lens, take)]
+        for i, lay in enumerate(layout):
+            if lay is not None and lay[0].size == 0:
+                raise RuntimeError(f"MUNC has no deterministic blocks for chain {i}")
+        blocks = sum(lay[0].size for lay in layout if lay is not None)
+        recs = np.zeros(blocks * self.m, dtype=L.MUNC_BLOCK_REC)
+        included = np.zeros(blocks, dtype=np.int64)
+        L.check_value(self._lib.csr_batch_munc_block_sums(self._ctx, int(block_intervals), mask, recs.ctypes.data_as(C.c_void_p),
+                                                          recs.shape[0], L._i64p(included), blocks))
+        out, at_rec, at_blk = [], 0, 0
+        for lay in layout:
+            if lay is None:
+                out.append(None)
+                continue
+            nb = lay[0].size
+            part = recs[at_rec:at_rec + nb * self.m].reshape(self.m, nb)
+            rec = {k: np.ascontiguousarray(part[k]) for k in ("valid", "q", "qp", "qe", "qq")}
+            rec.update(included=included[at_blk:at_blk + nb].copy(), starts=lay[0], ends=lay[1])
+            out.append(rec)
+            at_rec += nb * self.m
+            at_blk += nb
+        return out
+
+    def munc_prior_track(self, trend, floor: float = 1.0e-12, cap=None, chains=None):
+        """`evalPSplineLogVarianceTrend` (core.py:6628-6655) of the float32 level xs[:,0] of the resident smoothed fit (the prior
+        mean track of consenrich.py:8163) into the resident per-interval "seed_prior".  trend: (knots, beta, degree, xMin, xMax) or
+        an object with those attributes; floor / cap: the reference's eps / maxVariance.  The device evaluates degrees up to 5
+        and up to 512 basis functions (ValueError beyond); degree < 0 or empty knots is the constant fallback."""
+        from . import munc_track as MT
+
+        knots, beta, degree, x_min, x_max = MT.trend_fields(trend)
+        knots, beta = np.ascontiguousarray(knots.ravel()), np.ascontiguousarray(beta.ravel())
+        MT.check_trend_limits(knots, beta, degree)
+        log_floor, log_cap = MT.log_bounds(floor, cap)
+        _take, mask = self._track_take(chains)
+        L.check_value(self._lib.csr_batch_munc_prior_track(self._ctx, mask, L.dp(knots), knots.shape[0], L.dp(beta), beta.shape[0],
+                                                           degree, x_min, x_max, log_floor, log_cap))
+
+    def munc_track_finish(self, nu_local, nu_prior, replicate_factors=None, count_floor=None, floor: float = 1.0e-12, cap=None,
+                          use_eb: bool = True, blacklist_quantile: float = 0.05, chains=None):
+        """The finished `matrixMunc` of the taken chains INTO THE BATCH'S OWN munc (the next `forward_backward` runs on it; the
+        fit's resident results are dropped).  Per (sample j, interval), as `getMuncTrack` (core.py:8390-8880) does with a pooled
+        trend, a prior variance track, a pooled Nu_0 and an effective Nu_L: local = clamp("seed_smooth"), prior =
+        clamp(float32(float64("seed_prior") * factor_j)) (no product where |factor_j - 1| <= 1e-8), (Nu_L local + Nu_0 prior) /
+        (Nu_L + Nu_0) in float64, clamped, plus the count floor where it is finite, clamped, cast to float32.  Then
+        `applyBlacklistMuncFloor` with minR = 1e-12 under the seed loop's exclude mask (skipped without one) and the clamp of
+        consenrich.py:9107-9113.
+
+        nu_local / nu_prior: scalars or one value per sample, the reference's EB_effectiveNuL (at least 4) and EB_pooledNu0
+        (capped at 50 Nu_L here); replicate_factors: one per sample (None: 1); floor / cap: the reference's
+        varianceFloorForTrend and maxR (None or <= 0: none); use_eb=False is the reference's no-EB branch (nu_* unused).
+        count_floor[chain]: the caller's RAW (m, n) floor, NaN = missing ("seed_count_floor" has them zeroed); it is uploaded to
+        "seed_track_floor".
+
+        Raises what the reference raises, first chain and sample first: the count floor's ValueError of
+        `_coerceMuncCountModelVarianceFloor`, then an invalid local value, then an invalid prior value (both under the native's
+        "localVarianceTrack must contain finite positive values at index i", as `getMuncTrack` passes them), and the
+        RuntimeError of consenrich.py:9100-9106.  Nothing of the batch changes then.
+
+        Returns {"diagnostics": per chain (None where not taken) a list of the native's diagnostics dicts per sample,
+        "floors": per chain the float64 blacklist floors per sample}."""
+        from . import munc_track as MT
+
+        m, nc = self.m, len(self.chain_lens)
+        take, mask = self._track_take(chains)
+        floor_, cap_, cap_kernel = MT.variance_bounds(floor, floor, cap if cap is not None and cap > 0.0 else None)
+        floor32, cap32 = MT._f32(floor_), MT._f32(cap_kernel)
+        factors = np.ones(m) if replicate_factors is None else np.asarray(replicate_factors, dtype=np.float64).reshape(-1)
+        if factors.shape[0] != m:
+            raise ValueError("one replicate factor per sample")
+        if np.any(~np.isfinite(factors) | (factors <= 0.0)):
+            raise ValueError("replicateVarianceFactor must be positive and finite")
+        prm = (L.MuncTrackPrm * m)()
+        if use_eb:
+            nu_l = np.broadcast_to(np.asarray(nu_local, dtype=np.float64).reshape(-1), (m,))     # (a scalar, or one per sample)
+            nu_0 = np.broadcast_to(np.asarray(nu_prior, dtype=np.float64).reshape(-1), (m,))
+            for j in range(m):
+                if not np.isfinite(nu_l[j]) or nu_l[j] < 4.0:
+                    raise ValueError("EB_effectiveNuL must be finite and at least 4.0")
+                if MT._prior_strength(nu_0[j]) is None:
+                    raise ValueError("nu_prior must be finite and at least 4.0 (the branch that estimates Nu_0 is not built)")
+                n0 = min(float(nu_0[j]), 50.0 * float(nu_l[j]))          # core.py:8796-8804
+                prm[j] = L.MuncTrackPrm(MT._f32(nu_l[j]), MT._f32(n0), 0.0, float(factors[j]), 0, 0)
+        else:
+            for j in range(m):
+                prm[j] = L.MuncTrackPrm(0.0, 0.0, 0.0, 1.0, 0, 0)
+        floors_in = {}
+        if count_floor is not None:
+            items = count_floor.items() if isinstance(count_floor, dict) else enumerate(count_floor)
+            floors_in = {int(i): v for i, v in items if v is not None and take[int(i)]}
+        for i, f in floors_in.items():
+            work = np.asarray(f)
+            if work.shape != (m, self.chain_lens[i]):
+                raise ValueError("countModelVarianceFloor must be a one-dimensional track matching the MUNC interval count")
+            if work.dtype != np.float32:        # (the device sees float32: a negative value that rounds to -0.0 is caught here)
+                work = np.asarray(work, dtype=np.float64)
+                if np.any(np.isfinite(work) & (work < 0.0)):
+                    raise ValueError("countModelVarianceFloor must be nonnegative where finite")
+            self._seed_put(i, "seed_track_floor", work.astype(np.float32))
+        if floors_in:
+            for i in range(nc):
+                if take[i] and i not in floors_in:
+                    self._seed_put(i, "seed_track_floor", np.full((m, self.chain_lens[i]), np.nan, np.float32))
+        taken = [i for i in range(nc) if take[i]]
+        outs = (L.MuncTrackOut * (len(taken) * m))()
+        non_finite = np.zeros(len(taken), dtype=np.int64)
+        clamp_hi = float(cap) if cap is not None and np.isfinite(float(cap)) and float(cap) > MT.NUMERIC_VARIANCE_FLOOR else 0.0
+        L.check_value(self._lib.csr_batch_munc_track_finish(self._ctx, mask, prm, floor32, cap32, int(bool(use_eb)), int(bool(floors_in)),
+                                                            MT.NUMERIC_VARIANCE_FLOOR, float(np.clip(float(blacklist_quantile), 0.0, 1.0)),
+                                                            MT.NUMERIC_VARIANCE_FLOOR, clamp_hi, outs, L._i64p(non_finite)))
+        diagnostics, floors = [None] * nc, [None] * nc
+        for k, i in enumerate(taken):
+            n, diag, fl = self.chain_lens[i], [], []
+            for j in range(m):
+                res = MT._out_dict(outs[k * m + j])
+                if res["invalid_count_floor"] >= 0:
+                    raise ValueError("countModelVarianceFloor must be nonnegative where finite")
+                for kind in ("invalid_local", "invalid_prior"):
+                    if res[kind] >= 0:
+                        raise ValueError(f"localVarianceTrack must contain finite positive values at index {res[kind]}")
+                if res["floor_finite"] == 0:
+                    res["floor_missing"] = 0        # core.py:7404-7405: a floor without a finite entry is no floor
+                diag.append(MT.track_diagnostics(res, n, bool(use_eb)))
+                fl.append(res["blacklist_floor"])
+            diagnostics[i], floors[i] = diag, np.asarray(fl, dtype=np.float64)
+        for k, i in enumerate(taken):
+            if non_finite[k]:
+                raise RuntimeError(f"MUNC matrix for chain {i} has {int(non_finite[k])} non-finite entries")
+        return {"diagnostics": diagnostics, "floors": floors}
+
     def export(self, what: int):
         L.check(self._lib.csr_batch_export(self._ctx, int(what)))
 

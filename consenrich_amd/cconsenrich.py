@@ -35,6 +35,7 @@ __all__ = [
     "cstateShrinkInitialSums", "cstateShrinkMixtureEMStep", "cstateShrinkMixtureEMStepPrepared", "cstateShrinkMixturePosterior",
     "cstateShrinkMixturePosteriorPrepared",
     "cMuncObservationMomentSeedPass", "cMuncSmoothDenseLocalEvidence",
+    "cEvalPSplineLogVarianceTrend", "cFinalizeMuncEBTrack",
 ]
 
 
@@ -643,6 +644,8 @@ from .ess import cEstimateEffectiveSampleSize  # noqa: E402,F401
 
 # dense observation-variance seed natives (pyx:4843-5351, 5577-5741), implemented in consenrich_amd/munc.py
 from .munc import cMuncObservationMomentSeedPass, cMuncSmoothDenseLocalEvidence  # noqa: E402,F401
+# the pooled trend's evaluation and the finalisation of a track (pyx:5364-5544, 5761-5894), implemented in consenrich_amd/munc_track.py
+from .munc_track import cEvalPSplineLogVarianceTrend, cFinalizeMuncEBTrack  # noqa: E402,F401
 
 # dependence span from the per-chromosome matrices (pyx:3360-4120), implemented in consenrich_amd/depspan.py
 from .depspan import cchooseDependenceSpan  # noqa: E402,F401

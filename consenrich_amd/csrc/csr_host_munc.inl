@@ -247,6 +247,21 @@ extern "C" int csr_batch_munc_seed_begin(csr_ctx *c, const unsigned char *chain_
     return 0;
 }
 
+// the arrays of the finished tracks (csr_host_munc_track.inl) exist from their first use: the prior track is zero, the raw count
+// floor NaN ("missing") until written
+static int munc_track_array(csr_ctx *c, int32_t id) {
+    BatchState::MuncSeed &S = c->seed;
+    if (id == CSR_MUNC_SEED_PRIOR && !S.prior) {
+        CHECK(dalloc(c, &S.prior, c->Npad));
+        HIPOK(hipMemsetAsync(S.prior, 0, 4 * (size_t)c->Npad, c->stream));
+    }
+    if (id == CSR_MUNC_SEED_TRACK_FLOOR && !S.trackFloor) {
+        CHECK(dalloc(c, &S.trackFloor, c->m * c->Npad));
+        HIPOK(hipMemsetD32Async((hipDeviceptr_t)S.trackFloor, 0x7fc00000, (size_t)(c->m * c->Npad), c->stream));
+    }
+    return 0;
+}
+
 // the device array behind a CSR_MUNC_SEED_* id; *perCell: (m, n), else (n); *bytes: element size
 static int munc_seed_array(csr_ctx *c, int32_t id, void **ptr, bool *perCell, size_t *bytes) {
     BatchState::MuncSeed &S = c->seed;
@@ -266,6 +281,8 @@ static int munc_seed_array(csr_ctx *c, int32_t id, void **ptr, bool *perCell, si
         case CSR_MUNC_SEED_G: *ptr = S.g; *perCell = false; break;
         case CSR_MUNC_SEED_GVAR: *ptr = S.gvar; *perCell = false; break;
         case CSR_MUNC_SEED_EXCLUDE: *ptr = S.exclude; *perCell = false; *bytes = 1; break;
+        case CSR_MUNC_SEED_PRIOR: *ptr = S.prior; *perCell = false; break;
+        case CSR_MUNC_SEED_TRACK_FLOOR: *ptr = S.trackFloor; break;
         default: return fail("bad seed array id %d", id);
     }
     if (!*ptr) return fail("seed array %d is not in use (csr_batch_munc_seed_begin)", id);
@@ -275,6 +292,7 @@ static int munc_seed_copy(csr_ctx *c, int32_t chain, int32_t id, void *host, boo
     CHECK(munc_need_seed(c));
     CHECK(check_chain(c, chain));
     if (!host) return fail("null host buffer");
+    if (up && (id == CSR_MUNC_SEED_PRIOR || id == CSR_MUNC_SEED_TRACK_FLOOR)) CHECK(munc_track_array(c, id));
     void *dev;
     bool perCell;
     size_t eb;
@@ -431,6 +449,34 @@ extern "C" int csr_batch_munc_seed_stats(csr_ctx *c, csr_munc_seed_stats *out) {
     return 0;
 }
 
+// The counting selection of order statistics of float32 cells (k_munc_rank_count): want[2 s + r] is the 0-based rank of statistic
+// r of slot s, ans[2 s + r] its order key (munc_order_value gives the float's bits), found bit by bit from the top in 32 passes
+// over the cells.  Slots are the nChains chains of dOff / dLen with all their tracks (perTrack 0) or every (chain, track) row by
+// itself (perTrack 1, slot chain * m + track); exclude / finiteOnly leave cells out.  dTrial / dCount: 2 words per slot
+static int munc_rank_select(csr_ctx *c, const char *scope, const float *x, int64_t rowStride, int m, const unsigned char *exclude,
+                            int perTrack, int finiteOnly, const int64_t *dOff, const int64_t *dLen, int nChains, int64_t longest, unsigned int *dTrial,
+                            unsigned long long *dCount, const std::vector<unsigned long long> &want, std::vector<unsigned int> &ans) {
+    const size_t words = want.size();
+    std::vector<unsigned long long> cnt(words);
+    std::vector<unsigned int> trial(words);
+    ans.assign(words, 0u);
+    const int64_t perBlock = 256 * (int64_t)MUNC_RANK_ITEMS;
+    const dim3 grid((unsigned)std::max<int64_t>((longest + perBlock - 1) / perBlock, 1), (unsigned)m, (unsigned)nChains);
+    Scope sc(c, scope);
+    for (int bit = 31; bit >= 0; --bit) {
+        for (size_t r = 0; r < words; ++r) trial[r] = ans[r] | ((bit ? (1u << bit) : 1u) - 1u);
+        HIPOK(hipMemcpyAsync(dTrial, trial.data(), 4 * words, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemsetAsync(dCount, 0, 8 * words, c->stream));
+        CHECK(launch(c, nullptr, "k_munc_rank_count", k_munc_rank_count, grid, dim3(256), 0, c->stream, x, rowStride, dOff, dLen,
+                     (const unsigned int *)dTrial, dCount, exclude, perTrack, finiteOnly));
+        HIPOK(hipMemcpyAsync(cnt.data(), dCount, 8 * words, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        for (size_t r = 0; r < words; ++r)
+            if (cnt[r] <= want[r]) ans[r] |= 1u << bit;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // `_updateSeedBackground` (consenrich.py:7688-7777) from the resident arrays, after a seed pass and before the swap: the
 // background solve of csr_batch_background_update fed with the seed's per-cell weights (CSR_BG_SEED_WEIGHTS: float32 of
@@ -505,8 +551,8 @@ extern "C" int csr_batch_munc_seed_background(csr_ctx *c, const csr_bg_cfg *cfg_
             }
         }
         // q99 of the current total: ranks floor((N - 1) 0.99) and the next one, NumPy's lerp
-        std::vector<unsigned long long> want(2 * (size_t)ns), cnt(2 * (size_t)ns);
-        std::vector<unsigned int> ans(2 * (size_t)ns, 0u), trial(2 * (size_t)ns);
+        std::vector<unsigned long long> want(2 * (size_t)ns);
+        std::vector<unsigned int> ans;
         std::vector<double> frac((size_t)ns);
         for (int k = 0; k < ns; ++k) {
             const int64_t N = c->m * c->chains[S.idx[k]].n;
@@ -515,22 +561,8 @@ extern "C" int csr_batch_munc_seed_background(csr_ctx *c, const csr_bg_cfg *cfg_
             want[2 * k + 1] = (unsigned long long)std::min<int64_t>((int64_t)fl + 1, N - 1);
             frac[k] = vi - fl;
         }
-        const int64_t perBlock = 256 * (int64_t)MUNC_RANK_ITEMS;
-        const dim3 grid((unsigned)std::max<int64_t>((S.longest + perBlock - 1) / perBlock, 1), (unsigned)c->m, (unsigned)ns);
-        {
-            Scope sc(c, "munc_g_q99_select");
-            for (int bit = 31; bit >= 0; --bit) {
-                for (size_t r = 0; r < trial.size(); ++r) trial[r] = ans[r] | ((bit ? (1u << bit) : 1u) - 1u);
-                HIPOK(hipMemcpyAsync(S.rankTrial, trial.data(), 4 * trial.size(), hipMemcpyHostToDevice, c->stream));
-                HIPOK(hipMemsetAsync(S.rankCount, 0, 8 * cnt.size(), c->stream));
-                CHECK(launch(c, nullptr, "k_munc_rank_count", k_munc_rank_count, grid, dim3(256), 0, c->stream, (const float *)S.total[S.cur],
-                             c->Npad, (const int64_t *)S.dOff, (const int64_t *)S.dLen, (const unsigned int *)S.rankTrial, S.rankCount));
-                HIPOK(hipMemcpyAsync(cnt.data(), S.rankCount, 8 * cnt.size(), hipMemcpyDeviceToHost, c->stream));
-                HIPOK(hipStreamSynchronize(c->stream));
-                for (size_t r = 0; r < ans.size(); ++r)
-                    if (cnt[r] <= want[r]) ans[r] |= 1u << bit;
-            }
-        }
+        CHECK(munc_rank_select(c, "munc_g_q99_select", S.total[S.cur], c->Npad, (int)c->m, nullptr, 0, 0, S.dOff, S.dLen, ns, S.longest, S.rankTrial,
+                               S.rankCount, want, ans));
         for (int k = 0; k < ns; ++k) {
             float fa, fb;
             const unsigned int ua = munc_order_value(ans[2 * k]), ub = munc_order_value(ans[2 * k + 1]);

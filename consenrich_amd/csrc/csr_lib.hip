@@ -23,6 +23,7 @@
 #include "csr_depspan.h"
 #include "csr_shrink.h"
 #include "csr_munc.h"
+#include "csr_munc_track.h"
 #include "csr_step_groups.h"
 #include "csr_chain_tracks.h"
 
@@ -379,6 +380,9 @@ struct BatchState {
         double bgPad = 0.0;
         bool bgUseWeights = true;
         csr_munc_seed_stats stats{};
+        // finished tracks (csr_host_munc_track.inl), each from dalloc at its first use: the prior variance track (per interval),
+        // the caller's raw count floor with its NaNs ((m, Npad)) and the finished track before it becomes the batch's munc
+        float *prior = nullptr, *trackFloor = nullptr, *track = nullptr;
     } seed;
     int exportSignal = 0;       // CSR_SIGNAL_*: what the export stages read as signal (csr_batch_set_export_signal)
     // ROCCO's work arrays without presence (csr_host_rocco.inl): backtrace words, per-chain maxima and flags; its growable work
@@ -993,3 +997,4 @@ static int launch(csr_ctx *c, const char *scope, const char *what, void (*kernel
 #include "csr_host_depspan.inl"
 #include "csr_host_shrink.inl"
 #include "csr_host_munc.inl"
+#include "csr_host_munc_track.inl"

@@ -459,19 +459,27 @@ __host__ __device__ __forceinline__ unsigned int munc_order_value(unsigned int k
 // counts[2 c + r] += #cells of chain c whose order key is <= trial[2 c + r]: one pass of the bit-by-bit selection of two order
 // statistics of the (m, n) cells of `x`.  grid (ceil(longest /
 // (256 * MUNC_RANK_ITEMS)), m, nChains); a lane counts MUNC_RANK_ITEMS cells, the workgroup folds its lanes and adds once per
-// rank (integer atomics only: a few thousand per pass and chain instead of one per wavefront of cells)
+// rank (integer atomics only: a few thousand per pass and chain instead of one per wavefront of cells).
+// perTrack: the two order statistics are those of every (chain, track) row by itself, slot c * m + track instead of c (the
+// blacklist floor of csr_munc_track.h); exclude (per interval, or nullptr): cells of intervals with a set byte are left out;
+// finiteOnly: so are cells that are not finite
 constexpr int MUNC_RANK_ITEMS = 16;
 __global__ __launch_bounds__(256) void k_munc_rank_count(const float *x, int64_t rowStride, const int64_t *chainOff, const int64_t *chainLen,
-                                                         const unsigned int *trial, unsigned long long *counts) {
+                                                         const unsigned int *trial, unsigned long long *counts,
+                                                         const unsigned char *exclude, int perTrack, int finiteOnly) {
     const int c = blockIdx.z;
     const int64_t n = chainLen[c];
     const float *row = x + (int64_t)blockIdx.y * rowStride + chainOff[c];
-    const unsigned int t0 = trial[2 * c], t1 = trial[2 * c + 1];
+    const unsigned char *ex = exclude ? exclude + chainOff[c] : nullptr;
+    const int64_t slot = perTrack ? (int64_t)c * gridDim.y + blockIdx.y : c;
+    const unsigned int t0 = trial[2 * slot], t1 = trial[2 * slot + 1];
     unsigned int c0 = 0, c1 = 0;
     for (int it = 0; it < MUNC_RANK_ITEMS; ++it) {
         const int64_t i = ((int64_t)blockIdx.x * MUNC_RANK_ITEMS + it) * 256 + threadIdx.x;
-        if (i < n) {
-            const unsigned int key = munc_order_key(__float_as_uint(row[i]));
+        if (i < n && !(ex && ex[i] != 0)) {
+            const float v = row[i];
+            if (finiteOnly && !(__builtin_fabsf(v) <= 3.402823466e+38f)) continue;
+            const unsigned int key = munc_order_key(__float_as_uint(v));
             c0 += key <= t0 ? 1u : 0u;
             c1 += key <= t1 ? 1u : 0u;
         }
@@ -485,8 +493,8 @@ __global__ __launch_bounds__(256) void k_munc_rank_count(const float *x, int64_t
     __syncthreads();
     if (threadIdx.x == 0) {
         const unsigned int s0 = part[0][0] + part[0][1] + part[0][2] + part[0][3], s1 = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-        if (s0) atomicAdd(&counts[2 * c], (unsigned long long)s0);
-        if (s1) atomicAdd(&counts[2 * c + 1], (unsigned long long)s1);
+        if (s0) atomicAdd(&counts[2 * slot], (unsigned long long)s0);
+        if (s1) atomicAdd(&counts[2 * slot + 1], (unsigned long long)s1);
     }
 }
 

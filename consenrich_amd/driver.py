@@ -51,6 +51,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib as L
+from . import munc_track as MT
 from .batch import DeviceBatch
 
 
@@ -964,3 +965,37 @@ def munc_seed_batch(batch: DeviceBatch, *, pad: float, window: int, passes: int 
             rec["seed_mean"] = batch.download(i, "xs")[:, 0].astype(np.float64)
         out.append(rec)
     return out
+
+
+def munc_track_batch(batch: DeviceBatch, *, block_intervals: int, fit_trend, dependence_multiplier: float = 2.0, chain_index=None,
+                     trigamma=None, count_floor=None, floor: float = 1.0e-6, cap=None, use_eb: bool = True,
+                     blacklist_quantile: float = 0.05, chains=None) -> dict:
+    """From the seed loop's resident arrays to the finished `matrixMunc` in the batch's own munc, after `munc_seed_batch`: no
+    (m, n) array crosses the bus (but the caller's raw `count_floor`, on its way in).  In this order:
+      1. `munc_block_sums`: the block records of consenrich.py:7981-8040;
+      2. `munc_track.pooled_block_rows` over all taken chains (dependence_multiplier: the reference's
+         muncTrendBlockDependenceMultiplier; chain_index, trigamma: see there);
+      3. `fit_trend(pooled)`: the caller's host fit on the pooled rows.  It returns a dict with
+           "trend"              (knots, beta, degree, xMin, xMax), or an object with those attributes: the `trend` of the
+                                reference's `fitPooledMuncVarianceTrend` (a `fitPSplineLogVarianceTrend` result);
+           "replicate_factors"  one per sample, its `replicateVarianceFactors` (None: ones);
+           "nu0"                per sample or scalar: `EB_computePooledPriorStrength` (the reference's EB_pooledNu0);
+           "nuL"                per sample or scalar: the effective Nu_L of the ESS scan (EB_effectiveNuL);
+      4. `munc_prior_track` with the trend (floor / cap: the reference's varianceFloorForTrend and maxR);
+      5. `munc_track_finish`.
+    chains: per-chain booleans that keep chains (fold chains, say) out of the pool and of the result; None: the seed loop's.
+    Returns {"pooled": the pooled rows, "fit": what fit_trend returned, "diagnostics", "floors": of `munc_track_finish`}.
+    With use_eb=False the fit and the prior track are skipped (the reference's no-EB branch)."""
+    sums = batch.munc_block_sums(block_intervals, chains=chains)
+    pooled = MT.pooled_block_rows(sums, chain_index=chain_index, dependence_multiplier=dependence_multiplier, trigamma=trigamma)
+    fit = None
+    if use_eb:
+        fit = fit_trend(pooled)
+        for key in ("trend", "nu0", "nuL"):
+            if key not in fit:
+                raise ValueError(f"fit_trend must return {key!r}")
+        batch.munc_prior_track(fit["trend"], floor=floor, cap=cap, chains=chains)
+    done = batch.munc_track_finish(fit["nuL"] if use_eb else 0.0, fit["nu0"] if use_eb else 0.0,
+                                   replicate_factors=fit.get("replicate_factors") if use_eb else None, count_floor=count_floor,
+                                   floor=floor, cap=cap, use_eb=use_eb, blacklist_quantile=blacklist_quantile, chains=chains)
+    return {"pooled": pooled, "fit": fit, "diagnostics": done["diagnostics"], "floors": done["floors"]}

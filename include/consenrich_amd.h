@@ -1173,7 +1173,9 @@ int csr_munc_smooth_local(int64_t m, int64_t n, const float *local, int64_t wind
 enum {
     CSR_MUNC_SEED_TOTAL = 0, CSR_MUNC_SEED_LOCAL, CSR_MUNC_SEED_RHO, CSR_MUNC_SEED_OMEGA, CSR_MUNC_SEED_G, CSR_MUNC_SEED_GVAR,
     CSR_MUNC_SEED_WEIGHT, CSR_MUNC_SEED_COUNT_FLOOR, CSR_MUNC_SEED_EXCLUDE, CSR_MUNC_SEED_SMOOTH, CSR_MUNC_SEED_TOTAL_NEXT,
-    CSR_MUNC_SEED_RHO_NEXT, CSR_MUNC_SEED_OMEGA_NEXT
+    CSR_MUNC_SEED_RHO_NEXT, CSR_MUNC_SEED_OMEGA_NEXT,
+    CSR_MUNC_SEED_PRIOR,        /* (n) float32: the prior variance track (csr_batch_munc_prior_track, or uploaded); zero before */
+    CSR_MUNC_SEED_TRACK_FLOOR   /* (m, n) float32: the caller's RAW count floor, NaN = missing, for csr_batch_munc_track_finish */
 };
 /* total := the batch's resident munc, omega = rho = 1, everything else 0; chain_mask (n_chains bytes or NULL = all): the chains
  * the loop takes.  use_count_floor / use_exclude: the pass reads COUNT_FLOOR, the rolling mean reads EXCLUDE (per interval). */
@@ -1200,6 +1202,71 @@ int csr_batch_munc_seed_stats(csr_ctx *ctx, csr_munc_seed_stats *out);
 int csr_batch_munc_seed_background(csr_ctx *ctx, const csr_bg_cfg *cfg, double pad, int32_t use_weights, int32_t g_mode, csr_bg_out *out);
 /* the last update's float64 weight / rhs tracks of one chain and the float64 sums of the float64 weights (any may be NULL) */
 int csr_batch_munc_seed_background_tracks(csr_ctx *ctx, int32_t chain, double *weight, double *rhs, double *weight64);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Finished observation-variance tracks: what lies between csr_batch_munc_seed_finish and a finished matrixMunc, per cell.
+ *   block summaries   consenrich.py:7981-8040: per (sample, block) the count of valid cells and np.sum of q, q * predictor,
+ *                     q * evidence and q * q over them (NumPy's order), per block the non-excluded intervals
+ *   prior track       `cEvalPSplineLogVarianceTrend` (pyx:5761-5894) on the predictor sign(x) log1p(|x|) of a mean track
+ *   finalisation      `cFinalizeMuncEBTrack` (pyx:5364-5544) as `getMuncTrack` (core.py:8390-8880) chains it, then
+ *                     `applyBlacklistMuncFloor` (core.py:7183-7222) and the clamp of consenrich.py:9100-9113
+ * Everything equals the reference bit for bit except what passes through log1p (sum q * predictor) and exp (the prior track).
+ * The P-spline is data: knots (n_knots), beta (n_basis), degree, x_min, x_max.  degree < 0, n_knots = 0 or n_basis = 0 is the
+ * reference's constant fallback (evaluated on the host with the C library's exp).  Otherwise degree <= 5, n_basis <= 512,
+ * n_basis >= degree + 1 and n_knots >= n_basis + degree + 1 (the reference reads past its arrays where the last two fail), else
+ * CSR_ERR_VALUE.
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct csr_munc_block_rec {
+    int64_t valid;              /* cells of the block that pass `validResponse` */
+    double q, qp, qe, qq;       /* np.sum over them of q, q * predictor, q * evidence, q * q */
+} csr_munc_block_rec;
+typedef struct csr_munc_track_prm {     /* one per track */
+    double nu_local, nu_prior, posterior;   /* posterior: filled by the library (nu_local + nu_prior) */
+    double factor;                          /* replicate variance factor */
+    int32_t scale, reserved_;               /* filled by the library: |factor - 1| > 1e-8 */
+} csr_munc_track_prm;
+typedef struct csr_munc_track_out {     /* one per (chain, track) */
+    int64_t invalid_local, invalid_prior, invalid_count_floor;     /* the lowest invalid index of each kind, -1: none */
+    int64_t support, floor_finite, floor_added, floor_missing;     /* the native's counters */
+    double blacklist_floor;                                         /* the track's blacklist floor (the base floor where none applies) */
+} csr_munc_track_out;
+/* host arrays (default context).  evidence / weight: C-order (m, n) float32; exclude: n bytes or NULL; mean: n float64 (the
+ * predictor is taken of it); recs: (m, blocks) records, included: blocks, with blocks as for the resident form below */
+int csr_munc_block_sums(int64_t m, int64_t n, const float *evidence, const float *weight, const unsigned char *exclude,
+                        const double *mean, int64_t block_intervals, csr_munc_block_rec *recs, int64_t *included);
+/* out (n) float32 */
+int csr_munc_eval_pspline(int64_t n, const double *predictor, const double *knots, int64_t n_knots, const double *beta,
+                          int64_t n_basis, int32_t degree, double x_min, double x_max, double log_floor, double log_cap, float *out);
+/* one track of n intervals; prior / count_floor may be NULL (use_eb 0 / no floor: NaN = missing, pyx:5423-5438);
+ * prm->nu_local / nu_prior are read with use_eb.  out (n) float32 and the counters are valid where no index of *res is >= 0 */
+int csr_munc_finalize_track(int64_t n, const float *local, const float *prior, const float *count_floor,
+                            const csr_munc_track_prm *prm, double floor, double cap, int32_t use_eb, float *out,
+                            csr_munc_track_out *res);
+/* `applyBlacklistMuncFloor` with a non-negative base floor on a C-order (m, n) float32 matrix, in place; mask: n bytes;
+ * floors: m float64.  The quantile of a row is np.quantile's on a float32 row (NumPy 2: float32 index arithmetic and lerp) */
+int csr_munc_blacklist_floor(int64_t m, int64_t n, float *munc, const unsigned char *mask, double base_floor, double quantile,
+                             double *floors);
+/* Resident forms, after csr_batch_munc_seed_finish.  chain_mask: n_chains bytes or NULL = the chains of the seed loop; a chain
+ * outside the seed loop is an error.  Blocks: max(2, block_intervals) intervals (at most 2048), a last block shorter than 2 is
+ * dropped.  recs: per taken chain, in order, (m, blocks of the chain) records; included: per taken chain its blocks; n_recs /
+ * n_blocks: the sizes the caller computed (checked).  Reads SMOOTH, WEIGHT, EXCLUDE and xs[:,0] of the resident smoothed fit,
+ * which must still be resident (an error before any launch otherwise). */
+int csr_batch_munc_block_sums(csr_ctx *ctx, int64_t block_intervals, const unsigned char *chain_mask, csr_munc_block_rec *recs,
+                              int64_t n_recs, int64_t *included, int64_t n_blocks);
+/* PRIOR := the trend on the predictor of xs[:,0] of the resident smoothed fit, for the taken chains */
+int csr_batch_munc_prior_track(csr_ctx *ctx, const unsigned char *chain_mask, const double *knots, int64_t n_knots,
+                               const double *beta, int64_t n_basis, int32_t degree, double x_min, double x_max, double log_floor,
+                               double log_cap);
+/* Per (track, interval) of the taken chains: local = SMOOTH, prior = PRIOR (scaled by the track's factor), the native's
+ * shrinkage with prm[track], the count floor TRACK_FLOOR (use_count_floor; `_coerceMuncCountModelVarianceFloor`: not finite =
+ * missing, negative = invalid), then the blacklist floor of the seed loop's EXCLUDE mask (base_floor, quantile; skipped without
+ * a mask) and the clamp to [float32(clamp_lo), float32(clamp_hi)] (clamp_hi <= 0: no upper clamp).  out: (taken chains, m)
+ * records; non_finite: per taken chain.  Where a record has an invalid index, or non_finite is not zero, NOTHING of the batch
+ * has changed and the caller raises the reference's error.  Otherwise the result is the batch's own munc for the taken chains
+ * (as after csr_batch_munc_seed_working: the resident fit results are dropped). */
+int csr_batch_munc_track_finish(csr_ctx *ctx, const unsigned char *chain_mask, csr_munc_track_prm *prm, double floor, double cap,
+                                int32_t use_eb, int32_t use_count_floor, double base_floor, double quantile, double clamp_lo,
+                                double clamp_hi, csr_munc_track_out *out, int64_t *non_finite);
 
 typedef struct csr_run_stats {
     int64_t blocks;             /* speculative blocks in the batch */
